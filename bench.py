@@ -16,7 +16,11 @@ completed when the timed region ends).  Workload at every N: the configuration B
 configs[2]: ViT-B/14 518x518, 100 queries, batch 64 -- which fits ONE MI355X, so each GPU runs a full batch of 64 (weak
 scaling: global batch 64 N).  At N > 1 the same line also carries `global64_sharded`: configs[2] split literally, 64 / N
 images per GPU.
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0: metric / value / unit / higher_is_better / dtype, ms_per_step (one timed step, K of them) and the
+configuration.  A plain run does only that: set-up, W warm-up steps, the K timed steps, the line.
+`--dump-outputs DIR` also writes the last timed step's detections (at N > 1 the gathered buffer of rank 0) as DIR/pred_logits.npy and
+DIR/pred_boxes.npy, float32; the inputs are seeded, so two builds can be compared output for output.
+`--full` adds everything beyond the headline figure, each leg taking runs of its own after the timed region:
   roofline     : the dominant kernel class (bf16 MFMA GEMM) -- ALGORITHMIC FLOPs (2 M N K per launch) / its summed launch
                  time, measured with HIP events on the launch stream by the library's profile mode over extra forwards of the
                  same step, right after the timed region;
@@ -29,7 +33,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
                  headline (N = 1 only);
   also         : BASELINE configs[1] (ViT-B/14 224x224, batch 32) in both modes, configs[3] (ViT-L/14 518x518 bf16, 16 images) and
                  configs[4] (ViT-g/14 518x518 fp8 MFMA, 32 images) on their per-GPU shards, and `train_step`: the native train()-mode step
-                 (section 8 row f1) against the autograd composite on the same frozen prefix (N = 1 only).
+                 (section 8 row f1) against the autograd composite on the same frozen prefix (N = 1 only);
+  N > 1        : `global64_sharded`, the check that the gathered buffer holds every rank's detections, and every rank's shard against the
+                 CPU oracle (`per_rank.gpu_vs_oracle`; a rank outside its gate fails the job).
 Other workloads / modes: --workload {vits224,vitb224,vitl518,vitg518}, --precision {bf16,bf16x3,fp16x2,fp32,fp8}.
 `--rehearse-cpu` swaps the model for a stub on the CPU with gloo: it exercises launcher, sharding, barriers, timing and the
 overlapped gather without a GPU (tests/test_dist_cpu.py) and labels its line as a rehearsal -- never a measurement.
@@ -71,12 +77,18 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="vitb518", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp8", "bf16x3", "fp16x2"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip parity_gated_mode / also / global64_sharded")
+    ap.add_argument("--full", action="store_true", help="also the legs beyond the headline: roofline, cpu_baseline, parity_gated_mode / "
+                    "fp16x2_mode / also, global64_sharded and the N > 1 gather / per-rank oracle checks")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline (and the legs after it)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without parity_gated_mode / also / global64_sharded")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's detections as DIR/pred_logits.npy, DIR/pred_boxes.npy")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a captured hipGraph")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: all-gather on the compute stream instead of the side stream")
     ap.add_argument("--rehearse-cpu", action="store_true", help="CPU/gloo rehearsal of the control flow with a stub model (not a measurement)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def build(name, queries, precision, device):
@@ -239,6 +251,20 @@ def make_images(B_local, R, lo, device):
     for i in range(B_local):
         x[i] = torch.from_numpy(synth.uniform01(0, f"pixel_values.{R}x{R}.{lo + i}", (3, R, R))).to(device)
     return x
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, det, C):
+    """--dump-outputs: the packed detections [B, Q, C+4] a caller of forward_packed() receives, split as forward() returns them
+    (pred_logits [B, Q, C], pred_boxes [B, Q, 4]), float32; beyond DUMP_BYTES only the first images"""
+    import numpy as np
+    d = det.float().cpu().numpy()
+    d = d[:max(1, DUMP_BYTES // (d[0].size * 4))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pred_logits.npy"), np.ascontiguousarray(d[..., :C]))
+    np.save(os.path.join(out_dir, "pred_boxes.npy"), np.ascontiguousarray(d[..., C:]))
 
 
 class _StubModel:
@@ -485,9 +511,11 @@ def worker(a):
     global_batch = B_local * world
     ips = global_batch * a.steps / dt
     per_rank = timed.per_rank
+    if a.dump_outputs and rank == 0:      # before any --full leg launches more work on the device
+        dump_outputs(a.dump_outputs, st.last_gathered() if world > 1 else st.last_det, C)
     gather_ok = None
     rank_check = None
-    if world > 1:       # the gathered buffer holds every rank's detections in rank order (checked on the last step's buffer)
+    if world > 1 and a.full:       # the gathered buffer holds every rank's detections in rank order (checked on the last step's buffer)
         g = st.last_gathered()
         with torch.no_grad():
             mine = model.forward_packed(x)
@@ -521,11 +549,12 @@ def worker(a):
         fpi = flops_per_image(bb, dc, R, R)
         res["config"]["gflop_per_image"] = fpi / 1e9
         res["mfma_roofline_frac_end_to_end"] = ips * fpi / (PEAK[a.precision] * world)
-        traffic, traffic_src = pmc_traffic(a.workload, a.precision, B_local)
-        res["roofline"] = roofline_leg(model, x, a.precision, a.steps, traffic, traffic_src)
+        if a.full:
+            traffic, traffic_src = pmc_traffic(a.workload, a.precision, B_local)
+            res["roofline"] = roofline_leg(model, x, a.precision, a.steps, traffic, traffic_src)
 
     # ---- N > 1: BASELINE configs[2] split literally -- global batch 64, 64 / N images per GPU (strong-scaling view)
-    if world > 1 and not a.no_extras and a.workload == "vitb518" and not a.batch and 64 % world == 0:
+    if a.full and world > 1 and not a.no_extras and a.workload == "vitb518" and not a.batch and 64 % world == 0:
         bs = 64 // world
         lo2, _ = ddist.shard_bounds(64, rank, world)
         xs = x[:bs].contiguous() if cpu else make_images(bs, R, lo2, device)
@@ -538,7 +567,7 @@ def worker(a):
             res["global64_sharded"]["mfma_roofline_frac_end_to_end"] = 64 * a.steps / dt2 * fpi / (PEAK[a.precision] * world)
         del st2
 
-    if rank == 0 and world == 1 and not cpu and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not cpu and not a.no_cpu_baseline:
         # the oracle's two images are make_pixels(2, R, R, seed=0) = images 0 and 1 of the batch
         res["cpu_baseline"], oracle_first = cpu_baseline(bb, dc, R)
         res["cpu_baseline"]["gpu_vs_oracle"] = timed_vs_oracle(st, model, x, oracle_first, C)
@@ -612,7 +641,7 @@ def worker(a):
         torch.distributed.destroy_process_group()
         # a rank whose detections left the gate, or a gathered buffer that does not hold every rank's rows, fails the whole job (every
         # rank exits non-zero: the launcher propagates the first non-zero code)
-        if not gather_ok or not rank_check["all_in_gate"]:
+        if a.full and (not gather_ok or not rank_check["all_in_gate"]):
             if rank == 0:
                 print(f"[bench] FAILED: gather_checked={gather_ok}, per-rank oracle check {rank_check}", file=sys.stderr)
             sys.exit(3)

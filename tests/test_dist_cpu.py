@@ -69,7 +69,7 @@ def test_bench_self_launches_ranks_and_gathers(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rehearse-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rehearse-cpu", "--full"],
                        capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -103,7 +103,7 @@ def test_bench_under_the_drivers_torchrun_command_four_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-                        "--rehearse-cpu", "--no-extras"], capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
+                        "--rehearse-cpu", "--full", "--no-extras"], capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -122,12 +122,38 @@ def test_bench_fails_when_a_rank_leaves_the_gate(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["BENCH_REHEARSE_BREAK_RANK"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rehearse-cpu", "--no-extras"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rehearse-cpu", "--full", "--no-extras"],
                        capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
     assert r.returncode != 0
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     ranks = j["per_rank"]["gpu_vs_oracle"]["ranks"]
     assert ranks[0]["in_gate"] and not ranks[1]["in_gate"] and not j["per_rank"]["gpu_vs_oracle"]["all_in_gate"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_gathered_output(tmp_path):
+    """without --full the line holds the headline only (no gather / oracle checks, no global64_sharded); --dump-outputs writes the
+    last timed step's gathered detections of both ranks, in rank order, split into pred_logits / pred_boxes"""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rehearse-cpu",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert j["higher_is_better"] is True and j["unit"] == "images/s" and j["dtype"] == "bf16"
+    assert "global64_sharded" not in j and j["config"]["gather_checked"] is None and j["per_rank"]["gpu_vs_oracle"] is None
+    want = bench._StubModel(100, 91).forward_packed(bench.make_images(128, 28, 0, "cpu")).numpy()
+    logits, boxes = np.load(out / "pred_logits.npy"), np.load(out / "pred_boxes.npy")
+    assert logits.dtype == np.float32 and logits.shape == (128, 100, 91) and boxes.shape == (128, 100, 4)
+    assert np.array_equal(logits, want[..., :91]) and np.array_equal(boxes, want[..., 91:])
 
 
 def test_launcher_propagates_a_failing_rank(tmp_path):

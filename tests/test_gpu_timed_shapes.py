@@ -100,6 +100,30 @@ def test_timed_vitb518_configuration_vs_reference_and_oracle(G, B, precision):
     assert torch.equal(m.forward_packed(x) if precision != "fp32" else det, det)
 
 
+def test_bench_dump_outputs_are_the_timed_detections(G, tmp_path):
+    """a plain `bench.py --dump-outputs DIR` (the headline's bf16 mode, hipGraph + micro-batches, the batch cut to 8) writes the
+    timed batch's detections: images 0-1 no further from the fp32 oracle than the bf16-faithful oracle is (x K_BF16)"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["dtype"] == "bf16" and "roofline" not in j and "cpu_baseline" not in j
+    got_l, got_b = np.load(tmp_path / "pred_logits.npy"), np.load(tmp_path / "pred_boxes.npy")
+    C = cases.vitb(100, True)[1].num_classes
+    assert got_l.dtype == np.float32 and got_l.shape == (8, 100, C) and got_b.shape == (8, 100, 4)
+    o = _oracle_vitb518()
+    ref_l, ref_b = o["f32"]["pred_logits"].numpy(), o["f32"]["pred_boxes"].numpy()
+    emu_l, emu_b = o["bf16"]["pred_logits"].numpy(), o["bf16"]["pred_boxes"].numpy()
+    el, eb = rel_l2(got_l[:2], ref_l), rel_l2(got_b[:2], ref_b)
+    print(f"bench dump bf16: rel-L2 vs fp32 oracle logits {el:.2e} boxes {eb:.2e}")
+    assert el < K_BF16 * rel_l2(emu_l, ref_l) and eb < K_BF16 * rel_l2(emu_b, ref_b)
+
+
 @pytest.mark.parametrize("variant,B,precision", [("large", 16, "bf16"), ("large", 16, "bf16x3"), ("large", 16, "fp16x2"),
                                                  ("giant", 32, "fp8")])      # large is resident from test_gpu_forward.py; ViT-g in the mode BASELINE quotes (20 s per mode)
 def test_timed_vitl_vitg_configurations_vs_reference(G, variant, B, precision):

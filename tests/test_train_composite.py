@@ -97,18 +97,26 @@ def test_dropout_is_active_in_train_mode_only():
 def test_composite_gradients_match_the_reference_backward(name):
     """G9: the .grad of every trainable parameter after the REFERENCE's own train()-mode forward + backward (dropout 0, fixed linear
     loss; tests/golden/make_goldens.py::g9_gradients) against the autograd composite's -- the backward of row f1 pinned to what
-    train.py:1101 computes, not to a restatement."""
+    train.py:1101 computes, not to a restatement.
+    The ViT-B case's gradient is ill-conditioned (three tied layers whose sampling gradient is piecewise smooth): fp32 evaluations on
+    hosts whose CPU kernels sum in another order (e.g. AVX2 instead of AVX-512 GEMM paths) land up to 6x further from the reference's
+    float64 evaluation than the reference's own fp32 one, 1.5e-2 on the worst LoRA tensor.  Its fp32 forward and loss are held to the
+    fp32 golden; its gradients are taken in float64 and held to the float64 golden (g9_grad_vitb_224_f64) at the same tolerances."""
     g = cases.golden(name)
     model_name, R, B, kw = cases.G9_CASES[name]
     m = DINOv2ObjectDetector(dino_model_name=model_name, pretrained=False, **kw)
     sd = {k: torch.from_numpy(v) for k, v in synth.detector_state_dict(m._bb_cfg, m._dc_cfg, seed=1).items()}
     m.load_state_dict(sd, strict=True)
     m.train()
-    o = m(torch.from_numpy(synth.make_pixels(B, R, R, seed=0)))
-    gl, gb = cases.g9_loss_weights(B, m._dc_cfg.num_queries, m._dc_cfg.num_classes)
-    assert rel_err(o["pred_logits"].detach().numpy(), g["pred_logits"]) < 1e-3
-    loss = (o["pred_logits"] * torch.from_numpy(gl)).sum() + (o["pred_boxes"] * torch.from_numpy(gb)).sum()
+    x = torch.from_numpy(synth.make_pixels(B, R, R, seed=0))
+    gl, gb = (torch.from_numpy(w) for w in cases.g9_loss_weights(B, m._dc_cfg.num_queries, m._dc_cfg.num_classes))
+    runs = [(g, torch.float32)] + ([(cases.golden(name + "_f64"), torch.float64)] if "vitb" in name else [])
+    for g, dt in runs:
+        m = m.to(dt)
+        o = m(x.to(dt))
+        assert rel_err(o["pred_logits"].detach().numpy(), g["pred_logits"]) < 1e-3
+        loss = (o["pred_logits"] * gl.to(dt)).sum() + (o["pred_boxes"] * gb.to(dt)).sum()
+        assert abs(float(loss.detach()) - float(g["loss"])) < 1e-3 * max(1.0, abs(float(g["loss"])))
     loss.backward()
-    assert abs(float(loss.detach()) - float(g["loss"])) < 1e-3 * max(1.0, abs(float(g["loss"])))
     worst = cases.g9_check(m, g, 2e-4, 2e-4)
     print(f"{name}: worst gradient probe error {worst[0]:.2e} ({worst[1]})")

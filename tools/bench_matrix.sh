@@ -4,7 +4,7 @@ OUT=${1:-gpurun_out/matrix.log}
 : > $OUT
 for w in vitb518 vitb224 vits224 vitl518 vitg518; do
   for p in bf16 bf16x3 fp8; do
-    timeout -k 10 400 python bench.py --workload $w --precision $p --no-cpu-baseline --no-extras --steps 20 --warmup 5 2>/dev/null | python -c "
+    timeout -k 10 400 python bench.py --workload $w --precision $p --full --no-cpu-baseline --no-extras --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
