@@ -302,6 +302,40 @@ int dod_match_cost(const float* det, int B, int Q, int C, const int64_t* labels,
                    const int32_t* gt_offsets, int G, float w_class, float w_bbox, float w_giou, float alpha, float gamma,
                    int rows_from, float* cost, void* stream);
 
+/* ---- set-prediction loss and its gradient on device (the training criterion) ----------------------------------------
+ * Replaces SetCriterion.forward, dino_detector/losses.py:204-242: the focal loss over every [B, Q, C] logit with unmatched
+ * queries as background (loss_labels :100-146), the L1 and GIoU losses of the matched boxes (loss_boxes :148-185), each
+ * divided by max(num_boxes, 1).  The Hungarian assignment arrives as a match table.  Stateless; all pointers are DEVICE
+ * pointers owned by the caller; everything is enqueued on `stream`, no hidden sync, no allocation, no atomics (results are
+ * bit-identical from run to run).
+ *   pred_logits   fp32, row r = b*Q + q at pred_logits + r * logits_row_stride (>= C): a view of the packed [B, Q, C+4]
+ *                 detections (stride C+4) is read in place
+ *   pred_boxes    fp32 (cx, cy, w, h), row r at pred_boxes + r * boxes_row_stride (>= 4); NULL = no box terms
+ *   labels        int64 [G]; gt_boxes fp32 [G, 4] cxcywh: the targets of all images, concatenated
+ *   match         int32 [M = B*Q]: the global target row matched to query r, or -1 (background).  An entry outside [0, G)
+ *                 is background; a label equal to C (the reference's dropped one-hot column) or outside [0, C] only
+ *                 removes the focal positive -- no label or entry is ever used as an address unchecked.
+ *                 NULL = row r's target is labels[r] (then G must equal B*Q): nn FocalLoss, losses.py:9-68
+ *   num_boxes     fp32 device scalar (all-reduced by the caller when distributed); NULL = 1
+ * Forward: losses = fp32[3] {loss_ce, loss_bbox, loss_giou}, unweighted.  elem_loss (nullable, fp32 [B*Q, C] dense): the
+ * un-normalised per-element focal term (FocalLoss reduction='none').  workspace: dod_set_criterion_workspace_bytes(B, Q, C)
+ * bytes (DOD_ERR_STATE if smaller).  Two launches.
+ * Backward (one launch, recomputed from the inputs): d_losses = fp32[3] upstream gradient of `losses` (weights and
+ * accumulation arrive through it); d_elem (nullable, fp32 [B*Q, C]) replaces d_losses[0] element-wise (reduction='none').
+ * Writes dense d_logits fp32 [B*Q, C] and, when pred_boxes and d_boxes are given, dense d_boxes fp32 [B*Q, 4] (zero on
+ * unmatched rows).  Tie rules are those of torch autograd on the reference formula.
+ * DOD_ERR_INVALID: a NULL required pointer, non-positive B / Q / C, negative G, a row stride below C (logits) or 4 (boxes),
+ * M != B*Q, gamma < 0. */
+size_t dod_set_criterion_workspace_bytes(int B, int Q, int C);
+int dod_set_criterion_forward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
+                              int64_t boxes_row_stride, int B, int Q, int C, const int64_t* labels, const float* gt_boxes,
+                              int G, const int32_t* match, int M, const float* num_boxes, float alpha, float gamma,
+                              float* losses, float* elem_loss, void* workspace, size_t workspace_bytes, void* stream);
+int dod_set_criterion_backward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
+                               int64_t boxes_row_stride, int B, int Q, int C, const int64_t* labels, const float* gt_boxes,
+                               int G, const int32_t* match, int M, const float* num_boxes, float alpha, float gamma,
+                               const float* d_losses, const float* d_elem, float* d_logits, float* d_boxes, void* stream);
+
 /* ---- native training step of the decoder + heads (first slice) ---------------------------------------
  * What `loss.backward()` at dino_detector/train.py:1101 needs from DETRDecoder.forward (detr_decoder.py:47-83) over the
  * weight-tied DeformableDecoderLayer (deformable_attention.py:215-268, tied at :284): a train-mode forward (dropout at the
@@ -411,8 +445,9 @@ long dod_test_counter(const char* name);
 const char* dod_version(void);
 /* ABI revision of this header: bumped whenever an exported signature or struct layout changes (round 2's dod_set_weight gained its
  * dtype argument at revision 2; revision 4 = this file: the dod_debug_* entry points left the release library, dod_test_* replaced the three
- * the tests use, the folded-LayerNorm operators arrived).  A C caller compiled against DOD_ABI_VERSION checks it once at load. */
-#define DOD_ABI_VERSION 4
+ * the tests use, the folded-LayerNorm operators arrived; revision 5: the dod_set_criterion_* entry points).  A C caller compiled against
+ * DOD_ABI_VERSION checks it once at load. */
+#define DOD_ABI_VERSION 5
 int dod_abi_version(void);
 /* Devices visible to the HIP runtime libdinodet.so is bound to (<= 0: none / error).  The host uses it to
  * verify the library shares PyTorch's HIP runtime (pointers and streams cross this ABI). */
