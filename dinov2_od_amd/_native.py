@@ -134,6 +134,8 @@ SYMBOLS = {
     "dod_preprocess": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dod_preprocess_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dod_match_cost": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P]),
+    "dod_match_assign_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "dod_match_assign": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _SZ, _P]),
     "dod_set_criterion_workspace_bytes": (_SZ, [_I, _I, _I]),
     "dod_set_criterion_forward": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _I, _I, _P, _P, _I, _P, _I, _P, _F, _F, _P, _P, _P, _SZ, _P]),
     "dod_set_criterion_backward": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _I, _I, _P, _P, _I, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P]),
@@ -159,7 +161,7 @@ SYMBOLS = {
 }
 
 _lib = None
-ABI_VERSION = 5     # include/dinodet.h DOD_ABI_VERSION
+ABI_VERSION = 6     # include/dinodet.h DOD_ABI_VERSION
 
 
 def lib():

@@ -9,7 +9,9 @@ On the GPU the three unweighted losses come from `dod_set_criterion_forward` (tw
 fixed-order sum) and their gradient from ONE `dod_set_criterion_backward` launch (include/dinodet.h, csrc/criterion.hip):
 the logits and boxes are read in place -- the views of the packed [B, Q, C+4] detections `engine.split_detections` hands
 out included -- the assignment travels as an int32 [B*Q] match table built on the host from the matcher's CPU indices and
-uploaded with one async copy, and `num_boxes` stays a device scalar: no host sync of the criterion's own.  CPU tensors take
+uploaded with one async copy, and `num_boxes` stays a device scalar: no host sync of the criterion's own.  With
+`device_assignment=True` the table comes from `matcher.match_table` instead (the device solver, bit-identical to scipy), so
+the whole call runs without a host sync; its errors wait for `check_assignment()`.  CPU tensors take
 `composite_losses`, a torch composite of the same math (the CPU test suite pins it to the reference's autograd).
 There is no fall-back: a CUDA input without the HIP library raises.
 
@@ -174,20 +176,46 @@ def match_table(indices, counts, Q, pin=False):
 class SetCriterion(nn.Module):
     """Drop-in for dino_detector.losses.SetCriterion (constructor losses.py:79-98, forward :204-242)."""
 
-    def __init__(self, matcher, num_classes, weight_dict, focal_alpha=0.25, focal_gamma=2.0):
+    def __init__(self, matcher, num_classes, weight_dict, focal_alpha=0.25, focal_gamma=2.0, device_assignment=False):
+        """device_assignment=True: the match table comes from `matcher.match_table` (the device solver, no host sync) instead of
+        scipy on the host; its errors are deferred to `check_assignment()`.  The default keeps scipy and raises at once."""
         super().__init__()
         self.matcher = matcher
         self.num_classes = num_classes
         self.weight_dict = weight_dict
         self.focal_alpha = focal_alpha
         self.focal_gamma = focal_gamma
+        if device_assignment and not callable(getattr(matcher, "match_table", None)):
+            raise TypeError(f"device_assignment needs a matcher with match_table(); {type(matcher).__name__} has none")
+        self.device_assignment = bool(device_assignment)
+        self.last_assignment_status = None
+
+    def check_assignment(self):
+        """Synchronises and raises what the host path would have raised for the last device-assigned call: IndexError when a
+        label of any image is out of range, else the scipy ValueError of the first failing image.  No-op in host mode."""
+        from .matching import ASSIGN_ERRORS, ASSIGN_LABEL
+        if self.last_assignment_status is None:
+            return
+        st = self.last_assignment_status.cpu().tolist()
+        if ASSIGN_LABEL in st:
+            exc, msg = ASSIGN_ERRORS[ASSIGN_LABEL]
+            raise exc(msg)
+        for s in st:
+            if s:
+                exc, msg = ASSIGN_ERRORS[s]
+                raise exc(msg)
 
     def forward(self, outputs, targets):
         logits, boxes = outputs["pred_logits"], outputs["pred_boxes"]
         B, Q, C = logits.shape
         if C != self.num_classes:
             raise RuntimeError(f"criterion.num_classes = {self.num_classes} but pred_logits has {C} classes")
-        indices = self.matcher(outputs, targets)
+        if self.device_assignment:
+            if not logits.is_cuda:
+                raise ValueError("device_assignment needs CUDA outputs")
+            match, self.last_assignment_status = self.matcher.match_table(outputs, targets)
+        else:
+            indices = self.matcher(outputs, targets)
         dev = logits.device
         counts = [int(len(t["labels"])) for t in targets]
         nb = torch.full((1,), float(sum(counts)), dtype=torch.float32, device=dev)
@@ -199,11 +227,14 @@ class SetCriterion(nn.Module):
         else:
             labels = torch.zeros(0, dtype=torch.int64, device=dev)
             gt = torch.zeros((0, 4), dtype=torch.float32, device=dev)
-        table = match_table(indices, counts, Q, pin=logits.is_cuda)
-        if logits.is_cuda:
+        if self.device_assignment:                           # the table is already on the device
+            losses = native_losses(logits, boxes, labels, gt, match, nb, self.focal_alpha, self.focal_gamma)
+        elif logits.is_cuda:
+            table = match_table(indices, counts, Q, pin=True)
             match = table.to(dev, non_blocking=True)         # pinned host table: one async copy
             losses = native_losses(logits, boxes, labels, gt, match, nb, self.focal_alpha, self.focal_gamma)
         else:
+            table = match_table(indices, counts, Q)
             losses = composite_losses(logits, boxes, labels, gt, table, nb, self.focal_alpha, self.focal_gamma)
         out = {k: losses[n] for n, k in enumerate(LOSS_KEYS)}
         return {k: self.weight_dict[k] * out[k] if k in self.weight_dict else out[k] for k in out}

@@ -9,6 +9,10 @@ No CPU fallback for the cost computation: without the HIP library this module ra
 Reference behaviour kept on purpose: the reference builds each image's matrix over ALL B*Q predictions and then keeps
 `C[:num_queries]` (matching.py:102) -- the rows of image 0 for every image.  `per_image_rows=False` (default) reproduces
 that; `per_image_rows=True` matches each image's targets against its own predictions.
+
+`HungarianMatcher.match_table` is the opt-in device path: the same costs, then `assign` (`dod_match_assign`, a device
+restatement of scipy's solver whose result is bit-identical to scipy's) writes the criterion's match table on the GPU, with
+no host sync.  Errors become per-image status codes the caller reads later (`losses.SetCriterion.check_assignment`).
 """
 import numpy as np
 import torch
@@ -35,6 +39,41 @@ def match_cost(det, num_classes, labels, gt_boxes, offsets, cost_class=1.0, cost
                                        nat.ptr(offsets), G, float(cost_class), float(cost_bbox), float(cost_giou),
                                        float(focal_alpha), float(focal_gamma), int(rows_from), nat.ptr(cost), nat.stream_ptr()))
     return cost[: G * Q]
+
+
+# dod_match_assign status codes (include/dinodet.h) -> what the host path raises for that image
+ASSIGN_OK, ASSIGN_INVALID, ASSIGN_INFEASIBLE, ASSIGN_LABEL = 0, 1, 2, 3
+ASSIGN_ERRORS = {ASSIGN_INVALID: (ValueError, "matrix contains invalid numeric entries"),
+                 ASSIGN_INFEASIBLE: (ValueError, "cost matrix is infeasible"),
+                 ASSIGN_LABEL: (IndexError, "target label out of range")}
+
+
+def assign(cost, offsets, num_queries, labels=None, num_classes=None):
+    """scipy's linear_sum_assignment of every image's [Q, n_b] matrix in the flat fp32 CUDA buffer `cost` (image b at
+    offsets[b] * Q, as `match_cost` writes it), on the device.  offsets: int32 CUDA [B+1]; labels (optional, int64 CUDA
+    [G]) are checked against [0, num_classes).  Returns (match int32 [B*Q]: offsets[b] + target or -1, status int32 [B]:
+    ASSIGN_*), both CUDA tensors; nothing is read back."""
+    Q = int(num_queries)
+    if not (cost.is_cuda and cost.dtype == torch.float32):
+        raise ValueError("cost must be a CUDA fp32 tensor")
+    if not (offsets.is_cuda and offsets.dtype == torch.int32 and offsets.dim() == 1 and offsets.numel() >= 2):
+        raise ValueError("offsets must be a CUDA int32 tensor [B+1]")
+    if Q <= 0 or cost.numel() % Q:
+        raise ValueError(f"cost holds {cost.numel()} entries, not a multiple of num_queries = {Q}")
+    B, G = offsets.numel() - 1, cost.numel() // Q
+    if labels is not None:
+        if num_classes is None or labels.numel() != G:
+            raise ValueError("labels need num_classes and one entry per target")
+        labels = labels.to(cost.device, torch.int64).contiguous()
+    cost, offsets = cost.contiguous(), offsets.contiguous()
+    L = nat.lib()
+    ws = torch.empty(L.dod_match_assign_workspace_bytes(B, Q, G), dtype=torch.uint8, device=cost.device)
+    match = torch.empty(B * Q, dtype=torch.int32, device=cost.device)
+    status = torch.empty(B, dtype=torch.int32, device=cost.device)
+    nat.check(L.dod_match_assign(nat.ptr(cost) if G else None, nat.ptr(offsets), B, Q, G, nat.ptr(labels),
+                                 int(num_classes) if labels is not None else 0, nat.ptr(match), nat.ptr(status), nat.ptr(ws),
+                                 ws.numel(), nat.stream_ptr()))
+    return match, status
 
 
 class HungarianMatcher(nn.Module):
@@ -82,6 +121,36 @@ class HungarianMatcher(nn.Module):
             i, j = linear_sum_assignment(Cm)                     # matching.py:105
             out.append((torch.as_tensor(i, dtype=torch.int64), torch.as_tensor(j, dtype=torch.int64)))
         return out
+
+    @torch.no_grad()
+    def match_table(self, outputs, targets):
+        """The criterion's match table straight from the device: (match int32 [B*Q], status int32 [B]) CUDA tensors, equal to
+        `losses.match_table(self(outputs, targets), counts, Q)` wherever `forward` returns.  Nothing here synchronises: the
+        label check is status 3 and scipy's errors are statuses 1 / 2 (ASSIGN_ERRORS), for the caller to read later."""
+        logits, boxes = outputs["pred_logits"], outputs["pred_boxes"]
+        bs, num_queries, C = logits.shape
+        dev = logits.device
+        if not logits.is_cuda:
+            raise ValueError("match_table needs CUDA outputs")
+        det = torch.cat([logits, boxes], dim=-1).float().contiguous()
+        counts, lab, box = [], [], []
+        for t in targets:
+            if len(t) == 0:
+                counts.append(0)
+                continue
+            counts.append(int(t["labels"].numel()))
+            lab.append(t["labels"].reshape(-1).to(dev, torch.int64))
+            box.append(t["boxes"].reshape(-1, 4).to(dev, torch.float32))
+        if sum(counts) == 0:
+            return (torch.full((bs * num_queries,), -1, dtype=torch.int32, device=dev),
+                    torch.zeros(bs, dtype=torch.int32, device=dev))
+        labels = torch.cat(lab)
+        offs = torch.empty(len(counts) + 1, dtype=torch.int32, pin_memory=True)
+        offs.numpy()[:] = np.concatenate([[0], np.cumsum(counts)])
+        offs = offs.to(dev, non_blocking=True)                  # pinned: an async copy (a pageable one synchronises)
+        cost = match_cost(det, C, labels, torch.cat(box).contiguous(), offs, self.cost_class, self.cost_bbox, self.cost_giou,
+                          self.focal_alpha, self.focal_gamma, -1 if self.per_image_rows else 0)
+        return assign(cost, offs, num_queries, labels, C)
 
 
 def build_matcher(args):

@@ -302,6 +302,29 @@ int dod_match_cost(const float* det, int B, int Q, int C, const int64_t* labels,
                    const int32_t* gt_offsets, int G, float w_class, float w_bbox, float w_giou, float alpha, float gamma,
                    int rows_from, float* cost, void* stream);
 
+/* ---- Hungarian assignment on device (the matcher's linear_sum_assignment, matching.py:105) ---------------------------
+ * scipy.optimize.linear_sum_assignment of every image's [Q, n_b] matrix in the cost buffer dod_match_cost writes (image b at
+ * cost + gt_offsets[b]*Q), one workgroup per image.  Bit-identical to scipy's result, ties included: the same shortest
+ * augmenting path (Crouse) with the same double-precision operations in the same order.  All pointers
+ * are DEVICE pointers; one launch on `stream`, no sync, no allocation.
+ *   gt_offsets  int32 [B+1], as for dod_match_cost; G = gt_offsets[B] is the cost buffer's target count
+ *   labels      int64 [G] or NULL (NULL skips the label check); C the class count it is checked against
+ *   match       int32 [B*Q] out: entry b*Q + q = gt_offsets[b] + target, or -1 when query q is unmatched (the table
+ *               SetCriterion consumes); every row of an image whose status is not 0 is -1
+ *   status      int32 [B] out, per image:
+ *                 0  solved (an image without targets is solved, all rows -1)
+ *                 1  the matrix holds NaN or -inf: scipy raises ValueError("matrix contains invalid numeric entries");
+ *                    also for offsets outside [0, G] or decreasing (nothing of the image is read)
+ *                 2  infeasible: scipy raises ValueError("cost matrix is infeasible")
+ *                 3  a label of the image lies outside [0, C) (checked before the costs): the matcher raises IndexError
+ *   workspace   dod_match_assign_workspace_bytes(B, Q, G) bytes (DOD_ERR_STATE if smaller or NULL): state of the images too
+ *               large for LDS
+ * DOD_ERR_INVALID: a NULL offsets / match / status pointer, NULL cost with G > 0, non-positive B / Q, negative G, labels
+ * with C <= 0.  Argument errors return before any HIP call. */
+size_t dod_match_assign_workspace_bytes(int B, int Q, int G);
+int dod_match_assign(const float* cost, const int32_t* gt_offsets, int B, int Q, int G, const int64_t* labels, int C,
+                     int32_t* match, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- set-prediction loss and its gradient on device (the training criterion) ----------------------------------------
  * Replaces SetCriterion.forward, dino_detector/losses.py:204-242: the focal loss over every [B, Q, C] logit with unmatched
  * queries as background (loss_labels :100-146), the L1 and GIoU losses of the matched boxes (loss_boxes :148-185), each
@@ -445,9 +468,9 @@ long dod_test_counter(const char* name);
 const char* dod_version(void);
 /* ABI revision of this header: bumped whenever an exported signature or struct layout changes (round 2's dod_set_weight gained its
  * dtype argument at revision 2; revision 4 = this file: the dod_debug_* entry points left the release library, dod_test_* replaced the three
- * the tests use, the folded-LayerNorm operators arrived; revision 5: the dod_set_criterion_* entry points).  A C caller compiled against
- * DOD_ABI_VERSION checks it once at load. */
-#define DOD_ABI_VERSION 5
+ * the tests use, the folded-LayerNorm operators arrived; revision 5: the dod_set_criterion_* entry points; revision 6: dod_match_assign*).
+ * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
+#define DOD_ABI_VERSION 6
 int dod_abi_version(void);
 /* Devices visible to the HIP runtime libdinodet.so is bound to (<= 0: none / error).  The host uses it to
  * verify the library shares PyTorch's HIP runtime (pointers and streams cross this ABI). */
