@@ -753,13 +753,13 @@ int dod_decoder_train_forward(const dod_config* cfg, const dod_dec_train_params*
     TK(launch_mha_fwd_train(L.qkv, 3 * Dd, L.att, Dd, sc.Pd, B, Q, d.Hd, Dd, d.dh, scale, dropout_p, site_key(seed, j, 0), s));
     TK(lin_fwd(L.att, Dd, p->out_proj_w, p->out_proj_b, BQ, Dd, Dd, sc.y, Dd, ACT_NONE, s));
     TK(dropout_add(L.tgt_in, sc.y, L.t1, (size_t)BQ * Dd, dropout_p, site_key(seed, j, 1), s));
-    TK(launch_layernorm(L.t1, nullptr, p->norm1_w, p->norm1_b, cfg->dec_ln_eps, BQ, Dd, L.tgt1, nullptr, s));
+    TK(launch_layernorm(L.t1, nullptr, p->norm1_w, p->norm1_b, cfg->dec_ln_eps, BQ, Dd, ln_out(L.tgt1), s));
     TH(hipMemsetAsync(L.proj, 0, (size_t)BQ * d.ncp * 4, s));
     TK(launch_gemm_f32(L.tgt1, Dd, sc.cat_w, Dd, BQ, d.ncat, Dd, gepi(sc.cat_b, L.proj, d.ncp), s));
     TK(launch_deform_sample(L.proj, d.ncp, t.values, B, Q, N, d.Hd, d.P, d.dh, d.fh, d.fw, L.samp, s, 0));
     TK(lin_fwd(L.samp, Dd, p->op_w, p->op_b, BQ, Dd, Dd, sc.y, Dd, ACT_NONE, s));
     TK(dropout_add(L.tgt1, sc.y, L.t2, (size_t)BQ * Dd, dropout_p, site_key(seed, j, 2), s));
-    TK(launch_layernorm(L.t2, nullptr, p->norm2_w, p->norm2_b, cfg->dec_ln_eps, BQ, Dd, L.tgt2, nullptr, s));
+    TK(launch_layernorm(L.t2, nullptr, p->norm2_w, p->norm2_b, cfg->dec_ln_eps, BQ, Dd, ln_out(L.tgt2), s));
     TK(lin_fwd(L.tgt2, Dd, p->lin1_w, p->lin1_b, BQ, d.F, Dd, L.hid, d.F, ACT_RELU, s));                   // taped: post-ReLU, pre-dropout
     const float* hin = L.hid;
     if (dropout_p > 0.f) { TK(dropout_add(nullptr, L.hid, sc.y, (size_t)BQ * d.F, dropout_p, site_key(seed, j, 3), s)); hin = sc.y; }
@@ -767,7 +767,7 @@ int dod_decoder_train_forward(const dod_config* cfg, const dod_dec_train_params*
     TK(lin_fwd(hin, d.F, p->lin2_w, p->lin2_b, BQ, Dd, d.F, y2, Dd, ACT_NONE, s));
     TK(dropout_add(L.tgt2, y2, L.t3, (size_t)BQ * Dd, dropout_p, site_key(seed, j, 4), s));
     float* nxt = j + 1 < d.L ? t.l[j + 1].tgt_in : t.hs;
-    TK(launch_layernorm(L.t3, nullptr, p->norm3_w, p->norm3_b, cfg->dec_ln_eps, BQ, Dd, nxt, nullptr, s));
+    TK(launch_layernorm(L.t3, nullptr, p->norm3_w, p->norm3_b, cfg->dec_ln_eps, BQ, Dd, ln_out(nxt), s));
   }
   const int C = d.C;
   TK(launch_gemm_f32(t.hs, Dd, p->class_w, Dd, BQ, C, Dd, gepi(p->class_b, det, C + 4), s));
@@ -972,14 +972,14 @@ int dod_dense_decoder_train_forward(const dod_config* cfg, const dod_dense_dec_t
     TK(launch_mha_fwd_train(L.qkv, 3 * Dd, L.att, Dd, sc.Pd, B, Q, d.Hd, Dd, d.dh, scale, dropout_p, site_key(seed, j, 0), s));
     TK(lin_fwd(L.att, Dd, W.sa_out_w, W.sa_out_b, BQ, Dd, Dd, sc.y, Dd, ACT_NONE, s));
     TK(dropout_add(L.x_in, sc.y, L.t1, nBD, dropout_p, site_key(seed, j, 1), s));
-    TK(launch_layernorm(L.t1, nullptr, W.norm1_w, W.norm1_b, cfg->dec_ln_eps, BQ, Dd, L.x1, nullptr, s));
+    TK(launch_layernorm(L.t1, nullptr, W.norm1_w, W.norm1_b, cfg->dec_ln_eps, BQ, Dd, ln_out(L.x1), s));
     // dense cross-attention: q from the queries, k | v from the memory (in_proj rows 0..Dd-1 / Dd..3Dd-1)
     TK(lin_fwd(L.x1, Dd, W.ca_in_w, W.ca_in_b, BQ, Dd, Dd, L.cq, Dd, ACT_NONE, s));
     TK(lin_fwd(memory, Dd, W.ca_in_w + (size_t)Dd * Dd, W.ca_in_b + Dd, d.M, 2 * Dd, Dd, L.ckv, 2 * Dd, ACT_NONE, s));
     TK(launch_mha_fwd_rect(L.cq, Dd, L.ckv, L.ckv + Dd, 2 * Dd, L.catt, Dd, sc.Pd, B, Q, N, d.Hd, d.dh, scale, dropout_p, site_key(seed, j, 5), s));
     TK(lin_fwd(L.catt, Dd, W.ca_out_w, W.ca_out_b, BQ, Dd, Dd, sc.y, Dd, ACT_NONE, s));
     TK(dropout_add(L.x1, sc.y, L.t2, nBD, dropout_p, site_key(seed, j, 2), s));
-    TK(launch_layernorm(L.t2, nullptr, W.norm2_w, W.norm2_b, cfg->dec_ln_eps, BQ, Dd, L.x2, nullptr, s));
+    TK(launch_layernorm(L.t2, nullptr, W.norm2_w, W.norm2_b, cfg->dec_ln_eps, BQ, Dd, ln_out(L.x2), s));
     // FFN
     TK(lin_fwd(L.x2, Dd, W.lin1_w, W.lin1_b, BQ, F, Dd, L.hid, F, ACT_RELU, s));                         // taped: post-ReLU, pre-dropout
     const float* hin = L.hid;
@@ -987,7 +987,7 @@ int dod_dense_decoder_train_forward(const dod_config* cfg, const dod_dense_dec_t
     TK(lin_fwd(hin, F, W.lin2_w, W.lin2_b, BQ, Dd, F, sc.dbig, Dd, ACT_NONE, s));
     TK(dropout_add(L.x2, sc.dbig, L.t3, nBD, dropout_p, site_key(seed, j, 4), s));
     float* nxt = j + 1 < d.L ? t.l[j + 1].x_in : t.hs;
-    TK(launch_layernorm(L.t3, nullptr, W.norm3_w, W.norm3_b, cfg->dec_ln_eps, BQ, Dd, nxt, nullptr, s));
+    TK(launch_layernorm(L.t3, nullptr, W.norm3_w, W.norm3_b, cfg->dec_ln_eps, BQ, Dd, ln_out(nxt), s));
   }
   const int C = d.C;
   TK(launch_gemm_f32(t.hs, Dd, p->class_w, Dd, BQ, C, Dd, gepi(p->class_b, det, C + 4), s));
@@ -1279,7 +1279,7 @@ int dod_backbone_tail_train_forward(const dod_config* cfg, const dod_bb_tail_par
     TK(launch_lora_merge(bp.o.w, bp.o.A, bp.o.Bm, d.alpha, D, D, d.r, tb.Wo, s));
     TK(launch_lora_merge(bp.fc1.w, bp.fc1.A, bp.fc1.Bm, d.alpha, F1, D, d.r, tb.W1, s));
     TK(launch_lora_merge(bp.fc2.w, bp.fc2.A, bp.fc2.Bm, d.alpha, D, F, d.r, tb.W2, s));
-    TK(launch_layernorm(tb.x, nullptr, bp.ln1_w, bp.ln1_b, d.eps, M, D, tb.y1, nullptr, s));
+    TK(launch_layernorm(tb.x, nullptr, bp.ln1_w, bp.ln1_b, d.eps, M, D, ln_out(tb.y1), s));
     TK(lin_fwd(tb.y1, D, tb.Wqkv, tb.bqkv, M, 3 * D, D, tb.qkv, 3 * D, ACT_NONE, s));
     {
       AttnF32 a; a.q = tb.qkv; a.k = tb.qkv + D; a.v = tb.qkv + 2 * D; a.o = tb.ctx; a.ldq = a.ldk = a.ldv = 3 * D; a.ldo = D;
@@ -1291,7 +1291,7 @@ int dod_backbone_tail_train_forward(const dod_config* cfg, const dod_bb_tail_par
       GemmEpi e = gepi(bp.o.b, tb.x1, D, ACT_NONE, tb.x, D); e.scale = bp.ls1;
       TK(launch_gemm_f32(tb.ctx, D, tb.Wo, D, M, D, D, e, s));
     }
-    TK(launch_layernorm(tb.x1, nullptr, bp.ln2_w, bp.ln2_b, d.eps, M, D, tb.y2, nullptr, s));
+    TK(launch_layernorm(tb.x1, nullptr, bp.ln2_w, bp.ln2_b, d.eps, M, D, ln_out(tb.y2), s));
     TK(lin_fwd(tb.y2, D, tb.W1, bp.fc1.b, M, F1, D, tb.pre, F1, ACT_NONE, s));      // taped: the backward needs the pre-activation
     {
       const size_t n = (size_t)M * F;
@@ -1307,10 +1307,10 @@ int dod_backbone_tail_train_forward(const dod_config* cfg, const dod_bb_tail_par
     }
   }
   if (cfg->target_dim) {
-    TK(launch_layernorm(t.xout, nullptr, p->lnf_w, p->lnf_b, d.eps, M, D, t.f, nullptr, s));
+    TK(launch_layernorm(t.xout, nullptr, p->lnf_w, p->lnf_b, d.eps, M, D, ln_out(t.f), s));
     TK(lin_fwd(t.f, D, p->proj_w, p->proj_b, M, d.Dd, D, mem_out, d.Dd, ACT_NONE, s));
   } else {
-    TK(launch_layernorm(t.xout, nullptr, p->lnf_w, p->lnf_b, d.eps, M, D, mem_out, nullptr, s));
+    TK(launch_layernorm(t.xout, nullptr, p->lnf_w, p->lnf_b, d.eps, M, D, ln_out(mem_out), s));
   }
   return DOD_OK;
 }

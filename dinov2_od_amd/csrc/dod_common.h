@@ -246,15 +246,19 @@ int launch_swiglu_fp8(const bf16_t* in, int rows, int Fh, unsigned char* q, floa
 int launch_quant_rows_fp8(const void* x, int in_bf16, int ld, int rows, int cols, unsigned char* q, int ldq, float* scale,
                           hipStream_t s);
 
-// rows x D LayerNorm, optional pre-add (y = LN(x + add)), fp32 statistics; out bf16 or fp32
-// out_fp8 / out_scale (both or neither): e4m3 row + per-row scale (amax / 448) instead of the fp32 / bf16 output;
-// out_split3: split-product pair layout [hi | lo] (row pitch 2*D) instead
-// h2: out_split3 is written in the H2 operand format (row pitch 4*D bytes) instead
-int launch_layernorm(const float* x, const float* add, const float* gamma, const float* beta, float eps,
-                     int rows, int D, float* out_f32, bf16_t* out_bf16, hipStream_t s,
-                     unsigned char* out_fp8 = nullptr, float* out_scale = nullptr, bf16_t* out_split3 = nullptr, int h2 = 0,
-                     bf16_t* out_a3 = nullptr,       // out_a3 (with out_f32 only): also the bf16x3 activation layout [hi | hi | lo], row pitch 3*D
-                     unsigned char* out_bs = nullptr);   // with out_fp8 (and no out_scale): block-scaled e4m3 rows, e8m0 bytes [rows][2][D / 64]
+// rows x D LayerNorm, optional pre-add (y = LN(x + add)), fp32 statistics.  Where the normalised rows go (also the kernel's argument):
+struct LnOut {
+  float* f32 = nullptr;            // fp32 rows, and / or
+  bf16_t* bf16 = nullptr;          // bf16 rows
+  unsigned char* fp8 = nullptr;    // e4m3 rows instead, with scale (one per row, amax / 448) or bs
+  float* scale = nullptr;
+  bf16_t* split = nullptr;         // split-product pair layout [hi | lo] (row pitch 2*D) instead; split_h2: the H2 operand format (row pitch 4*D bytes)
+  bf16_t* a3 = nullptr;            // with f32 only: also the bf16x3 activation layout [hi | hi | lo], row pitch 3*D
+  unsigned char* bs = nullptr;     // with fp8 (and no scale): block-scaled e4m3 rows, e8m0 bytes [rows][2][D / 64]
+};
+inline LnOut ln_out(float* f32, bf16_t* bf16 = nullptr, bf16_t* a3 = nullptr) { LnOut o; o.f32 = f32; o.bf16 = bf16; o.a3 = a3; return o; }
+int launch_layernorm(const float* x, const float* add, const float* gamma, const float* beta, float eps, int rows, int D, const LnOut& out,
+                     hipStream_t s, int split_h2 = 0);
 // ---- folded LayerNorm (GemmEpi::ln_*): row statistics only.
 // rows of x -> operand copy of x ITSELF (kind LNOP_*, as GemmEpi::ln_op) + (mean, rstd) per row: what the first block's QKV needs (its
 // producer is the patch embedding, not a residual GEMM)

@@ -260,7 +260,7 @@ int launch_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int
   const int tiles_n = (N + FBN - 1) / FBN;
   const int tiles = ((M + FBM - 1) / FBM) * tiles_n;
   // Slices: from (N, K) alone -- the row count must not change a row's bits (micro-batches, single-image launches).  The callers that allow the
-  // split send at most ~16 m-tiles of N >= 128 here (larger row counts take the bf16 split-3 form, dod_api.hip qlinear) and any number for the
+  // split send at most ~16 m-tiles of N >= 128 here (larger row counts take the bf16 split-3 form, dod_forward.hip qlinear) and any number for the
   // narrow heads (N < 128): aim at two workgroups per CU for 16 m-tiles, at least 8 k-tiles per slice, at most 8 slices.
   int S = 1;
   float* part = nullptr; unsigned* counters = nullptr;

@@ -12,7 +12,6 @@
 // Output forms (compile-time: the round-2 kernel took them as runtime pointers / an int and carried every writer's registers -- 100
 // VGPRs, four waves per SIMD -- which cost 27 % of its bandwidth).
 enum { LN_F32 = 1, LN_BF16 = 2, LN_PAIR = 4, LN_H2 = 8, LN_FP8 = 16, LN_S3 = 32, LN_FP8MX = 64 };
-struct LnOut { float* f32; bf16_t* bf16; unsigned char* fp8; float* scale; bf16_t* split; bf16_t* a3; unsigned char* bs; };
 // NCH float4 chunks per lane (compile-time trip count: D = 768 holds a row in 3 x 4 registers instead of LN_MAXC x 4); EXACT: D == 256 NCH
 template <int NCH, bool EXACT, int OUT>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ add,
@@ -172,29 +171,26 @@ static void ln_dispatch(const float* x, const float* add, const float* gamma, co
 #undef LN_GO
 }
 
-int launch_layernorm(const float* x, const float* add, const float* gamma, const float* beta, float eps,
-                     int rows, int D, float* out_f32, bf16_t* out_bf16, hipStream_t s, unsigned char* out_fp8,
-                     float* out_scale, bf16_t* out_split3, int h2, bf16_t* out_a3, unsigned char* out_bs) {
+int launch_layernorm(const float* x, const float* add, const float* gamma, const float* beta, float eps, int rows, int D, const LnOut& o,
+                     hipStream_t s, int split_h2) {
   if (rows <= 0) return 1;
   if (D % 4 != 0 || D > 256 * LN_MAXC) return 2;
-  if (h2 && (!out_split3 || D % 32 != 0)) return 2;
-  if (out_bs) {        // block-scaled e4m3 rows: out_fp8 + one e8m0 byte per 32 columns (layout [rows][2][D / 64])
-    if (!out_fp8 || out_scale || out_f32 || out_bf16 || out_split3 || out_a3 || D % 64 != 0) return 2;
-    LnOut o{nullptr, nullptr, out_fp8, nullptr, nullptr, nullptr, out_bs};
+  if (split_h2 && (!o.split || D % 32 != 0)) return 2;
+  if (o.bs) {        // block-scaled e4m3 rows: fp8 + one e8m0 byte per 32 columns (layout [rows][2][D / 64])
+    if (!o.fp8 || o.scale || o.f32 || o.bf16 || o.split || o.a3 || D % 64 != 0) return 2;
     ln_dispatch<LN_FP8MX>(x, add, gamma, beta, eps, rows, D, o, s);
     return hipGetLastError() == hipSuccess ? 0 : 3;
   }
-  if ((out_fp8 == nullptr) != (out_scale == nullptr)) return 2;
-  LnOut o{out_f32, out_bf16, out_fp8, out_scale, out_split3, out_a3, nullptr};
-  if (out_a3) {
-    if (!out_f32 || out_bf16 || out_fp8 || out_split3) return 2;
+  if ((o.fp8 == nullptr) != (o.scale == nullptr)) return 2;
+  if (o.a3) {
+    if (!o.f32 || o.bf16 || o.fp8 || o.split) return 2;
     ln_dispatch<LN_F32 | LN_S3>(x, add, gamma, beta, eps, rows, D, o, s);
-  } else if (out_fp8) ln_dispatch<LN_FP8>(x, add, gamma, beta, eps, rows, D, o, s);
-  else if (out_split3 && (out_f32 || out_bf16)) return 2;
-  else if (out_split3) { if (h2) ln_dispatch<LN_H2>(x, add, gamma, beta, eps, rows, D, o, s); else ln_dispatch<LN_PAIR>(x, add, gamma, beta, eps, rows, D, o, s); }
-  else if (out_f32 && out_bf16) ln_dispatch<LN_F32 | LN_BF16>(x, add, gamma, beta, eps, rows, D, o, s);
-  else if (out_bf16) ln_dispatch<LN_BF16>(x, add, gamma, beta, eps, rows, D, o, s);
-  else if (out_f32) ln_dispatch<LN_F32>(x, add, gamma, beta, eps, rows, D, o, s);
+  } else if (o.fp8) ln_dispatch<LN_FP8>(x, add, gamma, beta, eps, rows, D, o, s);
+  else if (o.split && (o.f32 || o.bf16)) return 2;
+  else if (o.split) { if (split_h2) ln_dispatch<LN_H2>(x, add, gamma, beta, eps, rows, D, o, s); else ln_dispatch<LN_PAIR>(x, add, gamma, beta, eps, rows, D, o, s); }
+  else if (o.f32 && o.bf16) ln_dispatch<LN_F32 | LN_BF16>(x, add, gamma, beta, eps, rows, D, o, s);
+  else if (o.bf16) ln_dispatch<LN_BF16>(x, add, gamma, beta, eps, rows, D, o, s);
+  else if (o.f32) ln_dispatch<LN_F32>(x, add, gamma, beta, eps, rows, D, o, s);
   else return 2;
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
