@@ -27,7 +27,7 @@ class DodConfig(C.Structure):
     ]
 
 
-_P, _I, _F, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_P, _I, _F, _SZ, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 
 
 class DodDetection(C.Structure):
@@ -136,6 +136,15 @@ SYMBOLS = {
     "dod_match_cost": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P]),
     "dod_match_assign_workspace_bytes": (_SZ, [_I, _I, _I]),
     "dod_match_assign": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _SZ, _P]),
+    "dod_coco_eval_workspace_bytes": (_SZ, [_I64, _I, _I, _I64]),
+    "dod_coco_eval_set_gt": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dod_coco_eval_reset": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P]),
+    "dod_coco_eval_append": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P, _P, _I64, _P]),
+    "dod_coco_eval_append_host": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P, _I64, _P]),
+    "dod_coco_eval_evaluate": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P, _P, _P, _P, _P, _P]),
+    "dod_coco_eval_matches": (_I, [_P, _SZ, _I64, _I, _I, _I64, _I64, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "dod_op_sort_pairs_workspace_bytes": (_SZ, [_I64]),
+    "dod_op_sort_pairs_u64": (_I, [_P, _P, _P, _P, _I64, _I, _I, _P, _SZ, _P]),
     "dod_set_criterion_workspace_bytes": (_SZ, [_I, _I, _I]),
     "dod_set_criterion_forward": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _I, _I, _P, _P, _I, _P, _I, _P, _F, _F, _P, _P, _P, _SZ, _P]),
     "dod_set_criterion_backward": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _I, _I, _P, _P, _I, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P]),

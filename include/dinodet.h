@@ -325,6 +325,64 @@ size_t dod_match_assign_workspace_bytes(int B, int Q, int G);
 int dod_match_assign(const float* cost, const int32_t* gt_offsets, int B, int Q, int G, const int64_t* labels, int C,
                      int32_t* match, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- COCO bbox evaluation on device (compute_coco_metrics, dino_detector/utils.py:243-276) ---------------------------
+ * pycocotools' COCOeval (iouType 'bbox', useCats = 1, default parameters: 10 IoU thresholds, 101 recall thresholds, area
+ * ranges all / small / medium / large, maxDets 1 / 10 / 100) restated operation for operation in double precision
+ * (csrc/cocoeval.hip): precision / recall are bit-identical to the host library's, the 12 statistics
+ * equal up to the summation order of a mean.
+ *
+ * The evaluator's state lives in ONE caller-owned device workspace of dod_coco_eval_workspace_bytes(max_dets, I, K, G) bytes
+ * (0 for unsupported sizes); every call names the same four sizes.  I / K: the annotation file's unique image / category ids;
+ * G: its ground truths.  Limits: max_dets <= 2^24, I and K <= 2^24, G <= 2^26, at most 1024 ground truths in one (image,
+ * category) group; any number of groups and of detections per group (the 100 best of a group are kept, as maxDets[-1]
+ * keeps them).  Beyond a limit a call returns DOD_ERR_INVALID; a short or NULL workspace is DOD_ERR_STATE.
+ *
+ * dod_coco_eval_set_gt   HOST arrays: image_ids [I] / category_ids [K] sorted and unique; the ground truths sorted STABLY by
+ *                        gt_group = category index * I + image index (so a group keeps the file's order): bbox [G,4] xywh,
+ *                        the annotation's `area`, iscrowd bytes; iou_thrs [10] / rec_thrs [101] = np.linspace(.5, .95, 10) /
+ *                        np.linspace(0, 1, 101) (uploaded as given, never recomputed).  Clears the detections.  Synchronises.
+ * dod_coco_eval_append   `*count` (device int64) records of a device dod_detection buffer of capacity max_records -- what
+ *                        dod_postprocess writes -- are appended.  Two launches on `stream`, no host synchronisation.
+ * dod_coco_eval_append_host  n HOST detections with double boxes and scores (a results list).  Synchronises.
+ * dod_coco_eval_reset    forgets the detections (one launch).
+ * dod_coco_eval_evaluate stats: HOST double [12] = COCOeval.stats; precision / recall: DEVICE double [10,101,K,4,3] /
+ *                        [10,K,4,3] or NULL; n_dets / n_groups: HOST out or NULL (detections held, ground-truth groups).
+ *                        Synchronises (it reads the detection count and returns the statistics).  DOD_ERR_INVALID: more than
+ *                        max_dets detections were appended or a source buffer was truncated; a detection's image id is not
+ *                        in image_ids; a score is not finite.  Detections of a category the annotations lack are not
+ *                        evaluated (COCOeval's catIds come from the ground truth).
+ * dod_coco_eval_matches  after evaluate, copies out (DEVICE, each may be NULL) per sorted detection position [n_dets]: the
+ *                        input index, the rank in its (image, category) group, and bit a*10+t of matched / ignored for area
+ *                        range a and IoU threshold t (meaningful for rank < 100); per ground-truth group [n_groups]: its key
+ *                        and the non-ignored ground truths per area range [n_groups, 4]. */
+typedef struct dod_coco_det {
+  int64_t image_id;
+  int64_t category_id;
+  double bbox[4];         /* x, y, w, h */
+  double score;
+} dod_coco_det;           /* 56 bytes */
+size_t dod_coco_eval_workspace_bytes(int64_t max_dets, int n_images, int n_categories, int64_t n_gt);
+int dod_coco_eval_set_gt(void* workspace, size_t workspace_bytes, int64_t max_dets, int n_images, int n_categories, int64_t n_gt,
+                         const int64_t* image_ids, const int64_t* category_ids, const int64_t* gt_group, const double* gt_bbox,
+                         const double* gt_area, const uint8_t* gt_iscrowd, const double* iou_thrs, const double* rec_thrs, void* stream);
+int dod_coco_eval_reset(void* workspace, size_t workspace_bytes, int64_t max_dets, int n_images, int n_categories, int64_t n_gt, void* stream);
+int dod_coco_eval_append(void* workspace, size_t workspace_bytes, int64_t max_dets, int n_images, int n_categories, int64_t n_gt,
+                         const dod_detection* records, const int64_t* count, int64_t max_records, void* stream);
+int dod_coco_eval_append_host(void* workspace, size_t workspace_bytes, int64_t max_dets, int n_images, int n_categories, int64_t n_gt,
+                              const dod_coco_det* dets, int64_t n, void* stream);
+int dod_coco_eval_evaluate(void* workspace, size_t workspace_bytes, int64_t max_dets, int n_images, int n_categories, int64_t n_gt,
+                           double* stats, double* precision, double* recall, int64_t* n_dets, int32_t* n_groups, void* stream);
+int dod_coco_eval_matches(const void* workspace, size_t workspace_bytes, int64_t max_dets, int n_images, int n_categories, int64_t n_gt,
+                          int64_t n_dets, int32_t* det_index, int32_t* det_rank, uint64_t* matched, uint64_t* ignored, int32_t n_groups,
+                          uint64_t* group_keys, int32_t* npig, void* stream);
+
+/* Stable LSD radix sort (8-bit digits) of n <= 2^24 (64-bit key, 32-bit payload) pairs on key bits [begin_bit, end_bit), both
+ * multiples of 8: equal keys keep their input order.  Sorts (keys, vals) in place; keys_alt / vals_alt [n] are scratch.
+ * workspace: dod_op_sort_pairs_workspace_bytes(n) bytes (0 for unsupported n).  All DEVICE pointers; no sync. */
+size_t dod_op_sort_pairs_workspace_bytes(int64_t n);
+int dod_op_sort_pairs_u64(uint64_t* keys, uint32_t* vals, uint64_t* keys_alt, uint32_t* vals_alt, int64_t n, int begin_bit, int end_bit,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- set-prediction loss and its gradient on device (the training criterion) ----------------------------------------
  * Replaces SetCriterion.forward, dino_detector/losses.py:204-242: the focal loss over every [B, Q, C] logit with unmatched
  * queries as background (loss_labels :100-146), the L1 and GIoU losses of the matched boxes (loss_boxes :148-185), each
@@ -469,6 +527,8 @@ const char* dod_version(void);
 /* ABI revision of this header: bumped whenever an exported signature or struct layout changes (round 2's dod_set_weight gained its
  * dtype argument at revision 2; revision 4 = this file: the dod_debug_* entry points left the release library, dod_test_* replaced the three
  * the tests use, the folded-LayerNorm operators arrived; revision 5: the dod_set_criterion_* entry points; revision 6: dod_match_assign*).
+ * New entry points alone change no signature and no layout: dod_coco_eval_* and dod_op_sort_pairs_* joined revision 6, and a caller that
+ * needs them resolves them by name (the Python binding fails at load when one is missing).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);
