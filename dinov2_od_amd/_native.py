@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("DINODET_LIB") or os.path.join(_HERE, "lib", "libdinod
 DOD_F32, DOD_BF16 = 0, 1
 PREC = {"fp32": 0, "bf16": 1, "fp8": 2, "bf16x3": 3, "fp16x2": 4}
 ACT = {"none": 0, "relu": 1, "gelu": 2, "sigmoid": 3, "swiglu_pairs": 4}
+PW = {"gelu_bwd": 0, "swiglu_bwd": 1, "relu_drop_bwd": 2, "dropout_add": 3, "sigmoid_bwd4": 4}      # enum dod_pointwise_op
 
 
 class DodConfig(C.Structure):
@@ -161,6 +162,14 @@ SYMBOLS = {
     "dod_backbone_tail_workspace_bytes": (_SZ, [C.POINTER(DodConfig), _I, _I, _I]),
     "dod_backbone_tail_train_forward": (_I, [C.POINTER(DodConfig), _P, _P, _I, _I, _P, _P, _SZ, _P, _SZ, _P]),
     "dod_backbone_tail_train_backward": (_I, [C.POINTER(DodConfig), _P, _I, _I, _P, _P, _SZ, _P, _P, _SZ, _P]),
+    "dod_op_layernorm_bwd": (_I, [_P, _P, _P, _F, _I, _I, _P, _P, _P, _P]),
+    "dod_op_attention_f32_vjp_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
+    "dod_op_attention_f32_vjp": (_I, [_P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _F, C.c_uint64, _P, _SZ, _P]),
+    "dod_op_deform_sample_bwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "dod_op_lora_grads_workspace_bytes": (_SZ, [_I, _I]),
+    "dod_op_lora_grads": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _F, _P, _P, _P, _SZ, _P]),
+    "dod_op_train_pointwise": (_I, [_I, _P, _P, _P, _SZ, _I, _F, C.c_uint64, _P]),
+    "dod_op_colsum_add": (_I, [_P, _I, _I, _I, _P, _P]),
     "dod_reserve_gemm_scratch": (_I, [C.c_size_t]),
     "dod_test_set_option": (_I, [C.c_char_p, _I]),
     "dod_test_counter": (C.c_long, [C.c_char_p]),

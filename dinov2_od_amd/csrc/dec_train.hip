@@ -188,7 +188,7 @@ __global__ void batch_sum_kernel(const float* __restrict__ d, float* __restrict_
 template <int MAXC>       // 64-column chunks per lane: 16 (D <= 1024) or 32 (D <= 2048: ViT-g's 1536)
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ dy,
                                                      float eps, int rows, int D, float* __restrict__ dx, float* __restrict__ dgamma,
-                                                     float* __restrict__ dbeta, float* __restrict__ part) {
+                                                     float* __restrict__ dbeta, float* __restrict__ part, int nacc) {
   const int lane = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
   float dg[MAXC], db[MAXC];
 #pragma unroll
@@ -230,24 +230,37 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
   __syncthreads();
   for (int k = threadIdx.x; k < D; k += 256) {
     const float g_ = (sg[0][k] + sg[1][k]) + (sg[2][k] + sg[3][k]), b_ = (sb[0][k] + sb[1][k]) + (sb[2][k] + sb[3][k]);
-    if (part) { part[((size_t)blockIdx.x * 2) * D + k] = g_; part[((size_t)blockIdx.x * 2 + 1) * D + k] = b_; }      // deterministic mode: merged in block order
+    if (part && !nacc) { part[((size_t)blockIdx.x * 2) * D + k] = g_; part[((size_t)blockIdx.x * 2 + 1) * D + k] = b_; }      // deterministic mode: merged in block order
+    else if (part) { const size_t a = (size_t)(blockIdx.x % nacc) * 2; atomicAdd(part + a * D + k, g_); atomicAdd(part + (a + 1) * D + k, b_); }
     else { atomicAdd(dgamma + k, g_); atomicAdd(dbeta + k, b_); }
   }
 }
+#define LN_ACC 16            // interleaved accumulators of the fast mode's parameter gradients ...
+#define LN_ACC_FROM 512      // ... from this many workgroups (2 048 rows) up: below, the chain is short and the two extra launches would show
 int ln_bwd(const float* x, const float* gamma, const float* dy, float eps, int rows, int D, float* dx, float* dgamma, float* dbeta, hipStream_t s) {
   if (D > 2048) return 2;
   int blocks = (rows + 3) / 4; blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);      // one row per wave up to 8 192 rows
   float* part = nullptr;
+  int nacc = 0;
   if (det_mode()) {
     blocks = blocks > 256 ? 256 : blocks;
     part = det_scratch((size_t)blocks * 2 * D);
     if (!part) return 3;
+  } else if (blocks > LN_ACC_FROM) {
+    // A float atomic per column and workgroup straight into dgamma / dbeta is a chain of `blocks` roundings at the size of the running sum: at
+    // 2 048 workgroups its random walk reaches 1-2e-6 of the largest column, in an order that changes from run to run.  Long chains go through
+    // LN_ACC interleaved accumulators instead (workgroup b adds into accumulator b % LN_ACC: chains and sums 1 / LN_ACC as long), merged in order.
+    nacc = LN_ACC;
+    part = det_scratch((size_t)nacc * 2 * D);
+    if (!part) return 3;
+    if (hipMemsetAsync(part, 0, (size_t)nacc * 2 * D * 4, s) != hipSuccess) return 3;
   }
-  if (D <= 1024) hipLaunchKernelGGL(ln_bwd_kernel<16>, dim3(blocks), dim3(256), 0, s, x, gamma, dy, eps, rows, D, dx, dgamma, dbeta, part);
-  else hipLaunchKernelGGL(ln_bwd_kernel<32>, dim3(blocks), dim3(256), 0, s, x, gamma, dy, eps, rows, D, dx, dgamma, dbeta, part);
-  if (part) {      // part rows alternate (dgamma, dbeta) per block: two strided ordered sums
-    hipLaunchKernelGGL(ordered_add_kernel, dim3((D + 255) / 256), dim3(256), 0, s, part, blocks, 2 * D, D, dgamma);
-    hipLaunchKernelGGL(ordered_add_kernel, dim3((D + 255) / 256), dim3(256), 0, s, part + D, blocks, 2 * D, D, dbeta);
+  if (D <= 1024) hipLaunchKernelGGL(ln_bwd_kernel<16>, dim3(blocks), dim3(256), 0, s, x, gamma, dy, eps, rows, D, dx, dgamma, dbeta, part, nacc);
+  else hipLaunchKernelGGL(ln_bwd_kernel<32>, dim3(blocks), dim3(256), 0, s, x, gamma, dy, eps, rows, D, dx, dgamma, dbeta, part, nacc);
+  if (part) {      // part rows alternate (dgamma, dbeta) per block / accumulator: two strided ordered sums
+    const int np = nacc ? nacc : blocks;
+    hipLaunchKernelGGL(ordered_add_kernel, dim3((D + 255) / 256), dim3(256), 0, s, part, np, 2 * D, D, dgamma);
+    hipLaunchKernelGGL(ordered_add_kernel, dim3((D + 255) / 256), dim3(256), 0, s, part + D, np, 2 * D, D, dbeta);
   }
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
@@ -598,6 +611,26 @@ int tfail(int code, const char* fmt, ...) {
 #define TK(x) do { int r_ = (x); if (r_) return tfail(r_ == 3 ? DOD_ERR_HIP : DOD_ERR_INVALID, "decoder train: %s failed (%d)", #x, r_); } while (0)
 #define TH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return tfail(DOD_ERR_HIP, "decoder train: %s: %s", #x, hipGetErrorString(e_)); } while (0)
 
+// dproj zero on entry, dvalues accumulated; the scatter kernel, or in deterministic mode the three ordered ones.  Returns a dod_status.
+int launch_deform_bwd(const float* proj, int ldp, const float* values, const float* dout, int B, int Q, int N, int Hd, int P, int dh, int h, int w,
+                      float* dproj, float* dvalues, hipStream_t s) {
+  const int BQ = B * Q;
+  if (det_mode()) {
+    float* dref_part = det_scratch((size_t)BQ * Hd * 2);
+    if (!dref_part) return tfail(DOD_ERR_HIP, "deterministic mode: scratch allocation failed");
+    hipLaunchKernelGGL(deform_bwd_kernel<true>, dim3((unsigned)(((long)BQ * Hd + 3) / 4)), dim3(256), 0, s, proj, ldp, values, dout, B, Q, N, Hd, P, dh, h, w,
+                       dproj, dvalues, dref_part);
+    hipLaunchKernelGGL(deform_dref_det_kernel, dim3((BQ + 255) / 256), dim3(256), 0, s, dref_part, BQ, Hd, ldp, dproj);
+    hipLaunchKernelGGL(deform_bwd_values_det_kernel, dim3((unsigned)(((long)B * N * Hd + 3) / 4)), dim3(256), 0, s, proj, ldp, dout, B, Q, N, Hd, P, dh, h, w,
+                       dvalues);
+  } else {
+    hipLaunchKernelGGL(deform_bwd_kernel<false>, dim3((unsigned)(((long)BQ * Hd + 3) / 4)), dim3(256), 0, s, proj, ldp, values, dout, B, Q, N, Hd, P, dh, h, w,
+                       dproj, dvalues, nullptr);
+  }
+  TH(hipGetLastError());
+  return DOD_OK;
+}
+
 struct Dims { int B, N, Q, Dd, Hd, P, F, C, L, dh, ncat, ncp, BQ, M, fh, fw; };
 bool make_dims(const dod_config* c, int B, int N, Dims* d) {
   if (!c || B <= 0 || N <= 0 || !c->use_deformable) return false;
@@ -836,19 +869,7 @@ int dod_decoder_train_backward(const dod_config* cfg, const dod_dec_train_params
     TK(lin_bwd_w(sc.dbr, Dd, L.samp, Dd, BQ, Dd, Dd, G(grads->op_w), G(grads->op_b), s));
     TK(lin_bwd_x(sc.dbr, Dd, p->op_w, BQ, Dd, Dd, sc.dt, false, s));                                   // dt = d(samp)
     TH(hipMemsetAsync(sc.dproj, 0, (size_t)BQ * d.ncp * 4, s));
-    if (det_mode()) {
-      float* dref_part = det_scratch((size_t)BQ * d.Hd * 2);
-      if (!dref_part) return tfail(DOD_ERR_HIP, "deterministic mode: scratch allocation failed");
-      hipLaunchKernelGGL(deform_bwd_kernel<true>, dim3((unsigned)(((long)BQ * d.Hd + 3) / 4)), dim3(256), 0, s, L.proj, d.ncp, t.values, sc.dt, B, Q, N, d.Hd,
-                         d.P, d.dh, d.fh, d.fw, sc.dproj, sc.dvalues, dref_part);
-      hipLaunchKernelGGL(deform_dref_det_kernel, dim3((BQ + 255) / 256), dim3(256), 0, s, dref_part, BQ, d.Hd, d.ncp, sc.dproj);
-      hipLaunchKernelGGL(deform_bwd_values_det_kernel, dim3((unsigned)(((long)B * N * d.Hd + 3) / 4)), dim3(256), 0, s, L.proj, d.ncp, sc.dt, B, Q, N, d.Hd,
-                         d.P, d.dh, d.fh, d.fw, sc.dvalues);
-    } else {
-      hipLaunchKernelGGL(deform_bwd_kernel<false>, dim3((unsigned)(((long)BQ * d.Hd + 3) / 4)), dim3(256), 0, s, L.proj, d.ncp, t.values, sc.dt, B, Q, N, d.Hd,
-                         d.P, d.dh, d.fh, d.fw, sc.dproj, sc.dvalues, nullptr);
-    }
-    TH(hipGetLastError());
+    rc = launch_deform_bwd(L.proj, d.ncp, t.values, sc.dt, B, Q, N, d.Hd, d.P, d.dh, d.fh, d.fw, sc.dproj, sc.dvalues, s); if (rc) return rc;
     TK(lin_bwd_w(sc.dproj, d.ncp, L.tgt1, Dd, BQ, d.ncat, Dd, sc.dcat_w, sc.dcat_b, s));
     TK(lin_bwd_x(sc.dproj, d.ncp, sc.cat_w, BQ, d.ncat, Dd, sc.dtgt, true, s));                        // dtgt = d(tgt1)
     // LN1 <- tgt_in + dropout1(out_proj(att))
@@ -1127,13 +1148,17 @@ struct TScratch { float *dx, *da, *db, *dbig, *dqkv, *dS, *Pd, *T, *U, *dump, *d
 // Taken from 1 024 tokens per image up (518x518 inputs: 19.8 vs 21.9 ms per ViT-B batch-8 step, and no 2 x 720 MB of scratch); below
 // that the batched form is as fast (224x224: 10.0 vs 9.9 ms) and sits closer to a float64 evaluation -- the flash form takes
 // delta = <dO, O> from the forward's rounded output instead of sum_j P dP over the probabilities it multiplies (1.7e-5 vs 5.3e-5 from
-// float64 on the worst LoRA gradient at 1 370 tokens, the PyTorch composite 2.3e-5).  DINODET_ATTN_BWD_FLASH = 0 / 1 forces either.
+// float64 on the worst LoRA gradient at 1 370 tokens, the PyTorch composite 2.3e-5).  DINODET_ATTN_BWD_FLASH = 0 / 1 forces either, and so
+// does the test option "attn_bwd_flash" (which wins over the variable).
 // This is the SINGLE predicate: the scratch carve (no dS / Pd when it holds), the forward's log-sum-exp tape and the backward all ask it, and it
 // contains everything launch_attn_f32_bwd itself checks (head_dim 64; q / k / v / o pitches 3D and D multiples of 4: D = heads * 64) -- so that
 // launcher's "not taken" return (2) cannot occur behind it; there is no second scratch layout to fall back to.
 inline bool tail_flash_bwd(const TDims& d) {
   static const char* e = getenv("DINODET_ATTN_BWD_FLASH");
-  if (d.dh != 64 || d.D != d.H * 64 || d.D % 4 != 0 || d.B <= 0 || d.N <= 0 || (e && e[0] == '0')) return false;
+  if (d.dh != 64 || d.D != d.H * 64 || d.D % 4 != 0 || d.B <= 0 || d.N <= 0) return false;
+  const int o = dod_option(DOD_OPT_ATTN_BWD_FLASH);      // tests choose the form per case; set around a whole forward + backward
+  if (o >= 0) return o != 0;
+  if (e && e[0] == '0') return false;
   return (e && e[0] == '1') || d.N >= 1024;
 }
 size_t carve_tscratch(const TDims& d, void* base, TScratch* sc) {
@@ -1386,6 +1411,127 @@ int dod_backbone_tail_train_backward(const dod_config* cfg, const dod_bb_tail_pa
       TK(add_inplace(sc.dx, sc.db, nMD, s));                                                                              // dx = d(x): the block below's output
     }
   }
+  return DOD_OK;
+}
+
+}  // extern "C"
+
+// =============================================================================================================================
+// Operator entry points of the training kernels (include/dinodet.h "training-step operators"): each validates its arguments and calls
+// the launcher the step itself calls, so a test reaches every adjoint kernel on its own, at shapes the three steps never run.
+namespace {
+#define OPFAIL(...) return tfail(DOD_ERR_INVALID, __VA_ARGS__)
+inline size_t attn_vjp_ws(int B, int Lq, int Lk, int heads, int form) {
+  if (form == 0) return 2 * al256(mha_scratch_floats(B, heads, Lq, Lk) * 4);                    // scores / probabilities, adjoint
+  return al256((size_t)2 * B * heads * Lq * 4) + al256((size_t)B * heads * Lq * 4);             // (max, sum) per row, delta
+}
+inline bool attn_vjp_shape_ok(int B, int Lq, int Lk, int heads, int dh, int form) {
+  if (B <= 0 || Lq <= 0 || Lk <= 0 || heads <= 0 || dh <= 0 || dh > 128 || dh % 4) return false;
+  return form == 0 ? Lk <= MHA_MAXQ : (form == 1 && dh == 64);
+}
+inline dim3 pw_grid(size_t n, unsigned cap) { return dim3((unsigned)((n + 255) / 256 < cap ? (n + 255) / 256 : cap)); }
+}  // namespace
+
+extern "C" {
+
+int dod_op_layernorm_bwd(const float* x, const float* gamma, const float* dy, float eps, int rows, int D, float* dx, float* dgamma, float* dbeta,
+                         void* stream) {
+  if (!x || !gamma || !dy || !dx || !dgamma || !dbeta) OPFAIL("dod_op_layernorm_bwd: null buffer");
+  if (rows <= 0 || D <= 0 || D > 2048) OPFAIL("dod_op_layernorm_bwd: rows=%d D=%d outside rows >= 1, 1 <= D <= 2048", rows, D);
+  TK(ln_bwd(x, gamma, dy, eps, rows, D, dx, dgamma, dbeta, (hipStream_t)stream));
+  return DOD_OK;
+}
+
+size_t dod_op_attention_f32_vjp_workspace_bytes(int B, int Lq, int Lk, int heads, int dh, int form) {
+  return attn_vjp_shape_ok(B, Lq, Lk, heads, dh, form) ? attn_vjp_ws(B, Lq, Lk, heads, form) + 256 : 0;
+}
+int dod_op_attention_f32_vjp(const float* q, int ldq, const float* k, const float* v, int ldkv, const float* d_o, float* o, int ldo, float* dq, int lddq,
+                             float* dk, float* dv, int lddkv, int B, int Lq, int Lk, int heads, int dh, float scale, int form, float dropout_p,
+                             uint64_t key, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!q || !k || !v || !d_o || !o || !dq || !dk || !dv || !workspace) OPFAIL("dod_op_attention_f32_vjp: null buffer");
+  if (form != 0 && form != 1) OPFAIL("dod_op_attention_f32_vjp: form %d (0 = batched GEMMs, 1 = flash)", form);
+  if (!attn_vjp_shape_ok(B, Lq, Lk, heads, dh, form))
+    OPFAIL("dod_op_attention_f32_vjp: B=%d Lq=%d Lk=%d heads=%d head_dim=%d not taken by form %d (head_dim <= 128, a multiple of 4; form 0: Lk <= %d; form 1: head_dim 64)",
+           B, Lq, Lk, heads, dh, form, MHA_MAXQ);
+  const int Dm = heads * dh;
+  if (ldq < Dm || ldkv < Dm || ldo < Dm || lddq < Dm || lddkv < Dm || (ldq | ldkv | ldo | lddq | lddkv) % 4)
+    OPFAIL("dod_op_attention_f32_vjp: every pitch must be a multiple of 4 and at least heads * head_dim = %d", Dm);
+  if (dropout_p < 0.f || dropout_p >= 1.f || (form == 1 && dropout_p != 0.f)) OPFAIL("dod_op_attention_f32_vjp: dropout %g (form 0: [0, 1); form 1: 0)", dropout_p);
+  if (workspace_bytes < attn_vjp_ws(B, Lq, Lk, heads, form) + 256) return tfail(DOD_ERR_STATE, "dod_op_attention_f32_vjp: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  if (form == 0) {
+    float* Pd = (float*)base;
+    float* dS = (float*)(base + al256(mha_scratch_floats(B, heads, Lq, Lk) * 4));
+    TK(launch_mha_fwd_rect(q, ldq, k, v, ldkv, o, ldo, Pd, B, Lq, Lk, heads, dh, scale, dropout_p, key, s));
+    TK(launch_mha_bwd_rect(q, ldq, k, v, ldkv, d_o, ldo, dq, lddq, dk, dv, lddkv, dS, Pd, B, Lq, Lk, heads, dh, scale, dropout_p, key, s));
+    return DOD_OK;
+  }
+  float* lse = (float*)base;
+  float* delta = (float*)(base + al256((size_t)2 * B * heads * Lq * 4));
+  AttnF32 a; a.q = q; a.k = k; a.v = v; a.o = o; a.ldq = ldq; a.ldk = a.ldv = ldkv; a.ldo = ldo;
+  a.Lq = Lq; a.Lk = Lk; a.B = B; a.heads = heads; a.dh = dh; a.scale = scale; a.lse = lse;
+  TK(launch_attn_f32(a, s));
+  AttnF32Bwd g;
+  g.q = q; g.k = k; g.v = v; g.o = o; g.d_o = d_o; g.lse = lse; g.dq = dq; g.dk = dk; g.dv = dv; g.delta = delta;
+  g.ldq = ldq; g.ldk = g.ldv = ldkv; g.ldo = ldo; g.lddq = lddq; g.lddk = g.lddv = lddkv;
+  g.Lq = Lq; g.Lk = Lk; g.B = B; g.heads = heads; g.dh = dh; g.scale = scale;
+  TK(launch_attn_f32_bwd(g, s));
+  return DOD_OK;
+}
+
+int dod_op_deform_sample_bwd(const float* proj, int ldp, const float* values, const float* dout, int B, int Q, int N, int Hd, int P, int dh, int hh, int ww,
+                             float* dproj, float* dvalues, void* stream) {
+  if (!proj || !values || !dout || !dproj || !dvalues) OPFAIL("dod_op_deform_sample_bwd: null buffer");
+  if (B <= 0 || Q <= 0 || N <= 0 || Hd <= 0 || P < 1 || P > 8 || dh <= 0 || dh > 128)
+    OPFAIL("dod_op_deform_sample_bwd: B=%d Q=%d N=%d heads=%d points=%d head_dim=%d outside 1 <= points <= 8, 1 <= head_dim <= 128", B, Q, N, Hd, P, dh);
+  if (hh <= 0 || ww <= 0 || hh * ww != N) OPFAIL("dod_op_deform_sample_bwd: a %dx%d feature map does not hold %d tokens", hh, ww, N);
+  if (ldp < 2 + 3 * Hd * P) OPFAIL("dod_op_deform_sample_bwd: pitch %d below the %d columns of [ref | offsets | weights]", ldp, 2 + 3 * Hd * P);
+  hipStream_t s = (hipStream_t)stream;
+  TH(hipMemsetAsync(dproj, 0, (size_t)B * Q * ldp * 4, s));
+  return launch_deform_bwd(proj, ldp, values, dout, B, Q, N, Hd, P, dh, hh, ww, dproj, dvalues, s);
+}
+
+size_t dod_op_lora_grads_workspace_bytes(int M, int r) {
+  return M > 0 && r >= 1 && r <= 64 ? 2 * al256((size_t)M * up4(r) * 4) + 256 : 0;
+}
+int dod_op_lora_grads(const float* X, int in_f, const float* dY, int ldy, int out_f, const float* A, const float* Bm, int M, int r, float alpha, float* dA,
+                      float* dB, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!X || !dY || !A || !Bm || !dA || !dB || !workspace) OPFAIL("dod_op_lora_grads: null buffer");
+  if (r < 1 || r > 64) OPFAIL("dod_op_lora_grads: rank %d outside 1..64", r);
+  if (M <= 0 || in_f <= 0 || out_f <= 0 || ldy < out_f) OPFAIL("dod_op_lora_grads: M=%d in=%d out=%d ldy=%d", M, in_f, out_f, ldy);
+  if (workspace_bytes < dod_op_lora_grads_workspace_bytes(M, r)) return tfail(DOD_ERR_STATE, "dod_op_lora_grads: workspace too small");
+  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  TDims d; memset(&d, 0, sizeof d); d.M = M; d.r = r; d.alpha = alpha;
+  TScratch t; memset(&t, 0, sizeof t); t.T = (float*)base; t.U = (float*)(base + al256((size_t)M * up4(r) * 4));
+  TK(lora_grads(d, X, in_f, dY, ldy, out_f, A, Bm, dA, dB, t, (hipStream_t)stream));
+  return DOD_OK;
+}
+
+int dod_op_train_pointwise(int op, const float* a, const float* b, float* out, size_t n, int cols, float p, uint64_t key, void* stream) {
+  if (!b || !out || (!a && op != DOD_PW_DROPOUT_ADD)) OPFAIL("dod_op_train_pointwise: null buffer");
+  if (n == 0 || p < 0.f || p >= 1.f) OPFAIL("dod_op_train_pointwise: n=%zu p=%g", n, p);
+  hipStream_t s = (hipStream_t)stream;
+  switch (op) {
+    case DOD_PW_GELU_BWD: hipLaunchKernelGGL(gelu_bwd_kernel, pw_grid(n, 4096), dim3(256), 0, s, a, b, out, n); break;
+    case DOD_PW_SWIGLU_BWD:
+      if (cols <= 0) OPFAIL("dod_op_train_pointwise: swiglu_bwd needs cols = F > 0");
+      hipLaunchKernelGGL(swiglu_bwd_kernel, pw_grid(n * (size_t)cols, 4096), dim3(256), 0, s, a, b, out, n, cols); break;
+    case DOD_PW_RELU_DROP_BWD: hipLaunchKernelGGL(relu_drop_bwd_kernel, pw_grid(n, 2048), dim3(256), 0, s, a, b, out, n, p, (unsigned long long)key); break;
+    case DOD_PW_DROPOUT_ADD: TK(dropout_add(a, b, out, n, p, (unsigned long long)key, s)); return DOD_OK;
+    case DOD_PW_SIGMOID_BWD4:
+      if (cols < 4 || n > (size_t)(1 << 29)) OPFAIL("dod_op_train_pointwise: sigmoid_bwd4 needs a pitch cols >= 4 and n <= 2^29 rows");
+      hipLaunchKernelGGL(sigmoid_bwd4_kernel, dim3((unsigned)((n * 4 + 255) / 256)), dim3(256), 0, s, a, cols, b, 4, out, (int)n); break;
+    default: OPFAIL("dod_op_train_pointwise: unknown op %d", op);
+  }
+  TH(hipGetLastError());
+  return DOD_OK;
+}
+
+int dod_op_colsum_add(const float* src, int ld, int rows, int cols, float* dst, void* stream) {
+  if (!src || !dst) OPFAIL("dod_op_colsum_add: null buffer");
+  if (rows <= 0 || cols <= 0 || ld < cols) OPFAIL("dod_op_colsum_add: rows=%d cols=%d ld=%d", rows, cols, ld);
+  TK(colsum_add(src, ld, rows, cols, dst, (hipStream_t)stream));
   return DOD_OK;
 }
 

@@ -37,9 +37,10 @@ static bool check_common(dod_handle* h, int B, int H, int W, int* rc) {
 }
 
 // ---- test hooks (dod_common.h DOD_OPT_*)
-static std::atomic<int> g_options[DOD_OPT_COUNT] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+static std::atomic<int> g_options[DOD_OPT_COUNT] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
 int dod_option(int which) { return which >= 0 && which < DOD_OPT_COUNT ? g_options[which].load() : -1; }
-static const char* const k_option_names[DOD_OPT_COUNT] = {"tailsplit", "dec_fused_split", "mha_chunk_images", "no_fused_patch", "ln_fold", "deterministic", "f32_ksplit"};
+static const char* const k_option_names[DOD_OPT_COUNT] = {"tailsplit", "dec_fused_split", "mha_chunk_images", "no_fused_patch", "ln_fold", "deterministic", "f32_ksplit",
+                                                       "attn_bwd_flash"};
 
 extern "C" {
 

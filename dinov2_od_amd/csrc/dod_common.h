@@ -26,6 +26,7 @@ enum { DOD_OPT_TAILSPLIT = 0,         // GEMM wave-quantisation tail split: 0 of
        DOD_OPT_LN_FOLD,               // 0 = LayerNorm kernels instead of the folded form (read at dod_finalize_weights)
        DOD_OPT_DETERMINISTIC,         // 1 = ordered reductions instead of fp32 atomics in the training step's weight gradients
        DOD_OPT_F32_KSPLIT,            // fp32 GEMM K split across workgroups (gemm_f32.hip): 0 = never, 1 = also for the operator dod_op_linear
+       DOD_OPT_ATTN_BWD_FLASH,        // backbone-tail attention adjoint (dec_train.hip tail_flash_bwd): 0 = never the flash form, 1 = whenever head_dim is 64
        DOD_OPT_COUNT };
 int dod_option(int which);            // dod_api.hip; -1 when unset
 long gemm_tail_split_count();         // gemm_pp.hip: GEMM calls that took the tail-split path so far

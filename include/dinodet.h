@@ -503,6 +503,55 @@ int dod_backbone_tail_train_backward(const dod_config* cfg, const dod_bb_tail_pa
                                      const void* tape, size_t tape_bytes, const dod_bb_tail_params* grads, void* workspace,
                                      size_t workspace_bytes, void* stream);
 
+/* ---- training-step operators: the adjoint kernels of the three steps above, one at a time ---------------------------------
+ * What dod_decoder_train_*, dod_dense_decoder_train_* and dod_backbone_tail_train_* are made of (dec_train.hip, attn_f32m.hip), each
+ * behind a thin entry that validates its arguments and calls the launcher the step calls -- for parity tests at shapes the steps never
+ * run.  Stateless; every pointer is a caller-owned fp32 DEVICE buffer; enqueued on `stream`, no sync.  The "deterministic" test
+ * option / DINODET_DETERMINISTIC selects the ordered reductions exactly as in the steps (that mode keeps a library-owned partial-sum
+ * buffer).  DOD_ERR_INVALID before any launch for a NULL pointer or a shape outside the stated limits, DOD_ERR_STATE for a
+ * workspace that is too small; messages through dod_decoder_train_last_error().
+ *
+ * LayerNorm backward: x, dy, dx [rows, D] dense, D <= 2048.  dx is written; dgamma / dbeta [D] ACCUMULATE. */
+int dod_op_layernorm_bwd(const float* x, const float* gamma, const float* dy, float eps, int rows, int D, float* dx, float* dgamma,
+                         float* dbeta, void* stream);
+/* Attention forward + vector-Jacobian product in one call: o = dropout(softmax(scale q k^T)) v per (image, head), then dq, dk, dv
+ * for the upstream gradient d_o.  q [B*Lq, ldq], k / v [B*Lk, ldkv], o / d_o [B*Lq, ldo], dq [B*Lq, lddq], dk / dv [B*Lk, lddkv]: head h
+ * at columns h*dh of each, pitches multiples of 4 (q | k | v of one packed buffer: k = q + heads*dh, v = q + 2*heads*dh, ldq = ldkv).
+ * All four outputs are WRITTEN.
+ *   form 0  batched fp32 GEMMs around the softmax row kernels (the decoders' attention): head_dim <= 128, Lk <= 1408, dropout_p in
+ *           [0, 1) with the keep mask  u01(key, ((b*heads + h)*Lq + i)*Lk + j) >= dropout_p,  kept probabilities scaled by 1/(1-p);
+ *           u01(key, n) = (z >> 40) * 2^-24 for z = the splitmix64 finaliser of key + n * 0x9E3779B97F4A7C15 (mod 2^64)
+ *   form 1  the flash kernels (the backbone tail at >= 1 024 tokens): head_dim 64, dropout_p == 0; o comes from the forward that
+ *           also writes the log-sum-exp the adjoint recomputes its probabilities from
+ * workspace: dod_op_attention_f32_vjp_workspace_bytes(...) bytes (0 for a shape the form does not take; form 0 sizes it by the
+ * "mha_chunk_images" option in force at the time). */
+size_t dod_op_attention_f32_vjp_workspace_bytes(int B, int Lq, int Lk, int heads, int dh, int form);
+int dod_op_attention_f32_vjp(const float* q, int ldq, const float* k, const float* v, int ldkv, const float* d_o, float* o, int ldo,
+                             float* dq, int lddq, float* dk, float* dv, int lddkv, int B, int Lq, int Lk, int heads, int dh,
+                             float scale, int form, float dropout_p, uint64_t key, void* workspace, size_t workspace_bytes,
+                             void* stream);
+/* Adjoint of dod_op_deform_sample (same proj / values layout; dout [B*Q, Hd*dh]): dproj [B*Q, ldp] is zeroed and WRITTEN (columns
+ * 0..1 the reference logits, shared by all heads; then offsets; then point-weight logits), dvalues [B*N, Hd*dh] ACCUMULATES.
+ * 1 <= P <= 8, dh <= 128, hh*ww == N, ldp >= 2 + 3*Hd*P. */
+int dod_op_deform_sample_bwd(const float* proj, int ldp, const float* values, const float* dout, int B, int Q, int N, int Hd, int P,
+                             int dh, int hh, int ww, float* dproj, float* dvalues, void* stream);
+/* Gradients of one LoRA pair of out = X (W + alpha Bm A)^T:  dB [out_f, r] += alpha dY^T (X A^T),  dA [r, in_f] += alpha (dY Bm)^T X.
+ * X [M, in_f] dense, dY [M, out_f] with pitch ldy (a column block of a wider buffer), A [r, in_f], Bm [out_f, r]; 1 <= r <= 64
+ * (r <= 8: the rank-r kernels; above: the fp32 GEMMs, which take any pitch).  Both outputs ACCUMULATE. */
+size_t dod_op_lora_grads_workspace_bytes(int M, int r);
+int dod_op_lora_grads(const float* X, int in_f, const float* dY, int ldy, int out_f, const float* A, const float* Bm, int M, int r,
+                      float alpha, float* dA, float* dB, void* workspace, size_t workspace_bytes, void* stream);
+/* Element-wise adjoints; `out` is written (it may alias `a`).  keep(i) = u01(key, i) >= p as above; p in [0, 1).
+ *   DOD_PW_GELU_BWD       out[i] = a[i] * d/dx gelu_erf(b[i])                         a = dy, b = pre-activation, n elements
+ *   DOD_PW_SWIGLU_BWD     b = pre [n, 2*cols] = [x1 | x2], a = dh [n, cols] -> out [n, 2*cols] = [d x1 | d x2] of silu(x1) * x2
+ *   DOD_PW_RELU_DROP_BWD  out[i] = b[i] > 0 ? keep(i) a[i] / (1 - p) : 0            a = dy, b = the ReLU output
+ *   DOD_PW_DROPOUT_ADD    out[i] = a[i] + keep(i) b[i] / (1 - p)                      a may be NULL (out = dropped b)
+ *   DOD_PW_SIGMOID_BWD4   out[r][c] = a[r*cols + c] * s (1 - s), s = b[r*4 + c], c < 4   n rows, a with pitch cols >= 4 */
+enum dod_pointwise_op { DOD_PW_GELU_BWD = 0, DOD_PW_SWIGLU_BWD = 1, DOD_PW_RELU_DROP_BWD = 2, DOD_PW_DROPOUT_ADD = 3, DOD_PW_SIGMOID_BWD4 = 4 };
+int dod_op_train_pointwise(int op, const float* a, const float* b, float* out, size_t n, int cols, float p, uint64_t key, void* stream);
+/* dst[c] += sum_r src[r*ld + c], c < cols (the bias gradient) */
+int dod_op_colsum_add(const float* src, int ld, int rows, int cols, float* dst, void* stream);
+
 /* Scratch of the GEMMs' wave-quantisation tail split (K-split partial slabs; gemm_pp.hip) and of the fp32 GEMM's K split (gemm_f32.hip, fixed size).  dod_finalize_weights reserves 64 MiB on the
  * current device; operator-level callers (tests, tools) reserve it themselves.  Never allocated inside a forward / stream capture. */
 int dod_reserve_gemm_scratch(size_t bytes);
@@ -516,6 +565,8 @@ int dod_reserve_gemm_scratch(size_t bytes);
  *   "deterministic"    1 = ordered reductions instead of fp32 atomics in the training step's weight gradients (also DINODET_DETERMINISTIC=1)
  *   "f32_ksplit"       fp32 GEMM K split across workgroups (gemm_f32.hip): 0 = never, 1 = also in dod_op_linear (shipped: the decoder's small linears in
  *                      every mode but the strict fp32 one)
+ *   "attn_bwd_flash"   backbone-tail attention adjoint: 0 = never the flash form, 1 = whenever head_dim is 64 (shipped: from 1 024 tokens up;
+ *                      wins over DINODET_ATTN_BWD_FLASH).  Read when the tape and workspace are sized and in both passes: set it around a whole step
  * dod_test_counter("tail_splits"): GEMM calls that took the tail-split path so far; "rem_cuts": GEMM calls whose short last round ran as a
  * launch of its own (gemm_bf16.hip); "f32_ksplits": fp32 GEMM launches that split K across workgroups (gemm_f32.hip); -1 for an unknown name.
  * The in-kernel time stamps, the register-only MFMA probes and every tile / schedule override of the tuning rounds exist only in
@@ -528,7 +579,8 @@ const char* dod_version(void);
  * dtype argument at revision 2; revision 4 = this file: the dod_debug_* entry points left the release library, dod_test_* replaced the three
  * the tests use, the folded-LayerNorm operators arrived; revision 5: the dod_set_criterion_* entry points; revision 6: dod_match_assign*).
  * New entry points alone change no signature and no layout: dod_coco_eval_* and dod_op_sort_pairs_* joined revision 6, and a caller that
- * needs them resolves them by name (the Python binding fails at load when one is missing).
+ * needs them resolves them by name (the Python binding fails at load when one is missing).  The training-step operators
+ * (dod_op_layernorm_bwd ... dod_op_colsum_add) joined revision 6 the same way.
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);

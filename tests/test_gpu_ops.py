@@ -1,5 +1,6 @@
-"""`-m gpu`: every HIP kernel, called through the C ABI's operator entry points, against the CPU
-oracle / a plain fp32 torch statement of the same op, on seeded inputs.  Tolerances are written
+"""`-m gpu`: every HIP kernel of the inference path, called through the C ABI's operator entry points,
+against the CPU oracle / a plain fp32 torch statement of the same op, on seeded inputs (the training
+step's adjoint kernels: tests/test_gpu_train_ops.py, against float64).  Tolerances are written
 next to each comparison: fp32 kernels 1e-5-level (summation order only); bf16 kernels are
 compared with the SAME bf16-rounded operands evaluated in fp32 on the CPU."""
 import math

@@ -2,6 +2,7 @@
 the autograd composite of the same math (models/_autograd.py, itself pinned to the reference goldens by
 tests/test_train_composite.py): forward identical, every parameter gradient and d(memory) within 1e-4 -- the gradients
 `loss.backward()` at train.py:1101 produces for the decoder and heads."""
+import ctypes
 import os
 
 import numpy as np
@@ -227,12 +228,17 @@ def test_detector_train_step_uses_the_native_decoder_backward():
         assert rel_err(g1[k].cpu().numpy(), g0[k].cpu().numpy()) < 2e-3, k      # LoRA grads pass through two blocks of fp32 autograd
 
 
-@pytest.mark.parametrize("variant,R,B", [("micro", 70, 3), ("micro_r12", 70, 3), ("micro_swiglu", 70, 3), ("small", 224, 2), ("base", 224, 2),
-                                         ("small", 518, 1), ("giant3", 224, 2)])
-def test_native_backbone_tail_backward_matches_composite_autograd(variant, R, B):
+_TAIL_CASES = [("micro", 70, 3, -1), ("micro_r12", 70, 3, -1), ("micro_swiglu", 70, 3, -1), ("small", 224, 2, -1), ("base", 224, 2, -1),
+               ("small", 518, 1, -1), ("giant3", 224, 2, -1), ("micro", 70, 3, 1), ("small", 518, 1, 0)]
+
+
+@pytest.mark.parametrize("variant,R,B,flash", [pytest.param(*c, id=f"{c[0]}-{c[1]}-{c[2]}" + (f"-flash{c[3]}" if c[3] >= 0 else "")) for c in _TAIL_CASES])
+def test_native_backbone_tail_backward_matches_composite_autograd(variant, R, B, flash):
     """The LoRA-adapted blocks + final LayerNorm + projection (dod_backbone_tail_train_*): memory and the gradients of every
     lora_A / lora_B and of the projection against the composite's autograd on the same frozen-prefix output.  micro_r12: rank 12
-    takes the generic rank-r products (k-major fp32 GEMMs) instead of the r <= 8 kernels; 518: 1 370 tokens per image."""
+    takes the generic rank-r products (k-major fp32 GEMMs) instead of the r <= 8 kernels; 518: 1 370 tokens per image.
+    flash: the "attn_bwd_flash" test option (-1 the shipped rule: the flash-style attention adjoint from 1 024 tokens up): the flash
+    form at 26 tokens, the batched-GEMM form at 1 370 -- each held to the float64 bound of the FORM it takes, not of its token count."""
     from dinov2_od_amd.config import BackboneConfig
     from dinov2_od_amd.models import DINOv2Backbone
     from tests import gpu_util as G
@@ -258,11 +264,13 @@ def test_native_backbone_tail_backward_matches_composite_autograd(variant, R, B)
     def run(native):
         os.environ["DINODET_NATIVE_TRAIN"] = "1" if native else "0"
         try:
+            nat.set_option("attn_bwd_flash", flash)
             m.zero_grad(set_to_none=True)
             mem = m(x)
             (mem * wgt).sum().backward()
             return mem.detach().clone(), {k: p.grad.detach().clone() for k, p in m.named_parameters() if p.grad is not None}
         finally:
+            nat.set_option("attn_bwd_flash", -1)
             os.environ.pop("DINODET_NATIVE_TRAIN", None)
     m0, g0 = run(False)
     m1, g1 = run(True)
@@ -282,6 +290,21 @@ def test_native_backbone_tail_backward_matches_composite_autograd(variant, R, B)
     # rounding grows with the length of the softmax / token reductions: 257 tokens stay inside 1e-4 of the fp32 composite; at 1 370
     # tokens the two fp32 evaluations sit ~1e-4 apart and the native one must be no further from float64 than twice the composite
     tol = 1e-4 if N <= 257 else 3e-4
+    # which adjoint the library takes, from the library: the flash form carves no [B*H, N, N] score / adjoint scratch, so its workspace is the
+    # smaller one -- forcing either form must change the size, and the case's own setting must give the size of exactly one of them
+    from dinov2_od_amd.config import DecoderConfig
+    from dinov2_od_amd.engine import make_config
+    cfg = make_config(bb, DecoderConfig(), "fp32")
+    ws = {}
+    try:
+        for o in (0, 1, flash):
+            nat.set_option("attn_bwd_flash", o)
+            ws[o] = nat.lib().dod_backbone_tail_workspace_bytes(ctypes.byref(cfg), B, N, 2)
+    finally:
+        nat.set_option("attn_bwd_flash", -1)
+    assert 0 < ws[1] < ws[0], ws
+    flash_form = ws[flash] == ws[1]
+    assert flash_form == (flash == 1 or (flash < 0 and N >= 1024)), (ws, "the library did not take the attention adjoint this case is about")
     worst = ("", 0.0)
     worst64 = ("", 0.0, 0.0)
     for k in g0:
@@ -291,9 +314,9 @@ def test_native_backbone_tail_backward_matches_composite_autograd(variant, R, B)
         ref = g64[k].numpy()
         en, ec = rel_err(g1[k].double().cpu().numpy(), ref), rel_err(g0[k].double().cpu().numpy(), ref)
         worst64 = max(worst64, (k, en, ec), key=lambda t: t[1])
-        # the flash-style attention adjoint (N >= 1 024 tokens) takes delta = <dO, O> from the forward's rounded output: measured 5.3e-5
-        # from float64 on the worst tensor at 1 370 tokens, where the batched form gave 1.7e-5 and the composite 2.3e-5
-        assert en < (max(2e-5, 2.0 * ec) if N < 1024 else max(8e-5, 3.0 * ec)), (k, en, ec)
+        # the flash-style attention adjoint (shipped from 1 024 tokens up; every variant here has head_dim 64) takes delta = <dO, O> from the
+        # forward's rounded output and sits further from float64 than the batched form: each run prints both distances below
+        assert en < (max(8e-5, 3.0 * ec) if flash_form else max(2e-5, 2.0 * ec)), (k, en, ec)
     assert worst[1] > 0.0, "both runs took the same path"
     print(f"backbone tail {variant} R={R}: vs float64 worst native {worst64[1]:.2e} (composite {worst64[2]:.2e}) at {worst64[0]}")
     print(f"backbone tail {variant} R={R}: memory {rel_err(m1.cpu().numpy(), m0.cpu().numpy()):.2e}, worst gradient {worst[0]} {worst[1]:.2e}")

@@ -91,6 +91,82 @@ def test_decoder_train_entry_points_validate_arguments(lib):
     assert rc == 1 and b"null" in lib.dod_decoder_train_last_error()
 
 
+def test_training_operators_validate_arguments(lib):
+    """dod_op_layernorm_bwd ... dod_op_colsum_add: a null pointer or a shape past a documented limit is DOD_ERR_INVALID before any
+    launch (no GPU here: a launch would be DOD_ERR_HIP), a short workspace DOD_ERR_STATE; the workspace queries return 0 for the same
+    shapes.  `p` stands in for device pointers that are never dereferenced."""
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p)
+    err = lib.dod_decoder_train_last_error
+    big = 1 << 30
+    # LayerNorm backward: D <= 2048
+    assert lib.dod_op_layernorm_bwd(p, p, p, 1e-6, 4, 2052, p, p, p, None) == 1 and b"2048" in err()
+    assert lib.dod_op_layernorm_bwd(p, p, p, 1e-6, 0, 64, p, p, p, None) == 1
+    for i in (0, 1, 2, 6, 7, 8):
+        a = [p, p, p, 1e-6, 4, 64, p, p, p, None]
+        a[i] = None
+        assert lib.dod_op_layernorm_bwd(*a) == 1 and b"null" in err(), i
+    # attention: form 0 takes Lk <= 1408, form 1 head_dim 64 and no dropout; head_dim <= 128
+    ws = lib.dod_op_attention_f32_vjp_workspace_bytes
+    assert ws(1, 3, 1408, 1, 64, 0) > 0 and ws(1, 3, 1409, 1, 64, 0) == 0
+    assert ws(1, 3, 1409, 1, 64, 1) > 0 and ws(1, 3, 7, 1, 32, 1) == 0 and ws(1, 3, 7, 1, 132, 0) == 0 and ws(1, 3, 7, 1, 64, 2) == 0
+
+    def vjp(B=1, Lq=3, Lk=7, heads=1, dh=64, form=0, drop=0.0, ld=None, nbytes=big, null=None):
+        ld = heads * dh if ld is None else ld
+        a = [p, ld, p, p, ld, p, p, ld, p, ld, p, p, ld, B, Lq, Lk, heads, dh, 0.125, form, drop, 7, p, nbytes, None]
+        if null is not None:
+            a[null] = None
+        return lib.dod_op_attention_f32_vjp(*a)
+    assert vjp(Lk=1409, form=0) == 1 and b"1408" in err()
+    assert vjp(dh=32, form=1) == 1 and vjp(dh=96, form=1) == 1 and b"head_dim 64" in err()
+    assert vjp(dh=132, form=0) == 1 and vjp(form=2) == 1
+    assert vjp(form=1, drop=0.1) == 1 and b"dropout" in err()
+    assert vjp(form=0, drop=1.0) == 1
+    assert vjp(ld=66) == 1 and vjp(ld=60) == 1 and b"pitch" in err()
+    assert vjp(nbytes=16) == 3 and b"workspace" in err()
+    for i in (0, 2, 3, 5, 6, 8, 10, 11, 22):
+        assert vjp(null=i) == 1 and b"null" in err(), i
+    # deformable adjoint: 1 <= P <= 8, head_dim <= 128, h * w == N, pitch >= 2 + 3 Hd P
+    def dfm(P=2, dh=32, hh=2, ww=13, ldp=16, null=None):
+        a = [p, ldp, p, p, 1, 3, 26, 2, P, dh, hh, ww, p, p, None]
+        if null is not None:
+            a[null] = None
+        return lib.dod_op_deform_sample_bwd(*a)
+    assert dfm(P=9, ldp=64) == 1 and b"points" in err()
+    assert dfm(P=0) == 1 and dfm(dh=132) == 1
+    assert dfm(hh=5, ww=5) == 1 and b"feature map" in err()
+    assert dfm(ldp=12) == 1 and b"pitch" in err()
+    for i in (0, 2, 3, 12, 13):
+        assert dfm(null=i) == 1 and b"null" in err(), i
+    # LoRA gradients: 1 <= r <= 64
+    assert lib.dod_op_lora_grads_workspace_bytes(130, 64) > 0
+    assert lib.dod_op_lora_grads_workspace_bytes(130, 65) == 0 and lib.dod_op_lora_grads_workspace_bytes(130, 0) == 0
+
+    def lora(r=2, ldy=36, nbytes=big, null=None):
+        a = [p, 100, p, ldy, 36, p, p, 65, r, 1.0, p, p, p, nbytes, None]
+        if null is not None:
+            a[null] = None
+        return lib.dod_op_lora_grads(*a)
+    assert lora(r=0) == 1 and lora(r=65) == 1 and b"1..64" in err()
+    assert lora(ldy=32) == 1
+    assert lora(nbytes=16) == 3
+    for i in (0, 2, 5, 6, 10, 11, 12):
+        assert lora(null=i) == 1 and b"null" in err(), i
+    # element-wise adjoints and the column sum
+    pw = lib.dod_op_train_pointwise
+    assert pw(nat.PW["gelu_bwd"], None, p, p, 8, 0, 0.0, 0, None) == 1 and b"null" in err()
+    assert pw(nat.PW["dropout_add"], None, None, p, 8, 0, 0.0, 0, None) == 1
+    assert pw(nat.PW["dropout_add"], None, p, None, 8, 0, 0.0, 0, None) == 1
+    assert pw(nat.PW["relu_drop_bwd"], p, p, p, 8, 0, 1.0, 0, None) == 1
+    assert pw(nat.PW["swiglu_bwd"], p, p, p, 8, 0, 0.0, 0, None) == 1
+    assert pw(nat.PW["sigmoid_bwd4"], p, p, p, 8, 3, 0.0, 0, None) == 1
+    assert pw(17, p, p, p, 8, 0, 0.0, 0, None) == 1 and b"unknown op" in err()
+    assert lib.dod_op_colsum_add(None, 4, 4, 4, p, None) == 1 and lib.dod_op_colsum_add(p, 4, 4, 4, None, None) == 1
+    assert lib.dod_op_colsum_add(p, 3, 4, 4, p, None) == 1
+    # the new test option is known by name
+    assert lib.dod_test_set_option(b"attn_bwd_flash", 1) == 0 and lib.dod_test_set_option(b"attn_bwd_flash", -1) == 0
+
+
 def test_create_validates_arguments(lib):
     bb, dc = cases.cfg1(25)
     h = C.c_void_p()
