@@ -119,6 +119,7 @@ SYMBOLS = {
     "dod_op_split_pair": (_I, [_P, _I, _I, _I, _P, _P]),
     "dod_op_linear_x3": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "dod_op_attention_x3": (_I, [_P, _P, _I, _I, _I, _F, _P]),
+    "dod_op_attention_x3_h2": (_I, [_P, _P, _I, _I, _I, _F, _P]),
     "dod_op_split_h2": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "dod_op_linear_h2": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "dod_op_layernorm": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, _I, _P]),
@@ -126,6 +127,7 @@ SYMBOLS = {
     "dod_op_rowstats": (_I, [_P, _I, _I, _F, _P, _I, _P, _P]),
     "dod_op_ln_finalize": (_I, [_P, _I, _I, _F, _P, _P]),
     "dod_op_attention_bf16": (_I, [_P, _P, _I, _I, _I, _F, _P]),
+    "dod_op_attention_bf16_mx": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     "dod_op_attention_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P]),
     "dod_op_deform_sample": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "dod_op_pos_resize": (_I, [_P, _I, _I, _I, _I, _P, _P]),

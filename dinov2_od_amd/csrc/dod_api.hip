@@ -407,6 +407,17 @@ int dod_op_attention_x3(const void* qkv2, void* ctx2, int B, int N, int heads, f
   if (!qkv2 || !ctx2) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
   return rejected(nullptr, launch_attn_x3((const bf16_t*)qkv2, (bf16_t*)ctx2, B, N, heads, scale, (hipStream_t)stream), "dod_op_attention_x3");
 }
+// both flash kernels index their grid (8-padded (image, head) pairs x query blocks of at least 128 rows, plus one tail block per pair) with an int
+static bool attn_grid_fits(int B, int N, int heads) {
+  return (((long long)B * heads + 7) / 8 * 8) * (((long long)N + 127) / 128 + 1) <= 0x7fffffffLL;
+}
+// the H2 epilogue of the same kernel (ctx_h2 = 1): what the fp16x2 forward launches
+int dod_op_attention_x3_h2(const void* qkv2, void* ctx_h2, int B, int N, int heads, float scale, void* stream) {
+  if (!qkv2 || !ctx_h2) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
+  if (B <= 0 || N <= 0 || heads <= 0) return fail(nullptr, DOD_ERR_INVALID, "dod_op_attention_x3_h2: B=%d N=%d heads=%d must be positive", B, N, heads);
+  if (!attn_grid_fits(B, N, heads)) return fail(nullptr, DOD_ERR_INVALID, "dod_op_attention_x3_h2: B=%d N=%d heads=%d is more workgroups than one launch holds", B, N, heads);
+  return rejected(nullptr, launch_attn_x3((const bf16_t*)qkv2, (bf16_t*)ctx_h2, B, N, heads, scale, (hipStream_t)stream, 1), "dod_op_attention_x3_h2");
+}
 int dod_op_quant_rows_fp8(const void* x, int in_dtype, int ld, int rows, int cols, void* q, int ldq, float* scale, void* stream) {
   if (!x || !q || !scale) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
   return rejected(nullptr, launch_quant_rows_fp8(x, in_dtype == DOD_BF16, ld, rows, cols, (unsigned char*)q, ldq, scale, (hipStream_t)stream), "dod_op_quant_rows_fp8 rows=%d cols=%d", rows, cols);
@@ -418,6 +429,13 @@ int dod_op_layernorm(const float* x, const float* add, const float* gamma, const
 int dod_op_attention_bf16(const void* qkv, void* ctx, int B, int N, int heads, float scale, void* stream) {
   if (!qkv || !ctx) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
   return rejected(nullptr, launch_attn_bf16((const bf16_t*)qkv, (bf16_t*)ctx, B, N, heads, scale, (hipStream_t)stream), "dod_op_attention_bf16");
+}
+// the block-scaled e4m3 epilogue of the same kernel (ctx_bs set): what the fp8 forward launches
+int dod_op_attention_bf16_mx(const void* qkv, void* ctx_q8, void* ctx_bs, int B, int N, int heads, float scale, void* stream) {
+  if (!qkv || !ctx_q8 || !ctx_bs) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
+  if (B <= 0 || N <= 0 || heads <= 0) return fail(nullptr, DOD_ERR_INVALID, "dod_op_attention_bf16_mx: B=%d N=%d heads=%d must be positive", B, N, heads);
+  if (!attn_grid_fits(B, N, heads)) return fail(nullptr, DOD_ERR_INVALID, "dod_op_attention_bf16_mx: B=%d N=%d heads=%d is more workgroups than one launch holds", B, N, heads);
+  return rejected(nullptr, launch_attn_bf16((const bf16_t*)qkv, (bf16_t*)ctx_q8, B, N, heads, scale, (hipStream_t)stream, (unsigned char*)ctx_bs), "dod_op_attention_bf16_mx");
 }
 int dod_op_attention_f32(const float* q, const float* k, const float* v, float* o, int ldq, int ldk, int ldv, int ldo, int Lq, int Lk,
                          int B, int heads, int dh, float scale, void* stream) {

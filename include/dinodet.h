@@ -203,6 +203,9 @@ int dod_op_split_pair(const float* x, int ld, int rows, int cols, void* out, voi
 int dod_op_linear_x3(const void* A2, const void* W2, int M, int N, int K, const float* bias, const float* scale,
                      const float* resid, int ldr, void* out, int out_layout, int ldc, int act, void* stream);
 int dod_op_attention_x3(const void* qkv2, void* ctx2, int B, int N, int heads, float scale, void* stream);
+/* The same attention with the fp16x2 mode's epilogue: ctx_h2 [B*N] H2 activation rows of D = heads*64 columns (4*D bytes per row, the A
+ * operand of dod_op_linear_h2 with K = D): [ fp16(x) x D | per 16-column group: 16 x e4m3(h), 16 x e4m3((x - h) 2^11) ], h = fp16(x). */
+int dod_op_attention_x3_h2(const void* qkv2, void* ctx_h2, int B, int N, int heads, float scale, void* stream);
 /* fp16x2 (parity-gated mode) operators.  H2 operand format of a [rows, cols] matrix (cols % 32 == 0), 4*cols bytes per row:
  *   [ fp16(x) x cols | per 32-column block: 32 x e4m3(h 2^e), 32 x e4m3((x - h) 2^(e+11)) ],  h = fp16(x);
  *   activations: e = 0; weights (wexp != NULL): per row e = floor(log2(448 / max|h|)), wexp[row] = 127 - e (E8M0 byte) and the
@@ -244,6 +247,11 @@ int dod_op_layernorm(const float* x, const float* add, const float* gamma, const
                      int rows, int D, void* out, int out_dtype, void* stream);
 /* qkv [B*N, 3*heads*64] bf16 -> ctx [B*N, heads*64] bf16 */
 int dod_op_attention_bf16(const void* qkv, void* ctx, int B, int N, int heads, float scale, void* stream);
+/* The same attention with the fp8 mode's epilogue: the context leaves block-scaled, ctx_q8 [B*N, D] e4m3 bytes (D = heads*64; a head's 64
+ * columns are two blocks of 32) and ctx_bs [B*N][2][D / 64] e8m0 bytes in the dod_op_quant_mx_fp8 order: block b of a row (columns
+ * 32 b .. 32 b + 31) at byte (b & 1) * (D / 64) + (b >> 1); value = q * 2^(byte - 127), an all-zero block has byte 1.  Together they are
+ * the A operand of dod_op_linear_fp8_mx / _mx2 with K = D. */
+int dod_op_attention_bf16_mx(const void* qkv, void* ctx_q8, void* ctx_bs, int B, int N, int heads, float scale, void* stream);
 int dod_op_attention_f32(const float* q, const float* k, const float* v, float* o, int ldq, int ldk, int ldv,
                          int ldo, int Lq, int Lk, int B, int heads, int dh, float scale, void* stream);
 /* proj [B*Q, ldp] = [ref logits(2) | offsets(Hd*P*2) | weight logits(Hd*P)], values [B*N, Hd*dh] -> out [B*Q, Hd*dh] */

@@ -159,8 +159,11 @@ def _attn_ref(q, k, v, scale):
     return torch.softmax(s, -1) @ v.double()
 
 
-# the last five reach the 512-thread ping-pong kernel (heads * B * ceil(N / 256) >= 1024): an even and an odd number of key tiles (22, 23; the two
-# wave groups split the keys), the short-tail launch form (1370 = 5 x 256 + 90), a partial last block without it (577), ONE key tile (group 1 idle)
+# the first five run the 32-rows-per-wave body (attn_bf16_kernel<1>); the last five have heads * B * ceil(N / 256) >= 1024 and select the
+# 64-rows-per-wave body: (16, 1370, 12), (32, 577, 12) and (43, 300, 12) as the fused short-tail launch (remainders 90, 65, 44 <= 128: the trailing
+# workgroups run the 32-row body over them), (15, 1440, 12) as one launch with a long remainder (160 rows), (130, 60, 8) with ONE key tile and no full
+# query block.  (The 512-thread ping-pong form these shapes were first chosen for was not kept: attn_bf16.hip.)  Every form and output format against
+# float64 with per-element bounds and guard rows: tests/test_gpu_attention.py
 @pytest.mark.parametrize("B,N,heads", [(1, 17, 2), (2, 64, 1), (2, 257, 6), (1, 1370, 12), (3, 130, 2),
                                        (16, 1370, 12), (15, 1440, 12), (32, 577, 12), (130, 60, 8), (43, 300, 12)])
 def test_attention_bf16(G, B, N, heads):
@@ -180,8 +183,8 @@ def test_attention_bf16(G, B, N, heads):
 
 @pytest.mark.parametrize("B,heads", [(1, 1), (300, 2)], ids=["4-wave", "ping-pong"])
 def test_attention_bf16_forced_rescale(G, B, heads):
-    """Online-softmax rescale path: one key per later tile dominates every row (cdna guide rule 26).  In the ping-pong kernel the spikes sit
-    in DIFFERENT wave groups' key halves (tiles 0-2 / 3-4), so the final merge has to rescale as well."""
+    """Online-softmax rescale path: one key per later tile dominates every row (cdna guide rule 26).  (1, 1): the 32-rows-per-wave body;
+    (300, 2), whose id dates from a kernel form that was not kept: the 64-rows-per-wave body in the fused short-tail launch (300 = 256 + 44)."""
     N, D = 300, 64 * heads
     rng = np.random.default_rng(7)
     x = (rng.standard_normal((B, N, 3 * D)) * 0.5).astype(np.float32)

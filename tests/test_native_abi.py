@@ -167,6 +167,30 @@ def test_training_operators_validate_arguments(lib):
     assert lib.dod_test_set_option(b"attn_bwd_flash", 1) == 0 and lib.dod_test_set_option(b"attn_bwd_flash", -1) == 0
 
 
+def test_attention_epilogue_operators_validate_arguments(lib):
+    """dod_op_attention_bf16_mx / dod_op_attention_x3_h2 (the fp8 and fp16x2 modes' context epilogues): a null pointer, a non-positive
+    size or a grid past one launch is DOD_ERR_INVALID with a message before any launch (no GPU here: a launch would be DOD_ERR_HIP)."""
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p)
+    err = lambda: lib.dod_last_error(None)
+    mx, h2 = lib.dod_op_attention_bf16_mx, lib.dod_op_attention_x3_h2
+    for i in (0, 1, 2):
+        a = [p, p, p, 1, 17, 2, 0.125, None]
+        a[i] = None
+        assert mx(*a) == 1 and b"null" in err(), i
+    for i in (0, 1):
+        a = [p, p, 1, 17, 2, 0.125, None]
+        a[i] = None
+        assert h2(*a) == 1 and b"null" in err(), i
+    for B, N, heads in [(0, 17, 2), (-1, 17, 2), (1, 0, 2), (1, -5, 2), (1, 17, 0), (1, 17, -3)]:
+        assert mx(p, p, p, B, N, heads, 0.125, None) == 1 and b"dod_op_attention_bf16_mx" in err() and b"positive" in err(), (B, N, heads)
+        assert h2(p, p, B, N, heads, 0.125, None) == 1 and b"dod_op_attention_x3_h2" in err() and b"positive" in err(), (B, N, heads)
+    # 2^20 images x 2^10 heads x 9 query blocks: more workgroups than a launch's int index
+    assert mx(p, p, p, 1 << 20, 1000, 1 << 10, 0.125, None) == 1 and b"workgroups" in err()
+    assert h2(p, p, 1 << 20, 1000, 1 << 10, 0.125, None) == 1 and b"workgroups" in err()
+    assert mx(p, p, p, 1 << 16, 1, 1 << 16, 0.125, None) == 1 and h2(p, p, 1 << 16, 1, 1 << 16, 0.125, None) == 1      # B * heads past an int
+
+
 def test_create_validates_arguments(lib):
     bb, dc = cases.cfg1(25)
     h = C.c_void_p()
