@@ -174,7 +174,7 @@ int launch_attn_f32_mfma(const AttnF32& a, hipStream_t s) {
 
 
 // =============================================================================================================================
-// Flash-style adjoint (head_dim 64): the training step's backbone-tail attention backward (dec_train.hip) without the [B*H, N, N]
+// Flash-style adjoint (head_dim 64): the training step's backbone-tail attention backward (tail_train.hip) without the [B*H, N, N]
 // score / probability / adjoint buffers of the batched-GEMM form (~6 GB of traffic per ViT-B block at 8 x 1 370 tokens).  Scores are
 // recomputed tile by tile from q, k and the forward's log-sum-exp; every product on the exact-fp32 MFMA:
 //   P = 2^(s c - m_q) / l_q  (the forward's row max and sum),  dP = dO V^T,  dS = P o (dP - delta_q),  delta_q = <dO_q, O_q>

@@ -26,7 +26,7 @@ enum { DOD_OPT_TAILSPLIT = 0,         // GEMM wave-quantisation tail split: 0 of
        DOD_OPT_LN_FOLD,               // 0 = LayerNorm kernels instead of the folded form (read at dod_finalize_weights)
        DOD_OPT_DETERMINISTIC,         // 1 = ordered reductions instead of fp32 atomics in the training step's weight gradients
        DOD_OPT_F32_KSPLIT,            // fp32 GEMM K split across workgroups (gemm_f32.hip): 0 = never, 1 = also for the operator dod_op_linear
-       DOD_OPT_ATTN_BWD_FLASH,        // backbone-tail attention adjoint (dec_train.hip tail_flash_bwd): 0 = never the flash form, 1 = whenever head_dim is 64
+       DOD_OPT_ATTN_BWD_FLASH,        // backbone-tail attention adjoint (tail_train.hip tail_flash_bwd): 0 = never the flash form, 1 = whenever head_dim is 64
        DOD_OPT_COUNT };
 int dod_option(int which);            // dod_api.hip; -1 when unset
 long gemm_tail_split_count();         // gemm_pp.hip: GEMM calls that took the tail-split path so far
@@ -216,7 +216,7 @@ int launch_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int
                     const GemmEpi& e, hipStream_t s, bool allow_ksplit = false);      // allow_ksplit: gemm_f32.hip "K split across workgroups" (never in the strict fp32 mode)
 int gemm_f32_ksplit_reserve();      // scratch of that split; outside any stream capture
 long gemm_f32_ksplit_count();
-// The same exact-fp32 MFMA main loop for the training step's products (dec_train.hip): either operand may be given k-major
+// The same exact-fp32 MFMA main loop for the training step's products (train_ops.hip): either operand may be given k-major
 // ([K, rows]: the transposed products of a backward need no transposed copies), a two-level batch (image, head) walks strided views
 // (attention scores / context / their adjoints as batched GEMMs), the K range may be split over grid.z with an atomic accumulate.
 //   C[z] (+)= alpha * A[z] W[z]^T (+ bias, activation);   z = zb * hb + zh,  X[z] = X + zb * x_sb + zh * x_sh   (strides in floats)
@@ -291,7 +291,7 @@ struct AttnF32 {
 int launch_attn_f32(const AttnF32& a, hipStream_t s);
 // Adjoint of launch_attn_f32 without materialised scores (attn_f32m.hip; head_dim 64, exact-fp32 MFMA): q | k | v and their gradients
 // as strided [rows, ld] views like the forward's, o / d_o [B*Lq, ldo], lse from the forward, delta [B, heads, Lq] scratch.
-// Returns 2 when the shape is not taken: callers decide BEFORE sizing their scratch (dec_train.hip tail_flash_bwd is the one predicate and
+// Returns 2 when the shape is not taken: callers decide BEFORE sizing their scratch (tail_train.hip tail_flash_bwd is the one predicate and
 // implies every check made here), so behind that predicate a 2 is a programming error, not a fallback.
 struct AttnF32Bwd {
   const float *q, *k, *v, *o, *d_o, *lse;

@@ -3,7 +3,7 @@
 // gated at 1e-3 against the reference's fp32 CPU forward, (b) every decoder/head linear in both
 // modes (K11-K13, K17-K19: deformable_attention.py:86-94,181,232-238,264-266; detr_decoder.py:80-81),
 // whose sampling-coordinate math must stay fp32 (floor() at deformable_attention.py:114-115), and
-// (c) every product of the native training step (dec_train.hip; train.py:1079-1109).
+// (c) every product of the native training step (train_ops.hip; train.py:1079-1109).
 //   C[M,N] = A[M,K] * W[N,K]^T, arbitrary M, N, K (guarded).
 // Tile 64x64x16, 256 threads = 4 waves (2x2), one 32x32 accumulator per wave, computed transposed
 // (D = W_tile * A_tile^T) so a lane owns an output row and register quads run along n.

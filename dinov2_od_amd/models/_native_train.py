@@ -1,5 +1,5 @@
 """train()-mode decoder + heads on the native kernels: forward with a tape, hand-written HIP backward (SURVEY.md section 8 row f1,
-first slice; dinov2_od_amd/csrc/dec_train.hip).
+first slice; schedules in dinov2_od_amd/csrc/dec_train.hip and tail_train.hip, kernels in train_ops.hip).
 
 `decoder_train(module, src)` is what DETRDecoder.forward evaluates in train() mode for the deformable branch on the GPU: a
 torch.autograd.Function whose forward is `dod_decoder_train_forward` (dropout at the reference's five sites --
@@ -8,6 +8,7 @@ deformable_attention.py:195-209, 235, 261, 265-266 -- from a counter-based hash)
 one accumulator per tensor) and of `src`, through which autograd continues into the projection and the LoRA-adapted blocks (those
 are still the composite of models/_autograd.py).  torch supplies tensors, the stream and the autograd graph edge; no arithmetic.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -56,11 +57,11 @@ def supported(m, src):
     return nat.lib().dod_decoder_train_tape_bytes(C.byref(cfg), int(src.shape[0]), int(src.shape[1])) > 0
 
 
-def _struct(tensors):
+def _struct(tensors, cfg=None):
     s = nat.DodDecTrainParams()
     for f, t in zip(nat.DEC_TRAIN_FIELDS, tensors):
         setattr(s, f, t.data_ptr())
-    return s
+    return s, None              # no keepalive: the struct holds no host array
 
 
 def _check(rc):
@@ -69,50 +70,61 @@ def _check(rc):
         raise (ValueError if rc == 1 else RuntimeError)(msg.decode() if msg else f"dinodet error {rc}")
 
 
-class _DecoderTrain(torch.autograd.Function):
+# What tells the two decoder steps apart: the four entry points dod_<stem>_train_{tape_bytes, workspace_bytes, forward, backward}, the
+# builder of the parameter struct (tensors, cfg) -> (struct, keepalive), and whether d(memory) may be NULL when autograd does not ask for it
+_Step = collections.namedtuple("_Step", "stem struct null_d_memory")
+
+
+class _DecoderStep(torch.autograd.Function):
+    """train-mode forward with a tape and the native backward of either decoder branch"""
+
     @staticmethod
-    def forward(ctx, src, cfg, p, seed, *params):
-        L = nat.lib()
+    def forward(ctx, src, step, cfg, p, seed, *params):
+        fn = {k: getattr(nat.lib(), f"dod_{step.stem}_train_{k}") for k in ("tape_bytes", "workspace_bytes", "forward", "backward")}
         B, N, _ = src.shape
         src = src.contiguous()
         params = [t.detach().contiguous() for t in params]
         with torch.cuda.device(src.device):
-            tape = torch.empty(L.dod_decoder_train_tape_bytes(C.byref(cfg), B, N), dtype=torch.uint8, device=src.device)
-            ws = torch.empty(L.dod_decoder_train_workspace_bytes(C.byref(cfg), B, N), dtype=torch.uint8, device=src.device)
+            tape = torch.empty(fn["tape_bytes"](C.byref(cfg), B, N), dtype=torch.uint8, device=src.device)
+            ws = torch.empty(fn["workspace_bytes"](C.byref(cfg), B, N), dtype=torch.uint8, device=src.device)
             if tape.numel() == 0 or ws.numel() == 0:
                 raise ValueError("decoder configuration not supported by the native training kernels")
             det = torch.empty(B, cfg.num_queries, cfg.num_classes + 4, dtype=torch.float32, device=src.device)
-            ps = _struct(params)
-            _check(L.dod_decoder_train_forward(C.byref(cfg), C.byref(ps), nat.ptr(src), B, N, float(p), int(seed), nat.ptr(det), nat.ptr(tape),
-                                               tape.numel(), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+            ps, keep = step.struct(params, cfg)
+            _check(fn["forward"](C.byref(cfg), C.byref(ps), nat.ptr(src), B, N, float(p), int(seed), nat.ptr(det), nat.ptr(tape), tape.numel(),
+                                 nat.ptr(ws), ws.numel(), nat.stream_ptr()))
         ctx.save_for_backward(src, tape, *params)
-        ctx.cfg, ctx.p, ctx.seed, ctx.ws = cfg, float(p), int(seed), ws
+        ctx.step, ctx.fn, ctx.cfg, ctx.p, ctx.seed, ctx.ws = step, fn, cfg, float(p), int(seed), ws
         return det
 
     @staticmethod
     def backward(ctx, d_det):
-        L = nat.lib()
         src, tape, *params = ctx.saved_tensors
-        cfg = ctx.cfg
+        step, cfg = ctx.step, ctx.cfg
         B, N, _ = src.shape
         d_det = d_det.contiguous().float()
         with torch.cuda.device(src.device):
             grads = [torch.zeros_like(t) for t in params]
-            d_src = torch.empty_like(src) if ctx.needs_input_grad[0] else None
-            ps, gs = _struct(params), _struct(grads)
-            _check(L.dod_decoder_train_backward(C.byref(cfg), C.byref(ps), nat.ptr(src), B, N, ctx.p, ctx.seed, nat.ptr(d_det), nat.ptr(tape),
-                                                tape.numel(), C.byref(gs), nat.ptr(d_src), nat.ptr(ctx.ws), ctx.ws.numel(), nat.stream_ptr()))
-        return (d_src, None, None, None, *grads)
+            d_src = torch.empty_like(src) if ctx.needs_input_grad[0] or not step.null_d_memory else None
+            (ps, k1), (gs, k2) = step.struct(params, cfg), step.struct(grads, cfg)
+            _check(ctx.fn["backward"](C.byref(cfg), C.byref(ps), nat.ptr(src), B, N, ctx.p, ctx.seed, nat.ptr(d_det), nat.ptr(tape), tape.numel(),
+                                      C.byref(gs), nat.ptr(d_src), nat.ptr(ctx.ws), ctx.ws.numel(), nat.stream_ptr()))
+        return (d_src, None, None, None, None, *grads)
+
+
+def _draw_seed():
+    """one draw of torch's generator per call (so torch.manual_seed governs the masks), mixed with a call counter"""
+    _seed_counter[0] += 1
+    return (int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) << 20) ^ _seed_counter[0]
+
+
+_DEFORMABLE = _Step("decoder", _struct, null_d_memory=True)
 
 
 def decoder_train(m, src, seed=None):
     """DETRDecoder.forward in train() mode -> packed detections [B, Q, C+4] with the autograd edge to the native backward"""
     cfg = make_config(m._bb_cfg, m._dc_cfg, "fp32")
-    if seed is None:
-        # one draw of torch's generator per call (so torch.manual_seed governs the masks), mixed with a call counter
-        _seed_counter[0] += 1
-        seed = (int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) << 20) ^ _seed_counter[0]
-    return _DecoderTrain.apply(src, cfg, dropout_rate(m), seed, *_param_list(m))
+    return _DecoderStep.apply(src, _DEFORMABLE, cfg, dropout_rate(m), _draw_seed() if seed is None else seed, *_param_list(m))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -166,7 +178,8 @@ def dense_supported(m, src):
     return nat.lib().dod_dense_decoder_train_tape_bytes(C.byref(cfg), int(src.shape[0]), int(src.shape[1])) > 0
 
 
-def _dense_struct(tensors, nlayers):
+def _dense_struct(tensors, cfg):
+    nlayers = cfg.dec_layers
     layers = (nat.DodDenseLayerParams * nlayers)()
     it = iter(tensors)
     for lp in layers:
@@ -179,51 +192,13 @@ def _dense_struct(tensors, nlayers):
     return ps, layers          # keep `layers` alive as long as `ps`
 
 
-class _DenseDecoderTrain(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, src, cfg, p, seed, *params):
-        L = nat.lib()
-        B, N, _ = src.shape
-        src = src.contiguous()
-        params = [t.detach().contiguous() for t in params]
-        nl = cfg.dec_layers
-        with torch.cuda.device(src.device):
-            tape = torch.empty(L.dod_dense_decoder_train_tape_bytes(C.byref(cfg), B, N), dtype=torch.uint8, device=src.device)
-            ws = torch.empty(L.dod_dense_decoder_train_workspace_bytes(C.byref(cfg), B, N), dtype=torch.uint8, device=src.device)
-            if tape.numel() == 0 or ws.numel() == 0:
-                raise ValueError("decoder configuration not supported by the native training kernels")
-            det = torch.empty(B, cfg.num_queries, cfg.num_classes + 4, dtype=torch.float32, device=src.device)
-            ps, keep = _dense_struct(params, nl)
-            _check(L.dod_dense_decoder_train_forward(C.byref(cfg), C.byref(ps), nat.ptr(src), B, N, float(p), int(seed), nat.ptr(det), nat.ptr(tape),
-                                                     tape.numel(), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
-        ctx.save_for_backward(src, tape, *params)
-        ctx.cfg, ctx.p, ctx.seed, ctx.ws = cfg, float(p), int(seed), ws
-        return det
-
-    @staticmethod
-    def backward(ctx, d_det):
-        L = nat.lib()
-        src, tape, *params = ctx.saved_tensors
-        cfg = ctx.cfg
-        B, N, _ = src.shape
-        d_det = d_det.contiguous().float()
-        with torch.cuda.device(src.device):
-            grads = [torch.zeros_like(t) for t in params]
-            d_src = torch.empty_like(src)
-            ps, k1 = _dense_struct(params, cfg.dec_layers)
-            gs, k2 = _dense_struct(grads, cfg.dec_layers)
-            _check(L.dod_dense_decoder_train_backward(C.byref(cfg), C.byref(ps), nat.ptr(src), B, N, ctx.p, ctx.seed, nat.ptr(d_det), nat.ptr(tape),
-                                                      tape.numel(), C.byref(gs), nat.ptr(d_src), nat.ptr(ctx.ws), ctx.ws.numel(), nat.stream_ptr()))
-        return (d_src, None, None, None, *grads)
+_DENSE = _Step("dense_decoder", _dense_struct, null_d_memory=False)
 
 
 def dense_decoder_train(m, src, seed=None):
     """DETRDecoder.forward (use_deformable=False) in train() mode -> packed detections [B, Q, C+4] with the autograd edge to the native backward"""
     cfg = make_config(m._bb_cfg, m._dc_cfg, "fp32")
-    if seed is None:
-        _seed_counter[0] += 1
-        seed = (int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) << 20) ^ _seed_counter[0]
-    return _DenseDecoderTrain.apply(src, cfg, dense_dropout_rate(m), seed, *_dense_param_list(m))
+    return _DecoderStep.apply(src, _DENSE, cfg, dense_dropout_rate(m), _draw_seed() if seed is None else seed, *_dense_param_list(m))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -512,7 +512,7 @@ int dod_backbone_tail_train_backward(const dod_config* cfg, const dod_bb_tail_pa
                                      size_t workspace_bytes, void* stream);
 
 /* ---- training-step operators: the adjoint kernels of the three steps above, one at a time ---------------------------------
- * What dod_decoder_train_*, dod_dense_decoder_train_* and dod_backbone_tail_train_* are made of (dec_train.hip, attn_f32m.hip), each
+ * What dod_decoder_train_*, dod_dense_decoder_train_* and dod_backbone_tail_train_* are made of (train_ops.hip, attn_f32m.hip), each
  * behind a thin entry that validates its arguments and calls the launcher the step calls -- for parity tests at shapes the steps never
  * run.  Stateless; every pointer is a caller-owned fp32 DEVICE buffer; enqueued on `stream`, no sync.  The "deterministic" test
  * option / DINODET_DETERMINISTIC selects the ordered reductions exactly as in the steps (that mode keeps a library-owned partial-sum

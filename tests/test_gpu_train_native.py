@@ -103,7 +103,7 @@ def test_native_decoder_backward_matches_composite_autograd(case):
 
 @pytest.mark.parametrize("case", [CASES[1], CASES[2], CASES[4]], ids=lambda c: f"Dd{c[0]}_Q{c[2]}_N{c[8]}")
 def test_deterministic_mode_is_bit_reproducible_and_agrees_with_the_fast_step(case):
-    """DINODET_DETERMINISTIC=1 / test option "deterministic" (dec_train.hip det_mode): every reduction the fast training step merges with
+    """DINODET_DETERMINISTIC=1 / test option "deterministic" (train_ops.hip det_mode): every reduction the fast training step merges with
     fp32 atomics -- K-split gradient products, bias sums, LayerNorm gradients, the deformable sampling adjoint's scatter and its shared
     reference-logit columns -- runs in a fixed order.  Three runs of the same step give bit-identical gradients; the fast step (whose
     runs agree with each other to ~1e-6) agrees with them to 1e-5."""
@@ -330,7 +330,7 @@ _F64_YARD = {}     # distance of PyTorch-ROCm's own fp32 autograd (all blocks in
 def test_train_step_gradients_match_the_reference_backward(name, native):
     """G9 (tests/golden/make_goldens.py::g9_gradients): what the REFERENCE's own `loss.backward()` (train.py:1101) leaves in .grad of
     every trainable parameter -- decoder + heads through the tied deformable layers, projection, LoRA A / B of the last two blocks
-    through the frozen base -- dropout 0, fixed linear loss.  The native HIP step (dec_train.hip) and, beside it, the PyTorch-ROCm
+    through the frozen base -- dropout 0, fixed linear loss.  The native HIP step (dec_train.hip, tail_train.hip) and, beside it, the PyTorch-ROCm
     composite on the native frozen prefix are held to those gradients directly: per tensor a strided probe and the L2 / abs-sum of
     the whole gradient."""
     from tests import gpu_util as G

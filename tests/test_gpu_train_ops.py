@@ -1,4 +1,4 @@
-"""`-m gpu`: the training step's adjoint kernels (dec_train.hip, the second half of attn_f32m.hip), one at a time through their
+"""`-m gpu`: the training step's adjoint kernels (train_ops.hip, the second half of attn_f32m.hip), one at a time through their
 operator entry points (include/dinodet.h "training-step operators"), against the same operation in float64 on the CPU: plain torch
 ops under autograd on the float32-rounded inputs.
 
@@ -97,7 +97,7 @@ class _Mode:
 
 
 def _u01(key, idx):
-    """dec_train.hip u01(key, idx) in numpy uint64: the splitmix64 finaliser of key + idx * golden, top 24 bits as a float in [0, 1)"""
+    """train_ops.hip u01(key, idx) in numpy uint64: the splitmix64 finaliser of key + idx * golden, top 24 bits as a float in [0, 1)"""
     idx = np.asarray(idx, dtype=np.uint64)
     with np.errstate(over="ignore"):
         z = np.uint64(key) + idx * np.uint64(0x9E3779B97F4A7C15)
@@ -151,7 +151,7 @@ def test_layernorm_bwd(G, rows, D):
     """ln_bwd_kernel<16> up to D = 1024, <32> above; more rows than the 8 192 waves of the largest grid (the stride loop), more than the
     256 workgroups of the deterministic grid; dgamma and dbeta on their own normalisation (in the backbone tail they go to a dump).
     From 512 workgroups (2 048 rows) up the fast mode merges the workgroups' partials through 16 interleaved accumulators (ln_bwd in
-    dec_train.hip): one float atomic per column and workgroup straight into dgamma / dbeta is a chain of up to 2 048 roundings at the
+    train_ops.hip): one float atomic per column and workgroup straight into dgamma / dbeta is a chain of up to 2 048 roundings at the
     size of the running sum, whose order-dependent random walk reaches the 2e-6 floor at (9000, 192)."""
     x = 2.0 * _n(f"ln.x.{rows}.{D}", (rows, D)) + 0.5
     g = 1.0 + 0.1 * _n(f"ln.g.{D}", (D,))

@@ -91,6 +91,68 @@ def test_decoder_train_entry_points_validate_arguments(lib):
     assert rc == 1 and b"null" in lib.dod_decoder_train_last_error()
 
 
+def _layout_cases():
+    """(name, tape_bytes query, workspace_bytes query, arguments, test option to set around the call or None) of the three training steps"""
+    from dinov2_od_amd.config import BackboneConfig, DecoderConfig
+    bb0 = cases.cfg1(25)[0]
+    out = []
+
+    def dec(deform, Dd, Hd, Q, layers, F, Cn, P, B, N):
+        dc = DecoderConfig(num_queries=Q, hidden_dim=Dd, nheads=Hd, num_layers=layers, num_classes=Cn, dim_feedforward=F, n_points=P, use_deformable=deform)
+        step = "decoder" if deform else "dense_decoder"
+        out.append((f"{step}-Dd{Dd}-Q{Q}-P{P}-B{B}-N{N}", f"dod_{step}_train_tape_bytes", f"dod_{step}_train_workspace_bytes", (make_config(bb0, dc, "fp32"), B, N), None))
+    dec(True, 128, 4, 7, 2, 256, 11, 2, 2, 26)            # CASES[0] of test_gpu_train_native.py
+    dec(True, 192, 2, 5, 2, 256, 11, 4, 2, 1370)          # CASES[2]: 4 points, head_dim 96
+    dec(True, 256, 4, 25, 2, 512, 91, 2, 2, 257)          # CASES[3]
+    dec(True, 128, 4, 7, 2, 256, 11, 9, 2, 26)            # not taken: 9 sampling points
+    dec(False, 128, 4, 7, 2, 256, 11, 2, 2, 17)           # DENSE_CASES[0]
+    dec(False, 256, 4, 25, 2, 512, 91, 2, 2, 257)         # DENSE_CASES[3]: N > Q, the cross-attention sizes the score scratch
+    dec(False, 256, 4, 25, 2, 512, 91, 2, 2, 9)           # N < Q: the self-attention does
+    dec(False, 128, 4, 7, 2, 256, 11, 2, 2, 1409)         # not taken: more than 1 408 memory tokens
+
+    def tail(name, flash, B=2, N=257, nblocks=2, **kw):
+        cfg = make_config(BackboneConfig(**kw), DecoderConfig(), "fp32")
+        out.append((f"tail-{name}-flash{flash}", "dod_backbone_tail_tape_bytes", "dod_backbone_tail_workspace_bytes", (cfg, B, N, nblocks), flash))
+    tail("vits", 1, hidden=384, heads=6, lora_r=2, target_dim=256)      # ViT-S at 224x224, flash attention adjoint: no score scratch
+    tail("vits", 0, hidden=384, heads=6, lora_r=2, target_dim=256)      # the batched-GEMM adjoint
+    tail("vitg", -1, hidden=1536, heads=24, swiglu=True, lora_r=2)      # SwiGLU, the shipped rule
+    tail("vits-r65", -1, hidden=384, heads=6, lora_r=65)                # not taken: LoRA rank past 64
+    return out
+
+
+# (tape bytes, workspace bytes) as built from commit fafa2de -- the last one with all three schedules in one dec_train.hip
+_LAYOUT_PARENT = {
+    "decoder-Dd128-Q7-P2-B2-N26": (227840, 151296),
+    "decoder-Dd192-Q5-P4-B2-N1370": (2308352, 2247168),
+    "decoder-Dd256-Q25-P2-B2-N257": (1946880, 1276160),
+    "decoder-Dd128-Q7-P9-B2-N26": (0, 0),
+    "dense_decoder-Dd128-Q7-P2-B2-N17": (281600, 158720),
+    "dense_decoder-Dd256-Q25-P2-B2-N257": (3617024, 2687744),
+    "dense_decoder-Dd256-Q25-P2-B2-N9": (1585408, 792832),
+    "dense_decoder-Dd128-Q7-P2-B2-N1409": (0, 0),
+    "tail-vits-flash1": (41058048, 7937024),
+    "tail-vits-flash0": (41058048, 14351872),
+    "tail-vitg-flash-1": (334099712, 70003200),
+    "tail-vits-r65-flash-1": (0, 0),
+}
+
+
+def test_training_tape_and_workspace_layouts_are_pinned(lib):
+    """*_tape_bytes / *_workspace_bytes of the three training steps return what they returned before the schedules were split over
+    dec_train.hip / tail_train.hip and their carve functions moved onto one carver: same buffers, same order, same 256-byte slots.  An
+    unsupported configuration still reports 0 from both."""
+    got = {}
+    for name, ftape, fws, (cfg, *dims), flash in _layout_cases():
+        if flash is not None:
+            assert lib.dod_test_set_option(b"attn_bwd_flash", flash) == 0
+        try:
+            got[name] = (getattr(lib, ftape)(C.byref(cfg), *dims), getattr(lib, fws)(C.byref(cfg), *dims))
+        finally:
+            lib.dod_test_set_option(b"attn_bwd_flash", -1)
+    assert got == _LAYOUT_PARENT
+    assert sum(v == (0, 0) for v in got.values()) == 3 and all(a > 0 and b > 0 for a, b in got.values() if (a, b) != (0, 0))
+
+
 def test_training_operators_validate_arguments(lib):
     """dod_op_layernorm_bwd ... dod_op_colsum_add: a null pointer or a shape past a documented limit is DOD_ERR_INVALID before any
     launch (no GPU here: a launch would be DOD_ERR_HIP), a short workspace DOD_ERR_STATE; the workspace queries return 0 for the same
