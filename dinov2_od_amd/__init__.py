@@ -11,4 +11,7 @@ def __getattr__(name):
     if name in ("DINOv2ObjectDetector", "DINOv2Backbone", "DETRDecoder"):
         from . import models
         return getattr(models, name)
+    if name == "optim":      # dinov2_od_amd.optim.Adam / clip_grad_norm_: the optimizer step on the HIP kernels
+        import importlib
+        return importlib.import_module(".optim", __name__)
     raise AttributeError(name)

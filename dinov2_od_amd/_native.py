@@ -73,6 +73,12 @@ class DodBbTailParams(C.Structure):
                 ("lnf_w", C.c_void_p), ("lnf_b", C.c_void_p), ("proj_w", C.c_void_p), ("proj_b", C.c_void_p)]
 
 
+class DodOptimTensor(C.Structure):
+    """struct dod_optim_tensor (include/dinodet.h): one parameter of the optimizer step"""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64),
+                ("step_size", C.c_float), ("bc2_sqrt", C.c_float)]
+
+
 class DodLnFold(C.Structure):
     """struct dod_ln_fold (include/dinodet.h): the folded-LayerNorm legs of dod_op_linear_ln"""
     _fields_ = [("stats", C.c_void_p), ("csum", C.c_void_p), ("op_out", C.c_void_p), ("part", C.c_void_p), ("shift", C.c_void_p),
@@ -172,6 +178,10 @@ SYMBOLS = {
     "dod_op_lora_grads": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _F, _P, _P, _P, _SZ, _P]),
     "dod_op_train_pointwise": (_I, [_I, _P, _P, _P, _SZ, _I, _F, C.c_uint64, _P]),
     "dod_op_colsum_add": (_I, [_P, _I, _I, _I, _P, _P]),
+    "dod_optim_workspace_bytes": (_SZ, [_I, _I64]),
+    "dod_optim_clip_grad_norm": (_I, [_P, _I, _F, _P, _P, _SZ, _P]),
+    "dod_optim_adam_step": (_I, [_P, _I, C.c_double, C.c_double, _F, C.c_double, _F, _P, _P, _SZ, _P]),
+    "dod_optim_last_error": (C.c_char_p, []),
     "dod_reserve_gemm_scratch": (_I, [C.c_size_t]),
     "dod_test_set_option": (_I, [C.c_char_p, _I]),
     "dod_test_counter": (C.c_long, [C.c_char_p]),

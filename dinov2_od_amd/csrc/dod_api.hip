@@ -54,6 +54,10 @@ long dod_test_counter(const char* name) {
   if (name && !strcmp(name, "tail_splits")) return gemm_tail_split_count();
   if (name && !strcmp(name, "rem_cuts")) return gemm_rem_cut_count();
   if (name && !strcmp(name, "f32_ksplits")) return gemm_f32_ksplit_count();
+  if (name && !strcmp(name, "optim_launches")) return optim_launch_count();
+  if (name && !strcmp(name, "optim_chunk_elems")) return optim_constant(0);
+  if (name && !strcmp(name, "optim_table_tensors")) return optim_constant(1);
+  if (name && !strcmp(name, "optim_norm_table_tensors")) return optim_constant(2);
   return -1;
 }
 

@@ -30,6 +30,8 @@ enum { DOD_OPT_TAILSPLIT = 0,         // GEMM wave-quantisation tail split: 0 of
        DOD_OPT_COUNT };
 int dod_option(int which);            // dod_api.hip; -1 when unset
 long gemm_tail_split_count();         // gemm_pp.hip: GEMM calls that took the tail-split path so far
+long optim_launch_count();            // optim.hip: launches of the optimizer entries so far
+long optim_constant(int which);       // optim.hip: 0 elements per workgroup, 1 / 2 tensors per update / norm launch
 long gemm_rem_cut_count();            // gemm_bf16.hip: GEMM calls whose short last round ran as a launch of its own
 
 #ifdef DINODET_TUNING

@@ -560,6 +560,40 @@ int dod_op_train_pointwise(int op, const float* a, const float* b, float* out, s
 /* dst[c] += sum_r src[r*ld + c], c < cols (the bias gradient) */
 int dod_op_colsum_add(const float* src, int ld, int rows, int cols, float* dst, void* stream);
 
+/* ---- optimizer step on device: gradient-norm clip + Adam (train.py:1000-1004, 1101-1110 of the reference) ----------------
+ * torch.nn.utils.clip_grad_norm_ (2-norm) followed by torch.optim.Adam (L2 weight_decay, no amsgrad) over a list of dense
+ * fp32 tensors, in two kinds of launch (csrc/optim.hip): the gradients' sum of squares, accumulated in
+ * double, one partial per workgroup; then the update, in which every workgroup adds the partials in a fixed order, forms
+ *   total_norm = (float)sqrt(sum),  coef = min(1, max_norm / (sqrt(sum) + 1e-6))          (a NaN norm gives a NaN coef)
+ * and updates its chunk once:
+ *   g = coef * g_raw + weight_decay * p;  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g g;
+ *   p -= step_size * m / (sqrt(v) / bc2_sqrt + eps)
+ * with step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) formed by the caller in double PER TENSOR (a parameter
+ * whose gradient was None on some step has a smaller t).  g, m and v are evaluated in double and rounded once when stored.
+ * beta1 / beta2 / weight_decay are doubles: 1 - (float)0.999 is 1.3e-5 away from 0.001, 36 times the bound on v by itself, and where
+ * coef * g_raw and weight_decay * p cancel, a rounded weight_decay would leave g with no correct digit.
+ * The tensor descriptors travel in the kernel arguments: a list longer than one argument table (64 tensors for the update, 128
+ * for the norm) takes more launches; tensors with n = 0 are skipped.  16-byte accesses where all pointers of a tensor are
+ * 16-byte aligned, 4-byte ones otherwise and for the n mod 4 tail; nothing past n is read or written.  No atomics: two runs of
+ * the same input give the same bits.  Everything is enqueued on `stream`; no synchronisation, no allocation.
+ *   dod_optim_clip_grad_norm  scales every g in place (only g and n of a descriptor are read) and stores total_norm; gradients
+ *                             keep their bits when the norm is below max_norm
+ *   dod_optim_adam_step       max_norm > 0: clip and update fused, the clipped gradient is NOT written back, total_norm is stored.
+ *                             max_norm <= 0: no clip, no norm launch, total_norm_dev and ws are not touched (may be NULL)
+ *   workspace                 dod_optim_workspace_bytes(n_tensors, total elements) bytes, monotone in both (0 for a negative one)
+ * n_tensors == 0 (or no elements at all) succeeds and stores total_norm = 0.  DOD_ERR_INVALID, before any HIP call and with a
+ * message behind dod_optim_last_error() (per thread): n_tensors < 0, a NULL list, a negative n, a NULL pointer of a tensor with
+ * n > 0, NULL total_norm_dev, a NULL or short workspace, betas outside [0, 1), negative eps / weight_decay.
+ * dod_test_counter("optim_launches") counts the launches of both entries; "optim_chunk_elems" / "optim_table_tensors" /
+ * "optim_norm_table_tensors" report the elements per workgroup and the tensors per update / norm launch. */
+typedef struct dod_optim_tensor { float* p; float* g; float* m; float* v; int64_t n; float step_size; float bc2_sqrt; } dod_optim_tensor;
+size_t dod_optim_workspace_bytes(int n_tensors, int64_t total_elems);
+int dod_optim_clip_grad_norm(const dod_optim_tensor* t, int n_tensors, float max_norm, float* total_norm_dev, void* ws, size_t ws_bytes,
+                             void* stream);
+int dod_optim_adam_step(const dod_optim_tensor* t, int n_tensors, double beta1, double beta2, float eps, double weight_decay, float max_norm,
+                        float* total_norm_dev, void* ws, size_t ws_bytes, void* stream);
+const char* dod_optim_last_error(void);
+
 /* Scratch of the GEMMs' wave-quantisation tail split (K-split partial slabs; gemm_pp.hip) and of the fp32 GEMM's K split (gemm_f32.hip, fixed size).  dod_finalize_weights reserves 64 MiB on the
  * current device; operator-level callers (tests, tools) reserve it themselves.  Never allocated inside a forward / stream capture. */
 int dod_reserve_gemm_scratch(size_t bytes);
@@ -588,7 +622,7 @@ const char* dod_version(void);
  * the tests use, the folded-LayerNorm operators arrived; revision 5: the dod_set_criterion_* entry points; revision 6: dod_match_assign*).
  * New entry points alone change no signature and no layout: dod_coco_eval_* and dod_op_sort_pairs_* joined revision 6, and a caller that
  * needs them resolves them by name (the Python binding fails at load when one is missing).  The training-step operators
- * (dod_op_layernorm_bwd ... dod_op_colsum_add) joined revision 6 the same way.
+ * (dod_op_layernorm_bwd ... dod_op_colsum_add) joined revision 6 the same way.  So did the optimizer step (dod_optim_*).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);
