@@ -27,12 +27,14 @@ enum { DOD_OPT_TAILSPLIT = 0,         // GEMM wave-quantisation tail split: 0 of
        DOD_OPT_DETERMINISTIC,         // 1 = ordered reductions instead of fp32 atomics in the training step's weight gradients
        DOD_OPT_F32_KSPLIT,            // fp32 GEMM K split across workgroups (gemm_f32.hip): 0 = never, 1 = also for the operator dod_op_linear
        DOD_OPT_ATTN_BWD_FLASH,        // backbone-tail attention adjoint (tail_train.hip tail_flash_bwd): 0 = never the flash form, 1 = whenever head_dim is 64
+       DOD_OPT_EPI_REGMATH,           // 16-wave bf16 GEMM, plain bf16 rows (gemm_x3.hip): 0 = the LDS-staged epilogue, 1 = epilogue math on the accumulators (shipped)
        DOD_OPT_COUNT };
 int dod_option(int which);            // dod_api.hip; -1 when unset
 long gemm_tail_split_count();         // gemm_pp.hip: GEMM calls that took the tail-split path so far
 long optim_launch_count();            // optim.hip: launches of the optimizer entries so far
 long optim_constant(int which);       // optim.hip: 0 elements per workgroup, 1 / 2 tensors per update / norm launch
 long gemm_rem_cut_count();            // gemm_bf16.hip: GEMM calls whose short last round ran as a launch of its own
+long gemm_epi_regmath_count();        // gemm_x3.hip: launches of the 16-wave bf16 GEMM that took the register epilogue
 
 #ifdef DINODET_TUNING
 #define DOD_TUNE_ENV(name) getenv(name)

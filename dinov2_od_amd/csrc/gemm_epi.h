@@ -342,7 +342,7 @@ __device__ __forceinline__ void drain_tile(const char* sm, int pitch, const Gemm
 // bf16 outputs without residual / row remap (QKV, fc1; plain or pair layout): EIGHT columns per lane -- one 16-byte store per lane
 // and row instead of two 8-byte ones: the store tail of a tile is bound by the number of store instructions, not by their bytes
 // (guide T21), and a workgroup per CU has nothing else to overlap it with.
-__device__ __forceinline__ bool drain8_ok(const GemmEpi& e, int N) {
+__host__ __device__ __forceinline__ bool drain8_ok(const GemmEpi& e, int N) {
   return e.out_bf16 && e.out_split <= 0 && !e.resid && e.rows_per_img == 0 && !e.a_scale && (!e.a_bs || e.w_bs) && !e.out_bs && (N & 7) == 0 && (e.ldc & 7) == 0 &&
          (e.out_split == 0 || ((-e.out_split) & 7) == 0);
 }
@@ -438,4 +438,43 @@ __device__ __forceinline__ void drain_tile_bf16x8(const char* sm, int pitch, con
       *reinterpret_cast<uint4*>(o - e.out_split) = lo;
     }
   }
+}
+
+// ---- the same rows drained from REGISTERS (gemm_x3.hip, REGM): plain bf16 rows (drain8_ok, no pair / H2 / SwiGLU form, no producer) do the
+// elementwise math on the accumulator quads -- it does not care which lane does it -- and cross the LDS once, as bf16, for the whole-row stores.
+inline bool epi_regmath_ok(const GemmEpi& e, int N) {
+  return drain8_ok(e, N) && e.out_split == 0 && !e.out_h2 && !e.glu && !e.ln_part && (!e.ln_part_in || (e.ln_npart >= 1 && e.ln_npart <= 8)) &&
+         (e.act == ACT_NONE || e.act == ACT_RELU || e.act == ACT_GELU);
+}
+// One accumulator quad through the arithmetic of drain_tile_bf16x8, expression for expression (the outputs are bit-identical): t = -mean rstd,
+// rs = rstd of the quad's row; c = the column sums (folded) or the LayerScale, b = the bias.
+template <int LN>
+__device__ __forceinline__ uint2 epi_quad_bf16(float4 v, const float4& c, const float4& b, float t1, float rs1, int act) {
+  if (LN == LN_CONS) {
+    const f32x2_t t = (f32x2_t)(t1), rs = (f32x2_t)(rs1);
+#define LN_PAIR_(va, vb, ca, cb, ba, bb)                                                                         \
+      { const f32x2_t c_ = {ca, cb}, b_ = {ba, bb}, a_ = {va, vb};                                                \
+        const f32x2_t o_ = __builtin_elementwise_fma(a_, rs, __builtin_elementwise_fma(t, c_, b_));               \
+        va = o_.x; vb = o_.y; }
+    LN_PAIR_(v.x, v.y, c.x, c.y, b.x, b.y) LN_PAIR_(v.z, v.w, c.z, c.w, b.z, b.w)
+#undef LN_PAIR_
+  } else {
+    v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
+  }
+  if (act == ACT_GELU) {
+    gelu_fast4(v);
+  } else if (act == ACT_RELU) {
+    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+  }
+  if (LN != LN_CONS) { v.x *= c.x; v.y *= c.y; v.z *= c.z; v.w *= c.w; }
+  return make_uint2(pack2bf(v.x, v.y), pack2bf(v.z, v.w));
+}
+// The staged bf16 tile: 512-byte rows, 8-byte slot s of row r at slot s ^ (r & 15).  A ds_write_b64 is served in four groups of 16 lanes --
+// here 16 consecutive rows at ONE column quad -- over 32 banks: the XOR puts them on 16 different slots (a row pad of 16 B leaves rows r and
+// r + 8 on one bank pair); the 16-byte chunk k of a row is chunk k ^ ((r >> 1) & 7), its halves swapped in odd rows, and a row's 32 readers stay
+// on 32 different chunks.
+__device__ __forceinline__ int epi_tile_w8(int row, int col) { return row * 512 + (((col >> 2) ^ (row & 15)) << 3); }
+__device__ __forceinline__ uint4 epi_tile_r16(const char* sm, int row, int c8) {
+  const uint4 q = *reinterpret_cast<const uint4*>(sm + row * 512 + ((c8 ^ ((row >> 1) & 7)) << 4));
+  return (row & 1) ? make_uint4(q.z, q.w, q.x, q.y) : q;
 }

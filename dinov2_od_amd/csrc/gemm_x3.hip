@@ -13,6 +13,7 @@
 // epilogue (gemm_epi.h), XCD-aware grouped tile order.
 #include "dod_common.h"
 #include "gemm_epi.h"
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 
@@ -25,9 +26,67 @@
 
 __device__ __forceinline__ int x3_swz(int row, int chunk) { return chunk ^ (((row >> 3) & 1) << 1); }   // 16x16x32 lane map, 64-B rows
 
+#define X3_PAR (X3_SLOTS * X3_STAGE)      // REGM: (mean, rstd)[256] | bias[256] | c or LayerScale[256] behind the ring
+
+// The register epilogue (REGM, below).  Lane (l15, l4) of wave (wm, wn) holds row wm*64 + i*16 + l15, columns wn*64 + j*16 + 4*l4 .. +3 in
+// acc[i][j]: math there, bf16 quads into the tile (the ring is free behind the barrier), then every wave instruction copies two whole 512-byte
+// rows out -- rows and 16-byte stores as in drain_tile_bf16x8.  Two halves: rows 0..31 of every 64 (i = 0, 1) leave while i = 2, 3 are computed
+// into the other rows, so the second half's math and GELU run under the first half's stores; the barriers wait for LDS operations only, never
+// for a store.  (The whole tile behind one barrier pair measured 1-3 % slower: profiles/epi_regmath_ab.txt.)
+template <int LN, int ACT>
+__device__ __forceinline__ void x3_epi_regs(char* smem, const f32x4 (&acc)[4][4], const GemmEpi& e, int M, int N, int m0, int n0, int tid) {
+  const int lane = tid & 63, wid = tid >> 6, wm = wid >> 2, wn = wid & 3, l15 = lane & 15, l4 = lane >> 4;
+  const int c8 = tid & 31, nd = n0 + 8 * c8;
+#define X3_LDS_SYNC asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory");
+#define X3_MATH(I0)                                                                                                    \
+  {                                                                                                                    \
+    float tt[2], rr[2];                                                                                                \
+    _Pragma("unroll") for (int ii = 0; ii < 2; ++ii) {                                                                 \
+      float2 st = make_float2(0.f, 0.f);                                                                               \
+      if (LN == LN_CONS) st = *reinterpret_cast<const float2*>(smem + X3_PAR + (wm * 64 + ((I0) + ii) * 16 + l15) * 8); \
+      tt[ii] = -st.x * st.y; rr[ii] = st.y;                                                                            \
+    }                                                                                                                  \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                                    \
+      const int col = wn * 64 + j * 16 + 4 * l4;                                                                       \
+      const float4 b4 = *reinterpret_cast<const float4*>(smem + X3_PAR + 2048 + col * 4);                              \
+      const float4 c4 = *reinterpret_cast<const float4*>(smem + X3_PAR + 3072 + col * 4);                              \
+      _Pragma("unroll") for (int ii = 0; ii < 2; ++ii) {                                                               \
+        const f32x4 a = acc[(I0) + ii][j];                                                                             \
+        const uint2 o = epi_quad_bf16<LN>(make_float4(a[0], a[1], a[2], a[3]), c4, b4, tt[ii], rr[ii], ACT);           \
+        *reinterpret_cast<uint2*>(smem + epi_tile_w8(wm * 64 + ((I0) + ii) * 16 + l15, col)) = o;                      \
+      }                                                                                                                \
+    }                                                                                                                  \
+  }
+#define X3_COPY(P)      /* the four LDS reads first: one wait, then the guarded stores */                               \
+  {                                                                                                                    \
+    uint4 q[4];                                                                                                        \
+    _Pragma("unroll") for (int it = 0; it < 4; ++it) q[it] = epi_tile_r16(smem, it * 64 + (P) * 32 + (tid >> 5), c8);  \
+    _Pragma("unroll") for (int it = 0; it < 4; ++it) {                                                                 \
+      const int row = it * 64 + (P) * 32 + (tid >> 5);                                                                 \
+      if (nd < N && m0 + row < M) *reinterpret_cast<uint4*>(e.out_bf16 + (size_t)(m0 + row) * e.ldc + nd) = q[it];     \
+    }                                                                                                                  \
+  }
+  X3_LDS_SYNC
+  X3_MATH(0)
+  X3_LDS_SYNC
+  if (LN == LN_CONS && n0 == 0 && tid < 256 && m0 + tid < M && e.ln_part_in && e.ln_stats_out)      // the next producer's shift, as stage_row_stats publishes it
+    e.ln_stats_out[m0 + tid] = *reinterpret_cast<const float2*>(smem + X3_PAR + tid * 8);
+  X3_COPY(0)
+  X3_MATH(2)
+  X3_LDS_SYNC
+  X3_COPY(1)
+#undef X3_MATH
+#undef X3_COPY
+#undef X3_LDS_SYNC
+}
+
 // PLAIN = true: the same structure as an ordinary bf16 GEMM with BK = 64 -- the second plane of each operand holds k 32..63
 // of the K-tile instead of the lo halves, two products per K-tile (experiment / DINODET_GEMM_TILE=x).
-template <bool PLAIN, int LN>
+//
+// REGM (plain bf16 output rows, epi_regmath_ok): the epilogue math runs on the accumulators and the tile crosses the LDS once, as bf16
+// (x3_epi_regs above) instead of the shared LDS-staged epilogue: the row statistics, bias and column sums are fetched at kernel entry -- their
+// latency lies under the first K-tile's -- finished once and kept in 4 KiB behind the ring.
+template <bool PLAIN, int LN, bool REGM = false>
 __global__ __launch_bounds__(1024) void gemm_x3_256x256_kernel(const bf16_t* __restrict__ A2, int lda,
                                                                const bf16_t* __restrict__ W2, int ldw, int M, int N,
                                                                int K, GemmEpi e, int GM) {
@@ -73,40 +132,106 @@ __global__ __launch_bounds__(1024) void gemm_x3_256x256_kernel(const bf16_t* __r
   constexpr int KSTEP = PLAIN ? 2 * X3K : X3K;
   const int nk = K / KSTEP;
   const int l15 = lane & 15, l4 = lane >> 4;
+  // REGM: thread t < 256 fetches row m0 + t's statistics and column n0 + t's parameters BEFORE the first LDS-DMA is issued and uses them
+  // behind the wait for that tile (beside a pending LDS-DMA the compiler waits vmcnt(0) at the first use of an ordinary load): no wait of
+  // theirs lands in the K loop.  Addresses are clamped, not predicated, so that no load sits behind a branch of its own.
+  unsigned long long st_r = 0, pg_r[8];      // float2 pairs, kept whole (8-byte registers) until they are used
+  float b_e = 0.f, c_e = 1.f;
+  if constexpr (REGM) {
+    if (tid < 256) {
+      const int nc = n0 + tid < N ? n0 + tid : N - 1;
+      const float* sc = LN == LN_CONS ? e.ln_c : e.scale;
+      if (e.bias) b_e = e.bias[nc];
+      if (sc) c_e = sc[nc];
+      if (LN == LN_CONS) {
+        const int mc = m0 + tid < M ? m0 + tid : M - 1;
+        st_r = reinterpret_cast<const unsigned long long*>(e.ln_stats)[mc];
+        // (without group sums: eight more loads of the row's pair -- a load behind a branch would be waited for at the join)
+        const unsigned long long* p = reinterpret_cast<const unsigned long long*>(e.ln_part_in ? e.ln_part_in + (size_t)mc * e.ln_npart : e.ln_stats + mc);
+        const int gl = e.ln_part_in ? e.ln_npart - 1 : 0;
+#pragma unroll
+        for (int g = 0; g < 8; ++g) pg_r[g] = p[g < gl ? g : gl];
+      }
+    }
+  }
   STAGE_X3(0, 0)
   int offA[4], offW[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) { const int row = wm * 64 + i * 16 + l15; offA[i] = row * 64 + x3_swz(row, l4) * 16; }
 #pragma unroll
   for (int j = 0; j < 4; ++j) { const int row = wn * 64 + j * 16 + l15; offW[j] = 2 * X3_PLANE + row * 64 + x3_swz(row, l4) * 16; }
-  for (int kt = 0; kt < nk; ++kt) {
+#define X3_KTILE(kt)                                                                                         \
+  {                                                                                                          \
+    if ((kt) + 1 < nk) STAGE_X3(((kt) + 1) & 1, ((kt) + 1) * KSTEP)                                          \
+    const char* st = smem + ((kt) & 1) * X3_STAGE;                                                           \
+    bf16x8 wh[4], wl[4];                                                                                     \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                          \
+      wh[j] = *reinterpret_cast<const bf16x8*>(st + offW[j]);                                                \
+      wl[j] = *reinterpret_cast<const bf16x8*>(st + offW[j] + X3_PLANE);                                     \
+    }                                                                                                        \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                          \
+      const bf16x8 ah = *reinterpret_cast<const bf16x8*>(st + offA[i]);                                      \
+      const bf16x8 al = *reinterpret_cast<const bf16x8*>(st + offA[i] + X3_PLANE);                           \
+      _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                        \
+        if (PLAIN) {                                                                                         \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], ah, acc[i][j], 0, 0, 0);   /* k 0..31 */  \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[j], al, acc[i][j], 0, 0, 0);   /* k 32..63 */ \
+        } else {                                                                                             \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[j], ah, acc[i][j], 0, 0, 0);   /* small terms first */ \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], al, acc[i][j], 0, 0, 0);                \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], ah, acc[i][j], 0, 0, 0);                \
+        }                                                                                                    \
+      }                                                                                                      \
+    }                                                                                                        \
+  }
+  int kt0 = 0;
+  if constexpr (REGM) {
+    // the first K-tile on its own: behind its wait the early loads have landed too, and their registers end here, in front of the loop
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (tid < 256) {
+      // (volatile: no use of a loaded value may move up in front of the wait above)
+      asm volatile("" : "+v"(b_e), "+v"(c_e), "+v"(st_r));
+      if (LN == LN_CONS) {
+#pragma unroll
+        for (int g = 0; g < 8; ++g) asm volatile("" : "+v"(pg_r[g]));
+      }
+      float2 st_e = make_float2(__uint_as_float((unsigned)st_r), __uint_as_float((unsigned)(st_r >> 32)));
+      if (n0 + tid >= N) { b_e = 0.f; c_e = 1.f; }
+      if (LN == LN_CONS) {
+        if (m0 + tid >= M) {
+          st_e = make_float2(0.f, 0.f);
+        } else if (e.ln_part_in) {      // as stage_row_stats finishes them
+          float S = 0.f, Q = 0.f;
+#pragma unroll
+          for (int g = 0; g < 8; ++g)
+            if (g < e.ln_npart) { S += __uint_as_float((unsigned)pg_r[g]); Q += __uint_as_float((unsigned)(pg_r[g] >> 32)); }
+          const float dm = S / (float)K;
+          st_e = make_float2(st_e.x + dm, 1.0f / sqrtf(fmaxf(Q / (float)K - dm * dm, 0.f) + e.ln_eps));
+        }
+        *reinterpret_cast<float2*>(smem + X3_PAR + tid * 8) = st_e;
+      }
+      *reinterpret_cast<float*>(smem + X3_PAR + 2048 + tid * 4) = b_e;
+      *reinterpret_cast<float*>(smem + X3_PAR + 3072 + tid * 4) = c_e;
+    }
+    asm volatile("" ::: "memory");
+    X3_KTILE(0)
+    kt0 = 1;
+  }
+  for (int kt = kt0; kt < nk; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // tile kt landed (the only one in flight)
     __builtin_amdgcn_s_barrier();                         // ... for all waves, and all waves are done with tile kt-1
     asm volatile("" ::: "memory");
-    if (kt + 1 < nk) STAGE_X3((kt + 1) & 1, (kt + 1) * KSTEP)
-    const char* st = smem + (kt & 1) * X3_STAGE;
-    bf16x8 wh[4], wl[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      wh[j] = *reinterpret_cast<const bf16x8*>(st + offW[j]);
-      wl[j] = *reinterpret_cast<const bf16x8*>(st + offW[j] + X3_PLANE);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const bf16x8 ah = *reinterpret_cast<const bf16x8*>(st + offA[i]);
-      const bf16x8 al = *reinterpret_cast<const bf16x8*>(st + offA[i] + X3_PLANE);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (PLAIN) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], ah, acc[i][j], 0, 0, 0);   // k 0..31
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[j], al, acc[i][j], 0, 0, 0);   // k 32..63
-        } else {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[j], ah, acc[i][j], 0, 0, 0);   // small terms first
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], al, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], ah, acc[i][j], 0, 0, 0);
-        }
-      }
-    }
+    X3_KTILE(kt)
+  }
+#undef X3_KTILE
+  if constexpr (REGM) {
+    // the activation chosen once, not per quad: straight-line math between the barriers
+    if (e.act == ACT_GELU) x3_epi_regs<LN, ACT_GELU>(smem, acc, e, M, N, m0, n0, tid);
+    else if (e.act == ACT_RELU) x3_epi_regs<LN, ACT_RELU>(smem, acc, e, M, N, m0, n0, tid);
+    else x3_epi_regs<LN, ACT_NONE>(smem, acc, e, M, N, m0, n0, tid);
+    return;
   }
   // epilogue: two passes of 128 tile rows through a 128 x 256 fp32 LDS tile (pitch +16 B)
   constexpr int PITCH = X3N * 4 + 16;
@@ -155,6 +280,7 @@ int gemm_tile_mode() {
 }
 
 static constexpr int LDSX3 = (128 * (X3N * 4 + 16)) > X3_SLOTS * X3_STAGE ? (128 * (X3N * 4 + 16)) : X3_SLOTS * X3_STAGE;
+static constexpr int LDSX3E = X3_PAR + 4096;      // REGM: the ring (then the bf16 tile) + the tile's parameters
 
 static void x3_attr() {      // > 64 KiB of dynamic LDS: once per device
   static bool attr_set[16] = {};
@@ -164,6 +290,9 @@ static void x3_attr() {      // > 64 KiB of dynamic LDS: once per device
 #define ATTR_(LN_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3_256x256_kernel<false, LN_>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSX3); \
                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3_256x256_kernel<true, LN_>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSX3);
     ATTR_(LN_NONE) ATTR_(LN_CONS) ATTR_(LN_PROD)
+#undef ATTR_
+#define ATTR_(LN_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3_256x256_kernel<true, LN_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSX3E);
+    ATTR_(LN_NONE) ATTR_(LN_CONS)
 #undef ATTR_
     attr_set[dev] = true;
   }
@@ -197,12 +326,24 @@ int launch_gemm_x3(const bf16_t* A2, int lda, const bf16_t* W2, int ldw, int M, 
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
+static std::atomic<long> g_epi_regmath{0};
+long gemm_epi_regmath_count() { return g_epi_regmath.load(); }
+
 // plain bf16 GEMM on the same structure (256x256x64, 16 waves, two 64-KiB slots): K % 64 == 0
 int launch_gemm_bf16_k64(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s) {
   if (M <= 0 || N <= 0 || K <= 0 || K % 64 != 0) return 2;
   x3_attr();
   const int gm = gemm_tile_mode();
   const int tiles = ((M + X3M - 1) / X3M) * ((N + X3N - 1) / X3N);
+  // plain bf16 rows (QKV, fc1 of the bf16 mode): the register epilogue.  Test option DOD_OPT_EPI_REGMATH, read once per launch: 0 = the
+  // LDS-staged epilogue.  A template parameter, so that neither form carries the other's registers
+  if (dod_option(DOD_OPT_EPI_REGMATH) != 0 && epi_regmath_ok(e, N)) {
+#define GO_(LN_) hipLaunchKernelGGL((gemm_x3_256x256_kernel<true, LN_, true>), dim3(tiles), dim3(1024), LDSX3E, s, A, lda, W, ldw, M, N, K, e, gm);
+    if (ln_mode_of(e) == LN_CONS) { GO_(LN_CONS) } else { GO_(LN_NONE) }
+#undef GO_
+    ++g_epi_regmath;
+    return hipGetLastError() == hipSuccess ? 0 : 3;
+  }
 #define GO_(LN_) hipLaunchKernelGGL((gemm_x3_256x256_kernel<true, LN_>), dim3(tiles), dim3(1024), LDSX3, s, A, lda, W, ldw, M, N, K, e, gm);
   LN_DISPATCH(e, GO_)
 #undef GO_

@@ -609,8 +609,11 @@ int dod_reserve_gemm_scratch(size_t bytes);
  *                      every mode but the strict fp32 one)
  *   "attn_bwd_flash"   backbone-tail attention adjoint: 0 = never the flash form, 1 = whenever head_dim is 64 (shipped: from 1 024 tokens up;
  *                      wins over DINODET_ATTN_BWD_FLASH).  Read when the tape and workspace are sized and in both passes: set it around a whole step
+ *   "epi_regmath"      16-wave bf16 GEMM with plain bf16 output rows (QKV, fc1 of the bf16 mode; gemm_x3.hip): 0 = the LDS-staged fp32 epilogue,
+ *                      1 = the epilogue math on the accumulators (shipped; bit-identical).  Read once per launch
  * dod_test_counter("tail_splits"): GEMM calls that took the tail-split path so far; "rem_cuts": GEMM calls whose short last round ran as a
- * launch of its own (gemm_bf16.hip); "f32_ksplits": fp32 GEMM launches that split K across workgroups (gemm_f32.hip); -1 for an unknown name.
+ * launch of its own (gemm_bf16.hip); "f32_ksplits": fp32 GEMM launches that split K across workgroups (gemm_f32.hip); "epi_regmath": launches
+ * of the 16-wave bf16 GEMM that took the register epilogue; -1 for an unknown name.
  * The in-kernel time stamps, the register-only MFMA probes and every tile / schedule override of the tuning rounds exist only in
  * -DDINODET_TUNING builds (include/dinodet_tuning.h); the release library exports none of them. */
 int dod_test_set_option(const char* name, int value);

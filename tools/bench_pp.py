@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """A/B of bf16 GEMM kernel variants on the four ViT-B block shapes, interleaved rounds in ONE process (GPU box only).
     python tools/bench_pp.py [--batch 64] [--variants default,p] [--rounds 5]
-A variant is a value of DINODET_GEMM_TILE ("default" = the shape heuristic).  Prints the median time per variant and the
+A variant is a value of DINODET_GEMM_TILE ("default" = the shape heuristic), or "e0" / "e1" (test option epi_regmath; these need no tuning
+build: DINODET_LIB=dinov2_od_amd/lib/libdinodet.so).  Prints the median time per variant and the
 max deviation of each variant's output from the first one's."""
 import argparse
 import os
@@ -15,6 +16,10 @@ from dinov2_od_amd import _native as nat
 
 
 def set_variant(v):
+    nat.lib().dod_test_set_option(b"epi_regmath", -1)
+    if v.startswith("e"):                      # "e0" / "e1": LDS-staged / register epilogue of the 16-wave kernel (test option epi_regmath)
+        nat.lib().dod_test_set_option(b"epi_regmath", int(v[1:]))
+        v = "default"
     os.environ.pop("DINODET_GEMM_STAGGER", None)
     os.environ.pop("DINODET_EPI_RB", None)
     if "#" in v:                               # "<tile>#<rb>": residual loads in flight per thread (512-thread kernels)
