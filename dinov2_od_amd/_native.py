@@ -157,6 +157,13 @@ SYMBOLS = {
     "dod_set_criterion_workspace_bytes": (_SZ, [_I, _I, _I]),
     "dod_set_criterion_forward": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _I, _I, _P, _P, _I, _P, _I, _P, _F, _F, _P, _P, _P, _SZ, _P]),
     "dod_set_criterion_backward": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _I, _I, _P, _P, _I, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P]),
+    "dod_set_criterion_layers_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "dod_set_criterion_layers_forward": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _F, _F, _P, _P, _P, _SZ, _P]),
+    "dod_set_criterion_layers_backward": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P]),
+    "dod_decoder_train_aux_tape_bytes": (_SZ, [C.POINTER(DodConfig), _I, _I]),
+    "dod_decoder_train_aux_workspace_bytes": (_SZ, [C.POINTER(DodConfig), _I, _I]),
+    "dod_decoder_train_aux_forward": (_I, [C.POINTER(DodConfig), _P, _P, _I, _I, _F, C.c_uint64, _P, _P, _SZ, _P, _SZ, _P]),
+    "dod_decoder_train_aux_backward": (_I, [C.POINTER(DodConfig), _P, _P, _I, _I, _F, C.c_uint64, _P, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "dod_decoder_train_tape_bytes": (_SZ, [C.POINTER(DodConfig), _I, _I]),
     "dod_decoder_train_workspace_bytes": (_SZ, [C.POINTER(DodConfig), _I, _I]),
     "dod_decoder_train_forward": (_I, [C.POINTER(DodConfig), _P, _P, _I, _I, _F, C.c_uint64, _P, _P, _SZ, _P, _SZ, _P]),

@@ -16,6 +16,9 @@
 // side; clamp(min=0) passes at 0; l1_loss: 0 where pred == target; (1 - p_t)**0 has no pow gradient).
 // The same row kernel serves FocalLoss (losses.py:9-68): match == NULL means "row r's target is labels[r]", pred_boxes ==
 // NULL skips the box terms, num_boxes == NULL normalises by 1, elem_loss / d_elem carry reduction='none'.
+// Layered form (deep supervision: `layers` decoder outputs against the same targets): rows r = (l*B + b)*Q + q, each layer has
+// its own ceil(B*Q / 16) workgroups, partials and finalize workgroup, so layer l's losses and gradients are bit-identical to
+// the single-layer call on that layer's slice; still two launches forward, one backward.
 #include "dod_common.h"
 #include "../../include/dinodet.h"
 
@@ -28,7 +31,8 @@ constexpr int kRowsPerWg = kWaves * kRowsPerWave;
 struct CritArgs {
   const float* logits; long long ls;           // row r's logits at logits + r * ls
   const float* boxes; long long bs;            // row r's (cx, cy, w, h) at boxes + r * bs, or NULL
-  int R, C, G;
+  int R, C, G;                                 // R = rows of ONE layer; layer l's rows are l * R + (0 .. R-1)
+  int wgl;                                     // workgroups per layer: a workgroup never straddles a layer
   const long long* labels;                     // [G]
   const float* gt;                             // [G, 4] cxcywh
   const int* match;                            // [R], or NULL = identity
@@ -36,8 +40,8 @@ struct CritArgs {
   float alpha, gamma;
 };
 
-__device__ __forceinline__ int crit_target(const CritArgs& a, int r) {
-  return a.match ? a.match[r] : r;
+__device__ __forceinline__ int crit_target(const CritArgs& a, long long r) {
+  return a.match ? a.match[r] : (int)r;
 }
 
 // class column of row r, -1 = background (no target, or a label outside [0, C))
@@ -139,16 +143,17 @@ __device__ __forceinline__ void giou_pair_grad(const float* p, const float* t, f
 
 __device__ __forceinline__ float l1_sign(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
 
-__global__ __launch_bounds__(256) void crit_forward_kernel(CritArgs a, float* __restrict__ part, int nwg,
-                                                           float* __restrict__ elem) {
+__global__ __launch_bounds__(256) void crit_forward_kernel(CritArgs a, float* __restrict__ part, float* __restrict__ elem) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float ce = 0.f, l1 = 0.f, gi = 0.f;
+  const int layer = blockIdx.x / a.wgl, lwg = blockIdx.x - layer * a.wgl;
   for (int k = 0; k < kRowsPerWave; ++k) {
-    const int r = blockIdx.x * kRowsPerWg + wave * kRowsPerWave + k;
-    if (r >= a.R) break;
+    const int rl = lwg * kRowsPerWg + wave * kRowsPerWave + k;
+    if (rl >= a.R) break;
+    const long long r = (long long)layer * a.R + rl;
     const int m = crit_target(a, r);
     const int tc = crit_class(a, m);
-    const float* x = a.logits + (long long)r * a.ls;
+    const float* x = a.logits + r * a.ls;
     for (int c = lane; c < a.C; c += DOD_WAVE) {
       const float l = focal_elem(x[c], c == tc, a.alpha, a.gamma);
       ce += l;
@@ -169,15 +174,17 @@ __global__ __launch_bounds__(256) void crit_forward_kernel(CritArgs a, float* __
     const int i = threadIdx.x;
     float s = red[i][0];
     for (int w = 1; w < kWaves; ++w) s += red[i][w];
-    part[(size_t)i * nwg + blockIdx.x] = s;
+    part[((size_t)layer * 3 + i) * a.wgl + lwg] = s;
   }
 }
 
-// one workgroup: losses[i] = (sum of the nwg partials of loss i, in a fixed order) / max(num_boxes, 1)
+// one workgroup per layer: losses[i] = (sum of the layer's nwg partials of loss i, in a fixed order) / max(num_boxes, 1)
 __global__ __launch_bounds__(256) void crit_finalize_kernel(const float* __restrict__ part, int nwg,
                                                             const float* __restrict__ num_boxes,
                                                             float* __restrict__ losses) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  part += (size_t)blockIdx.x * 3 * nwg;
+  losses += (size_t)blockIdx.x * 3;
   __shared__ float red[3][kWaves];
   for (int i = 0; i < 3; ++i) {
     float s = 0.f;
@@ -200,14 +207,17 @@ __global__ __launch_bounds__(256) void crit_backward_kernel(CritArgs a, const fl
                                                             float* __restrict__ d_logits, float* __restrict__ d_boxes) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float nb = crit_norm(a);
+  const int layer = blockIdx.x / a.wgl, lwg = blockIdx.x - layer * a.wgl;
+  if (d_losses) d_losses += layer * 3;
   const float gce = d_elem ? 0.f : d_losses[0] / nb;
   for (int k = 0; k < kRowsPerWave; ++k) {
-    const int r = blockIdx.x * kRowsPerWg + wave * kRowsPerWave + k;
-    if (r >= a.R) break;
+    const int rl = lwg * kRowsPerWg + wave * kRowsPerWave + k;
+    if (rl >= a.R) break;
+    const long long r = (long long)layer * a.R + rl;
     const int m = crit_target(a, r);
     const int tc = crit_class(a, m);
-    const float* x = a.logits + (long long)r * a.ls;
-    float* dx = d_logits + (long long)r * a.C;
+    const float* x = a.logits + r * a.ls;
+    float* dx = d_logits + r * a.C;
     for (int c = lane; c < a.C; c += DOD_WAVE) {
       const float up = d_elem ? d_elem[(long long)r * a.C + c] / nb : gce;
       dx[c] = up * focal_grad(x[c], c == tc, a.alpha, a.gamma);
@@ -231,19 +241,21 @@ int crit_nwg(int B, int Q) { return (int)(((long long)B * Q + kRowsPerWg - 1) / 
 
 // host-side shape / stride validation shared by forward and backward
 int crit_args(CritArgs& a, const float* pred_logits, long long logits_row_stride, const float* pred_boxes,
-              long long boxes_row_stride, int B, int Q, int C, const int64_t* labels, const float* gt_boxes, int G,
-              const int32_t* match, int M, const float* num_boxes, float alpha, float gamma) {
-  if (!pred_logits || B <= 0 || Q <= 0 || C <= 0 || G < 0) return DOD_ERR_INVALID;
-  if ((long long)B * Q > 0x7fffffffLL || (long long)B * Q * C > 0x7fffffffffffLL) return DOD_ERR_INVALID;
+              long long boxes_row_stride, int layers, int B, int Q, int C, const int64_t* labels, const float* gt_boxes, int G,
+              const int32_t* match, long long M, const float* num_boxes, float alpha, float gamma) {
+  if (!pred_logits || layers <= 0 || B <= 0 || Q <= 0 || C <= 0 || G < 0) return DOD_ERR_INVALID;
+  const long long rows = (long long)layers * B * Q;
+  if ((long long)B * Q > 0x7fffffffLL || rows > 0x7fffffffLL || rows * C > 0x7fffffffffffLL) return DOD_ERR_INVALID;
+  if ((long long)layers * crit_nwg(B, Q) > 0x7fffffffLL) return DOD_ERR_INVALID;
   if (logits_row_stride < C) return DOD_ERR_INVALID;
   if (pred_boxes && boxes_row_stride < 4) return DOD_ERR_INVALID;
   if (G > 0 && !labels) return DOD_ERR_INVALID;
   if (G > 0 && pred_boxes && !gt_boxes) return DOD_ERR_INVALID;
-  if (match ? M != B * Q : G != B * Q) return DOD_ERR_INVALID;   // without a table, row r's target is labels[r]
+  if (match ? M != rows : G != rows) return DOD_ERR_INVALID;     // without a table, row r's target is labels[r]
   if (!(gamma >= 0.f) || !(alpha == alpha)) return DOD_ERR_INVALID;
   a.logits = pred_logits; a.ls = logits_row_stride;
   a.boxes = pred_boxes; a.bs = boxes_row_stride;
-  a.R = B * Q; a.C = C; a.G = G;
+  a.R = B * Q; a.C = C; a.G = G; a.wgl = crit_nwg(B, Q);
   a.labels = (const long long*)labels; a.gt = gt_boxes; a.match = match; a.num_boxes = num_boxes;
   a.alpha = alpha; a.gamma = gamma;
   return DOD_OK;
@@ -251,28 +263,53 @@ int crit_args(CritArgs& a, const float* pred_logits, long long logits_row_stride
 
 }  // namespace
 
-extern "C" size_t dod_set_criterion_workspace_bytes(int B, int Q, int C) {
-  if (B <= 0 || Q <= 0 || C <= 0) return 0;
-  return (size_t)3 * crit_nwg(B, Q) * sizeof(float);
+extern "C" size_t dod_set_criterion_layers_workspace_bytes(int layers, int B, int Q, int C) {
+  if (layers <= 0 || B <= 0 || Q <= 0 || C <= 0) return 0;
+  return (size_t)3 * layers * crit_nwg(B, Q) * sizeof(float);
+}
+extern "C" size_t dod_set_criterion_workspace_bytes(int B, int Q, int C) { return dod_set_criterion_layers_workspace_bytes(1, B, Q, C); }
+
+extern "C" int dod_set_criterion_layers_forward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
+                                                int64_t boxes_row_stride, int layers, int B, int Q, int C, const int64_t* labels,
+                                                const float* gt_boxes, int G, const int32_t* match, int M,
+                                                const float* num_boxes, float alpha, float gamma, float* losses, float* elem_loss,
+                                                void* workspace, size_t workspace_bytes, void* stream) {
+  CritArgs a;
+  const int rc = crit_args(a, pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, layers, B, Q, C, labels, gt_boxes, G,
+                           match, M, num_boxes, alpha, gamma);
+  if (rc != DOD_OK) return rc;
+  if (!losses || !workspace) return DOD_ERR_INVALID;
+  if (workspace_bytes < dod_set_criterion_layers_workspace_bytes(layers, B, Q, C)) return DOD_ERR_STATE;
+  float* part = (float*)workspace;
+  hipLaunchKernelGGL(crit_forward_kernel, dim3((unsigned)(layers * a.wgl)), dim3(256), 0, (hipStream_t)stream, a, part, elem_loss);
+  hipLaunchKernelGGL(crit_finalize_kernel, dim3((unsigned)layers), dim3(256), 0, (hipStream_t)stream, (const float*)part, a.wgl,
+                     num_boxes, losses);
+  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
 }
 
+extern "C" int dod_set_criterion_layers_backward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
+                                                 int64_t boxes_row_stride, int layers, int B, int Q, int C, const int64_t* labels,
+                                                 const float* gt_boxes, int G, const int32_t* match, int M,
+                                                 const float* num_boxes, float alpha, float gamma, const float* d_losses,
+                                                 const float* d_elem, float* d_logits, float* d_boxes, void* stream) {
+  CritArgs a;
+  const int rc = crit_args(a, pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, layers, B, Q, C, labels, gt_boxes, G,
+                           match, M, num_boxes, alpha, gamma);
+  if (rc != DOD_OK) return rc;
+  if (!d_logits || (!d_losses && !d_elem) || (pred_boxes && d_boxes && !d_losses)) return DOD_ERR_INVALID;
+  hipLaunchKernelGGL(crit_backward_kernel, dim3((unsigned)(layers * a.wgl)), dim3(256), 0, (hipStream_t)stream, a, d_losses,
+                     d_elem, d_logits, d_boxes);
+  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+}
+
+// one layer: the same kernels with layers = 1
 extern "C" int dod_set_criterion_forward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
                                          int64_t boxes_row_stride, int B, int Q, int C, const int64_t* labels,
                                          const float* gt_boxes, int G, const int32_t* match, int M, const float* num_boxes,
                                          float alpha, float gamma, float* losses, float* elem_loss, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-  CritArgs a;
-  const int rc = crit_args(a, pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, B, Q, C, labels, gt_boxes, G,
-                           match, M, num_boxes, alpha, gamma);
-  if (rc != DOD_OK) return rc;
-  if (!losses || !workspace) return DOD_ERR_INVALID;
-  if (workspace_bytes < dod_set_criterion_workspace_bytes(B, Q, C)) return DOD_ERR_STATE;
-  const int nwg = crit_nwg(B, Q);
-  float* part = (float*)workspace;
-  hipLaunchKernelGGL(crit_forward_kernel, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, a, part, nwg, elem_loss);
-  hipLaunchKernelGGL(crit_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)part, nwg, num_boxes,
-                     losses);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_set_criterion_layers_forward(pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, 1, B, Q, C, labels, gt_boxes, G,
+                                          match, M, num_boxes, alpha, gamma, losses, elem_loss, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dod_set_criterion_backward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
@@ -280,12 +317,6 @@ extern "C" int dod_set_criterion_backward(const float* pred_logits, int64_t logi
                                           const float* gt_boxes, int G, const int32_t* match, int M,
                                           const float* num_boxes, float alpha, float gamma, const float* d_losses,
                                           const float* d_elem, float* d_logits, float* d_boxes, void* stream) {
-  CritArgs a;
-  const int rc = crit_args(a, pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, B, Q, C, labels, gt_boxes, G,
-                           match, M, num_boxes, alpha, gamma);
-  if (rc != DOD_OK) return rc;
-  if (!d_logits || (!d_losses && !d_elem) || (pred_boxes && d_boxes && !d_losses)) return DOD_ERR_INVALID;
-  hipLaunchKernelGGL(crit_backward_kernel, dim3((unsigned)crit_nwg(B, Q)), dim3(256), 0, (hipStream_t)stream, a, d_losses,
-                     d_elem, d_logits, d_boxes);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_set_criterion_layers_backward(pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, 1, B, Q, C, labels, gt_boxes, G,
+                                           match, M, num_boxes, alpha, gamma, d_losses, d_elem, d_logits, d_boxes, stream);
 }

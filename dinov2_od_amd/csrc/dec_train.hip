@@ -51,9 +51,9 @@ HeadW head_view(const dod_dense_dec_train_params& p) { return {p.class_w, p.clas
 struct AttnTape { float *in, *qkv, *att, *t1, *out; };      // layer input, q | k | v, attention output, pre-norm sum, LN1 output
 struct FfnTape { float *in, *hid, *t3; };                   // LN2 output, post-ReLU (pre-dropout) hidden, pre-norm sum; LN3 writes the next layer's input
 struct QScratch { float *y, *dx, *dt, *dbr, *dbig, *dqkv, *dS, *Pd, *dhb, *dz; };      // dx / dt: the two d(activation) buffers a backward alternates between
-void carve_attn(dod::Carver& c, const QDims& d, AttnTape* a) {
+void carve_attn(dod::Carver& c, const QDims& d, AttnTape* a, bool own_in = true) {      // own_in false: the caller points a->in at the layer below's output
   const size_t n = (size_t)d.BQ * d.Dd;
-  a->in = takef(c, n); a->qkv = takef(c, 3 * n); a->att = takef(c, n); a->t1 = takef(c, n); a->out = takef(c, n);
+  a->in = own_in ? takef(c, n) : nullptr; a->qkv = takef(c, 3 * n); a->att = takef(c, n); a->t1 = takef(c, n); a->out = takef(c, n);
 }
 
 // The linear's input where the forward dropped it (the FFN's inner dropout, untaped): regenerated from x [BQ, K] into sc.y; p == 0: x itself.
@@ -121,25 +121,26 @@ int ffn_bwd(const Ctx& c, int j, const FfnW& w, const FfnW& g, const FfnTape& f,
 }
 
 // class logits and sigmoid boxes into det [BQ, C+4] (detr_decoder.py:80-81; utils.py:14-30); tapes hb (post-ReLU) and boxes.
-int heads_fwd(const Ctx& c, const HeadW& w, const float* hs, float* hb, float* boxes, float* det) {
-  const int BQ = c.d.BQ, Dd = c.d.Dd, C = c.d.C;
+// BQ = rows: B*Q, or L*B*Q when every layer's output is supervised (the heads are shared, so all layers go through one pass).
+int heads_fwd(const Ctx& c, const HeadW& w, int BQ, const float* hs, float* hb, float* boxes, float* det) {
+  const int Dd = c.d.Dd, C = c.d.C;
   TK(launch_gemm_f32(hs, Dd, w.class_w, Dd, BQ, C, Dd, gepi(w.class_b, det, C + 4), c.s));
   TK(lin_fwd(hs, Dd, w.bb0_w, w.bb0_b, BQ, Dd / 2, Dd, hb, Dd / 2, ACT_RELU, c.s));
   TK(launch_gemm_f32(hb, Dd / 2, w.bb2_w, Dd / 2, BQ, 4, Dd / 2, gepi(w.bb2_b, det + C, C + 4, ACT_SIGMOID), c.s));
   TK(launch_copy2d(det + C, C + 4, boxes, 4, BQ, 4, 4, c.s));
   return DOD_OK;
 }
-// sc.dx is WRITTEN with d(hs), the last layer's d(output).  Clobbers sc.dz, sc.dhb.
-int heads_bwd(const Ctx& c, const HeadW& w, const HeadW& g, const float* d_det, const float* hs, const float* hb, const float* boxes, const QScratch& sc) {
-  const int BQ = c.d.BQ, Dd = c.d.Dd, C = c.d.C;
+// dhs [BQ, Dd] is WRITTEN with d(hs) (BQ = rows, as heads_fwd).  Clobbers sc.dz, sc.dhb.
+int heads_bwd(const Ctx& c, const HeadW& w, const HeadW& g, int BQ, const float* d_det, const float* hs, const float* hb, const float* boxes, float* dhs, const QScratch& sc) {
+  const int Dd = c.d.Dd, C = c.d.C;
   TK(sigmoid_bwd4(d_det + C, C + 4, boxes, 4, sc.dz, BQ, c.s));
   TK(lin_bwd_w(sc.dz, 4, hb, Dd / 2, BQ, 4, Dd / 2, G(g.bb2_w), G(g.bb2_b), c.s));
   TK(lin_bwd_x(sc.dz, 4, w.bb2_w, BQ, 4, Dd / 2, sc.dhb, false, c.s));
   TK(relu_drop_bwd(sc.dhb, hb, sc.dhb, (size_t)BQ * (Dd / 2), 0.f, 0ull, c.s));
   TK(lin_bwd_w(sc.dhb, Dd / 2, hs, Dd, BQ, Dd / 2, Dd, G(g.bb0_w), G(g.bb0_b), c.s));
-  TK(lin_bwd_x(sc.dhb, Dd / 2, w.bb0_w, BQ, Dd / 2, Dd, sc.dx, false, c.s));
+  TK(lin_bwd_x(sc.dhb, Dd / 2, w.bb0_w, BQ, Dd / 2, Dd, dhs, false, c.s));
   TK(lin_bwd_w(d_det, C + 4, hs, Dd, BQ, C, Dd, G(g.class_w), G(g.class_b), c.s));
-  TK(lin_bwd_x(d_det, C + 4, w.class_w, BQ, C, Dd, sc.dx, true, c.s));
+  TK(lin_bwd_x(d_det, C + 4, w.class_w, BQ, C, Dd, dhs, true, c.s));
   return DOD_OK;
 }
 
@@ -148,23 +149,26 @@ struct Dims : QDims { int P, ncat, ncp, fh, fw; };
 bool make_dims(const dod_config* c, int B, int N, Dims* d) {
   if (!c || !c->use_deformable || !make_qdims(c, B, N, d)) return false;
   d->P = c->n_points; d->ncat = 2 + 3 * d->Hd * d->P; d->ncp = (int)up4(d->ncat);
-  if (d->P > 8 || d->P < 1) return false;
+  if (d->P > 8 || d->P < 1 || d->L < 1 || d->L > 64) return false;      // Tape::l
   int s = 1; while ((s + 1) * (s + 1) <= N) ++s;          // (h, w) of deformable_attention.py:241-256
   d->fh = s; d->fw = s;
   if (s * s != N) for (int i = s; i > 0; --i) if (N % i == 0) { d->fh = i; d->fw = N / i; break; }
   return true;
 }
+// nh = layers the heads see: 1 (the last layer's output only) or L (deep supervision: detections [L, B, Q, C+4]).
+// hs_all [L, BQ, Dd]: slot j is layer j's LN3 output and (j + 1 < L) layer j+1's sa.in; hs = the last slot, or all nh = L of them.
 struct Tape {
-  float *values, *hs, *hb, *boxes;
+  float *values, *hs_all, *hb, *boxes;
   struct Layer { AttnTape sa; float *proj, *samp, *t2; FfnTape ffn; } l[64];      // sa.out = tgt1, ffn.in = tgt2
 };
-size_t carve_tape(const Dims& d, const void* base, Tape& tt) {
+size_t carve_tape(const Dims& d, int nh, const void* base, Tape& tt) {
   dod::Carver c = carver(base);
   const size_t BQ = d.BQ, Dd = d.Dd;
-  tt.values = takef(c, (size_t)d.M * Dd); tt.hs = takef(c, BQ * Dd); tt.hb = takef(c, BQ * (Dd / 2)); tt.boxes = takef(c, BQ * 4);
+  tt.values = takef(c, (size_t)d.M * Dd); tt.hs_all = takef(c, d.L * BQ * Dd); tt.hb = takef(c, nh * BQ * (Dd / 2)); tt.boxes = takef(c, nh * BQ * 4);
   for (int j = 0; j < d.L; ++j) {
     auto& L = tt.l[j];
-    carve_attn(c, d, &L.sa);
+    carve_attn(c, d, &L.sa, j == 0);
+    if (j && tt.hs_all) L.sa.in = tt.hs_all + (j - 1) * BQ * Dd;
     L.proj = takef(c, BQ * d.ncp); L.samp = takef(c, BQ * Dd); L.t2 = takef(c, BQ * Dd);
     L.ffn.in = takef(c, BQ * Dd); L.ffn.hid = takef(c, BQ * (size_t)d.F); L.ffn.t3 = takef(c, BQ * Dd);
   }
@@ -173,16 +177,18 @@ size_t carve_tape(const Dims& d, const void* base, Tape& tt) {
 struct Scratch : QScratch {
   float *cat_w, *cat_b;                                     // fused [ref | offsets | weights] linear
   float *dproj, *dcat_w, *dcat_b, *dvalues;                 // backward
+  float *dhs;                                               // d(hs_all) [nh, BQ, Dd]; its LAST slot is dx, where the layer loop starts
 };
-size_t carve_scratch(const Dims& d, const void* base, Scratch& s) {
+size_t carve_scratch(const Dims& d, int nh, const void* base, Scratch& s) {
   dod::Carver c = carver(base);
   const size_t BQ = d.BQ, Dd = d.Dd, F = d.F, M = d.M;
   const size_t maxcols = (size_t)(3 * Dd > F ? 3 * Dd : F);           // widest activation of the query side
   s.y = takef(c, BQ * maxcols); s.cat_w = takef(c, (size_t)d.ncp * Dd); s.cat_b = takef(c, d.ncp);
-  s.dx = takef(c, BQ * Dd); s.dt = takef(c, BQ * Dd); s.dbr = takef(c, BQ * Dd); s.dbig = takef(c, BQ * maxcols); s.dproj = takef(c, BQ * d.ncp);
+  s.dhs = takef(c, nh * BQ * Dd); s.dx = s.dhs ? s.dhs + (nh - 1) * BQ * Dd : nullptr;
+  s.dt = takef(c, BQ * Dd); s.dbr = takef(c, BQ * Dd); s.dbig = takef(c, BQ * maxcols); s.dproj = takef(c, BQ * d.ncp);
   s.dcat_w = takef(c, (size_t)d.ncp * Dd); s.dcat_b = takef(c, d.ncp); s.dqkv = takef(c, BQ * 3 * Dd);
   s.dS = takef(c, mha_scratch_floats(d.B, d.Hd, d.Q, d.Q)); s.Pd = takef(c, mha_scratch_floats(d.B, d.Hd, d.Q, d.Q));
-  s.dvalues = takef(c, M * Dd); s.dhb = takef(c, BQ * (Dd / 2)); s.dz = takef(c, BQ * 4);
+  s.dvalues = takef(c, M * Dd); s.dhb = takef(c, nh * BQ * (Dd / 2)); s.dz = takef(c, nh * BQ * 4);
   return c.off;
 }
 int build_cat(const Dims& d, const dod_dec_train_params* p, const Scratch& sc, hipStream_t s) {
@@ -198,25 +204,15 @@ int build_cat(const Dims& d, const dod_dec_train_params* p, const Scratch& sc, h
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t dod_decoder_train_tape_bytes(const dod_config* cfg, int B, int N) {
-  Dims d; Tape t; if (!make_dims(cfg, B, N, &d)) return 0;
-  return carve_tape(d, nullptr, t) + 256;
-}
-size_t dod_decoder_train_workspace_bytes(const dod_config* cfg, int B, int N) {
-  Dims d; Scratch sc; if (!make_dims(cfg, B, N, &d)) return 0;
-  return carve_scratch(d, nullptr, sc) + 256;
-}
-
-int dod_decoder_train_forward(const dod_config* cfg, const dod_dec_train_params* p, const float* memory, int B, int N, float dropout_p,
-                              uint64_t seed, float* det, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
+// The deformable step, for both forms of supervision.  aux: the heads run over every layer's output -- det / d_det are [L, B, Q, C+4],
+// slice j = decoder layer j, slice L-1 = what the plain step returns -- and d(layer j's output) gains d_hs_all[j] on the way down.
+int deform_forward(const dod_config* cfg, bool aux, const dod_dec_train_params* p, const float* memory, int B, int N, float dropout_p, uint64_t seed, float* det,
+                   void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
   Dims d;
   if (!make_dims(cfg, B, N, &d)) return tfail(DOD_ERR_INVALID, "decoder train: unsupported configuration (deformable branch, head_dim <= 128, Dd <= 1024, Q <= %d)", MHA_MAXQ);
+  const int nh = aux ? d.L : 1;
   Tape t; Scratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
-  int rc = entry_check("decoder train", p && memory && det && tape && ws, dropout_p, tape_bytes, carve_tape(d, tape, t) + 256, ws_bytes, carve_scratch(d, ws, sc) + 256); if (rc) return rc;
+  int rc = entry_check("decoder train", p && memory && det && tape && ws, dropout_p, tape_bytes, carve_tape(d, nh, tape, t) + 256, ws_bytes, carve_scratch(d, nh, ws, sc) + 256); if (rc) return rc;
   const Ctx c = {d, cfg->dec_ln_eps, dropout_p, 1.0f / sqrtf((float)d.dh), seed, (hipStream_t)stream};
   hipStream_t s = c.s;
   const int BQ = d.BQ, Dd = d.Dd, Q = d.Q;
@@ -234,18 +230,19 @@ int dod_decoder_train_forward(const dod_config* cfg, const dod_dec_train_params*
     TK(launch_gemm_f32(L.sa.out, Dd, sc.cat_w, Dd, BQ, d.ncat, Dd, gepi(sc.cat_b, L.proj, d.ncp), s));
     TK(launch_deform_sample(L.proj, d.ncp, t.values, B, Q, N, d.Hd, d.P, d.dh, d.fh, d.fw, L.samp, s, 0));
     rc = postnorm_fwd(c, j, 2, ow, L.samp, Dd, L.sa.out, L.t2, L.ffn.in, sc.y); if (rc) return rc;
-    rc = ffn_fwd(c, j, fw, L.ffn, j + 1 < d.L ? t.l[j + 1].sa.in : t.hs, sc); if (rc) return rc;
+    rc = ffn_fwd(c, j, fw, L.ffn, t.hs_all + (size_t)j * BQ * Dd, sc); if (rc) return rc;               // = layer j+1's sa.in
   }
-  return heads_fwd(c, head_view(*p), t.hs, t.hb, t.boxes, det);
+  return heads_fwd(c, head_view(*p), nh * BQ, t.hs_all + (size_t)(d.L - nh) * BQ * Dd, t.hb, t.boxes, det);
 }
 
-int dod_decoder_train_backward(const dod_config* cfg, const dod_dec_train_params* p, const float* memory, int B, int N, float dropout_p,
-                               uint64_t seed, const float* d_det, const void* tape, size_t tape_bytes, const dod_dec_train_params* grads,
-                               float* d_memory, void* ws, size_t ws_bytes, void* stream) {
+int deform_backward(const dod_config* cfg, bool aux, const dod_dec_train_params* p, const float* memory, int B, int N, float dropout_p, uint64_t seed,
+                    const float* d_det, const void* tape, size_t tape_bytes, const dod_dec_train_params* grads, float* d_memory, void* ws, size_t ws_bytes,
+                    void* stream) {
   Dims d;
   if (!make_dims(cfg, B, N, &d)) return tfail(DOD_ERR_INVALID, "decoder train: unsupported configuration");
+  const int nh = aux ? d.L : 1;
   Tape t; Scratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
-  int rc = entry_check("decoder train", p && memory && d_det && tape && grads && ws, 0.f, tape_bytes, carve_tape(d, tape, t) + 256, ws_bytes, carve_scratch(d, ws, sc) + 256); if (rc) return rc;
+  int rc = entry_check("decoder train", p && memory && d_det && tape && grads && ws, 0.f, tape_bytes, carve_tape(d, nh, tape, t) + 256, ws_bytes, carve_scratch(d, nh, ws, sc) + 256); if (rc) return rc;
   const Ctx c = {d, cfg->dec_ln_eps, dropout_p, 1.0f / sqrtf((float)d.dh), seed, (hipStream_t)stream};
   hipStream_t s = c.s;
   const int BQ = d.BQ, Dd = d.Dd, Q = d.Q, HP = d.Hd * d.P;
@@ -257,9 +254,11 @@ int dod_decoder_train_backward(const dod_config* cfg, const dod_dec_train_params
   TH(hipMemsetAsync(sc.dcat_w, 0, (size_t)d.ncp * Dd * 4, s));
   TH(hipMemsetAsync(sc.dcat_b, 0, (size_t)d.ncp * 4, s));
   TH(hipMemsetAsync(sc.dvalues, 0, (size_t)d.M * Dd * 4, s));
-  rc = heads_bwd(c, head_view(*p), head_view(*grads), d_det, t.hs, t.hb, t.boxes, sc); if (rc) return rc;      // dx = d(last layer's output)
+  // one pass over the nh * BQ supervised rows; the last slot of dhs is dx = d(last layer's output)
+  rc = heads_bwd(c, head_view(*p), head_view(*grads), nh * BQ, d_det, t.hs_all + (size_t)(d.L - nh) * BQ * Dd, t.hb, t.boxes, sc.dhs, sc); if (rc) return rc;
   for (int j = d.L - 1; j >= 0; --j) {
     const auto& L = t.l[j];
+    if (aux && j + 1 < d.L) TK(add_inplace(sc.dx, sc.dhs + (size_t)j * BQ * Dd, (size_t)BQ * Dd, s));             // + the heads' own d(layer j's output)
     rc = ffn_bwd(c, j, fw, fg, L.ffn, sc); if (rc) return rc;                                                   // dt = d(tgt2)
     // LN2 <- tgt1 + dropout2(output_proj(samp)): dx = d(t2), dt = d(samp)
     rc = postnorm_bwd(c, j, 2, ow, og, L.t2, L.samp, Dd, -1, sc.dt, sc.dx, sc.dt, sc); if (rc) return rc;
@@ -282,6 +281,38 @@ int dod_decoder_train_backward(const dod_config* cfg, const dod_dec_train_params
   TK(lin_bwd_w(sc.dvalues, Dd, memory, Dd, d.M, Dd, Dd, G(grads->vp_w), G(grads->vp_b), s));
   if (d_memory) TK(lin_bwd_x(sc.dvalues, Dd, p->vp_w, d.M, Dd, Dd, d_memory, false, s));
   return DOD_OK;
+}
+size_t deform_bytes(const dod_config* cfg, bool aux, bool tape, int B, int N) {
+  Dims d; Tape t; Scratch sc; if (!make_dims(cfg, B, N, &d)) return 0;
+  return (tape ? carve_tape(d, aux ? d.L : 1, nullptr, t) : carve_scratch(d, aux ? d.L : 1, nullptr, sc)) + 256;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dod_decoder_train_tape_bytes(const dod_config* cfg, int B, int N) { return deform_bytes(cfg, false, true, B, N); }
+size_t dod_decoder_train_workspace_bytes(const dod_config* cfg, int B, int N) { return deform_bytes(cfg, false, false, B, N); }
+size_t dod_decoder_train_aux_tape_bytes(const dod_config* cfg, int B, int N) { return deform_bytes(cfg, true, true, B, N); }
+size_t dod_decoder_train_aux_workspace_bytes(const dod_config* cfg, int B, int N) { return deform_bytes(cfg, true, false, B, N); }
+
+int dod_decoder_train_forward(const dod_config* cfg, const dod_dec_train_params* p, const float* memory, int B, int N, float dropout_p,
+                              uint64_t seed, float* det, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
+  return deform_forward(cfg, false, p, memory, B, N, dropout_p, seed, det, tape, tape_bytes, ws, ws_bytes, stream);
+}
+int dod_decoder_train_backward(const dod_config* cfg, const dod_dec_train_params* p, const float* memory, int B, int N, float dropout_p,
+                               uint64_t seed, const float* d_det, const void* tape, size_t tape_bytes, const dod_dec_train_params* grads,
+                               float* d_memory, void* ws, size_t ws_bytes, void* stream) {
+  return deform_backward(cfg, false, p, memory, B, N, dropout_p, seed, d_det, tape, tape_bytes, grads, d_memory, ws, ws_bytes, stream);
+}
+int dod_decoder_train_aux_forward(const dod_config* cfg, const dod_dec_train_params* p, const float* memory, int B, int N, float dropout_p,
+                                  uint64_t seed, float* det, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
+  return deform_forward(cfg, true, p, memory, B, N, dropout_p, seed, det, tape, tape_bytes, ws, ws_bytes, stream);
+}
+int dod_decoder_train_aux_backward(const dod_config* cfg, const dod_dec_train_params* p, const float* memory, int B, int N, float dropout_p,
+                                   uint64_t seed, const float* d_det, const void* tape, size_t tape_bytes, const dod_dec_train_params* grads,
+                                   float* d_memory, void* ws, size_t ws_bytes, void* stream) {
+  return deform_backward(cfg, true, p, memory, B, N, dropout_p, seed, d_det, tape, tape_bytes, grads, d_memory, ws, ws_bytes, stream);
 }
 
 }  // extern "C"
@@ -355,7 +386,7 @@ int dod_dense_decoder_train_forward(const dod_config* cfg, const dod_dense_dec_t
     rc = postnorm_fwd(c, j, 2, {W.ca_out_w, W.ca_out_b, W.norm2_w, W.norm2_b}, L.catt, Dd, L.sa.out, L.t2, L.ffn.in, sc.y); if (rc) return rc;
     rc = ffn_fwd(c, j, ffn_view(W), L.ffn, j + 1 < d.L ? t.l[j + 1].sa.in : t.hs, sc); if (rc) return rc;
   }
-  return heads_fwd(c, head_view(*p), t.hs, t.hb, t.boxes, det);
+  return heads_fwd(c, head_view(*p), BQ, t.hs, t.hb, t.boxes, det);
 }
 
 int dod_dense_decoder_train_backward(const dod_config* cfg, const dod_dense_dec_train_params* p, const float* memory, int B, int N, float dropout_p,
@@ -371,7 +402,7 @@ int dod_dense_decoder_train_backward(const dod_config* cfg, const dod_dense_dec_
   const int BQ = d.BQ, Dd = d.Dd, Q = d.Q;
   float* dmem = d_memory ? d_memory : sc.dmem;                 // d(memory): the sum over the layers' k | v projections
   TH(hipMemsetAsync(dmem, 0, (size_t)d.M * Dd * 4, s));
-  rc = heads_bwd(c, head_view(*p), head_view(*grads), d_det, t.hs, t.hb, t.boxes, sc); if (rc) return rc;      // dx = d(last layer's output)
+  rc = heads_bwd(c, head_view(*p), head_view(*grads), BQ, d_det, t.hs, t.hb, t.boxes, sc.dx, sc); if (rc) return rc;      // dx = d(last layer's output)
   for (int j = d.L - 1; j >= 0; --j) {
     const dod_dense_layer_params& W = p->layers[j];
     const dod_dense_layer_params& Gw = grads->layers[j];

@@ -147,6 +147,80 @@ def native_losses(logits, boxes, labels, gt_boxes, match, num_boxes, alpha=0.25,
     return _CriterionFn.apply(logits, boxes, labels, gt_boxes, match, num_boxes, alpha, gamma)
 
 
+def _packed_layers(ts, last):
+    """L tensors [B, Q, last] -> (base tensor, row stride, keepalive) with layer l's row (b, q) at base + ((l*B + b)*Q + q) *
+    stride: in place when they are consecutive slices of one packed buffer (the [L, B, Q, C+4] detections of the native
+    deep-supervision step), else one stacked copy"""
+    rows = [_rows(t, last) for t in ts]
+    t0, s0 = rows[0]
+    step = t0.shape[0] * t0.shape[1] * s0 * 4
+    if all(s == s0 and t.data_ptr() == t0.data_ptr() + l * step for l, (t, s) in enumerate(rows)):
+        return t0, s0, [t for t, _ in rows]
+    st = torch.stack([t for t, _ in rows]).contiguous()
+    return st, last, [st]
+
+
+class _CriterionLayersFn(torch.autograd.Function):
+    """(L x pred_logits, L x pred_boxes) -> fp32 [L, 3] unweighted losses, all layers in the two launches of
+    dod_set_criterion_layers_forward; backward = one dod_set_criterion_layers_backward launch"""
+
+    @staticmethod
+    def forward(ctx, nl, labels, gt_boxes, match, num_boxes, alpha, gamma, *preds):
+        from . import _native as nat
+        logits, boxes = preds[:nl], preds[nl:]
+        B, Q, C = logits[0].shape
+        lg, ls, keep_l = _packed_layers(logits, C)
+        bx, bs, keep_b = _packed_layers(boxes, 4)
+        L = nat.lib()
+        ws = torch.empty(L.dod_set_criterion_layers_workspace_bytes(nl, B, Q, C) // 4, dtype=torch.float32, device=lg.device)
+        out = torch.empty((nl, 3), dtype=torch.float32, device=lg.device)
+        nat.check(L.dod_set_criterion_layers_forward(nat.ptr(lg), ls, nat.ptr(bx), bs, nl, B, Q, C, nat.ptr(labels), nat.ptr(gt_boxes),
+                                                     labels.numel(), nat.ptr(match), nl * B * Q, nat.ptr(num_boxes), float(alpha),
+                                                     float(gamma), nat.ptr(out), None, nat.ptr(ws), ws.numel() * 4, nat.stream_ptr()))
+        ctx.save_for_backward(labels, gt_boxes, match, num_boxes, *keep_l, *keep_b)
+        ctx.meta = (nl, B, Q, C, lg.data_ptr(), ls, bx.data_ptr(), bs, len(keep_l), float(alpha), float(gamma),
+                    [t.dtype for t in preds])
+        return out
+
+    @staticmethod
+    def backward(ctx, d_losses):
+        from . import _native as nat
+        labels, gt_boxes, match, num_boxes, *keep = ctx.saved_tensors
+        nl, B, Q, C, lgp, ls, bxp, bs, nkl, alpha, gamma, dts = ctx.meta
+        assert keep[0].data_ptr() == lgp and keep[nkl].data_ptr() == bxp       # the saved tensors ARE the buffers the forward read
+        d = d_losses.to(torch.float32).contiguous()
+        dev = keep[0].device
+        d_logits = torch.empty((nl, B, Q, C), dtype=torch.float32, device=dev)
+        d_boxes = torch.empty((nl, B, Q, 4), dtype=torch.float32, device=dev)
+        nat.check(nat.lib().dod_set_criterion_layers_backward(lgp, ls, bxp, bs, nl, B, Q, C, nat.ptr(labels), nat.ptr(gt_boxes),
+                                                              labels.numel(), nat.ptr(match), nl * B * Q, nat.ptr(num_boxes), alpha,
+                                                              gamma, nat.ptr(d), None, nat.ptr(d_logits), nat.ptr(d_boxes),
+                                                              nat.stream_ptr()))
+        grads = list(d_logits.unbind(0)) + list(d_boxes.unbind(0))
+        return (None,) * 7 + tuple(g.to(dt) for g, dt in zip(grads, dts))
+
+
+def native_losses_layers(logits, boxes, labels, gt_boxes, match, num_boxes, alpha=0.25, gamma=2.0):
+    """The unweighted losses [L, 3] of L layers' predictions (lists of [B,Q,C] / [B,Q,4] CUDA tensors) against one set of
+    targets; match int32 [L*B*Q]: each layer's own table, in the order of the lists"""
+    nl = len(logits)
+    if nl == 0 or len(boxes) != nl or not all(t.is_cuda for t in logits):
+        raise ValueError("native_losses_layers needs L >= 1 CUDA predictions (use composite_losses on the CPU)")
+    dev = logits[0].device
+    labels = labels.to(dev, torch.int64).contiguous()
+    gt_boxes = gt_boxes.to(dev, torch.float32).contiguous()
+    match = match.to(dev, torch.int32).contiguous()
+    num_boxes = num_boxes.to(dev, torch.float32).contiguous()
+    if gt_boxes.numel() != 4 * labels.numel():
+        raise ValueError("gt_boxes must be [G, 4] with G = len(labels)")
+    if match.numel() != nl * logits[0].shape[0] * logits[0].shape[1]:
+        raise ValueError("match must hold L*B*Q entries")
+    for lg, bx in zip(logits, boxes):
+        if lg.shape != logits[0].shape or bx.shape[:2] != lg.shape[:2] or bx.shape[-1] != 4:
+            raise ValueError("every layer needs pred_logits [B, Q, C] and pred_boxes [B, Q, 4] of the same shape")
+    return _CriterionLayersFn.apply(nl, labels, gt_boxes, match, num_boxes, alpha, gamma, *logits, *boxes)
+
+
 # ------------------------------------------------------------------ host glue
 def match_table(indices, counts, Q, pin=False):
     """int32 [B*Q] table from the matcher's (pred_idx, tgt_idx) pairs: entry b*Q + i = offset_b + j, else -1"""
@@ -205,7 +279,55 @@ class SetCriterion(nn.Module):
                 exc, msg = ASSIGN_ERRORS[s]
                 raise exc(msg)
 
+    def _forward_layers(self, outputs, targets):
+        """DETR's deep supervision (`outputs["aux_outputs"]`: the heads on decoder layers 0 .. L-2): every layer gets its own
+        assignment from the unchanged matcher, all share one num_boxes, the result gains loss_*_{i}; a key k_i is weighted by
+        weight_dict[k_i] if present, else weight_dict[k], else 1.  On the GPU all layers go through ONE layered call."""
+        aux = list(outputs["aux_outputs"])
+        layers = aux + [{k: outputs[k] for k in ("pred_logits", "pred_boxes")}]       # memory order of the native step's packed detections
+        B, Q, C = outputs["pred_logits"].shape
+        for o in layers:
+            if o["pred_logits"].shape[-1] != self.num_classes:
+                raise RuntimeError(f"criterion.num_classes = {self.num_classes} but pred_logits has {o['pred_logits'].shape[-1]} classes")
+        dev = outputs["pred_logits"].device
+        counts = [int(len(t["labels"])) for t in targets]
+        if self.device_assignment:
+            if dev.type != "cuda":
+                raise ValueError("device_assignment needs CUDA outputs")
+            tabs = [self.matcher.match_table(o, targets) for o in layers]
+            match = torch.cat([m for m, _ in tabs])
+            self.last_assignment_status = torch.cat([tabs[-1][1]] + [st for _, st in tabs[:-1]])      # the last layer's B, then each aux layer's
+        else:
+            pin = dev.type == "cuda"
+            match = torch.cat([match_table(self.matcher(o, targets), counts, Q, pin=False) for o in layers])
+            if pin:
+                match = match.pin_memory().to(dev, non_blocking=True)
+        nb = torch.full((1,), float(sum(counts)), dtype=torch.float32, device=dev)
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(nb)                              # once for all layers
+        if sum(counts):
+            labels = torch.cat([t["labels"].reshape(-1).to(dev, torch.int64) for t in targets if len(t["labels"])])
+            gt = torch.cat([t["boxes"].reshape(-1, 4).to(dev, torch.float32) for t in targets if len(t["labels"])])
+        else:
+            labels = torch.zeros(0, dtype=torch.int64, device=dev)
+            gt = torch.zeros((0, 4), dtype=torch.float32, device=dev)
+        lgs, bxs = [o["pred_logits"] for o in layers], [o["pred_boxes"] for o in layers]
+        if dev.type == "cuda":
+            losses = native_losses_layers(lgs, bxs, labels, gt, match, nb, self.focal_alpha, self.focal_gamma)
+        else:
+            losses = torch.stack([composite_losses(lg, bx, labels, gt, match[l * B * Q:(l + 1) * B * Q], nb, self.focal_alpha, self.focal_gamma)
+                                  for l, (lg, bx) in enumerate(zip(lgs, bxs))])
+        w = self.weight_dict
+        out = {k: w[k] * losses[-1, n] if k in w else losses[-1, n] for n, k in enumerate(LOSS_KEYS)}
+        for i in range(len(aux)):
+            for n, k in enumerate(LOSS_KEYS):
+                ki = f"{k}_{i}"
+                out[ki] = w[ki] * losses[i, n] if ki in w else (w[k] * losses[i, n] if k in w else losses[i, n])
+        return out
+
     def forward(self, outputs, targets):
+        if "aux_outputs" in outputs:
+            return self._forward_layers(outputs, targets)
         logits, boxes = outputs["pred_logits"], outputs["pred_boxes"]
         B, Q, C = logits.shape
         if C != self.num_classes:

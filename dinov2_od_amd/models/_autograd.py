@@ -112,6 +112,7 @@ def decoder_forward(m, src):
     B, N, Dd = src.shape
     Q, Hd, P = dc.num_queries, dc.nheads, dc.n_points
     tgt = m.query_embed.weight.unsqueeze(0).repeat(B, 1, 1)
+    intermediate = []                                 # deformable_attention.py:300-309: every layer's output
     if m.use_deformable:
         h, w = spatial_factor(N)
         for layer in m.decoder.layers:
@@ -125,7 +126,14 @@ def decoder_forward(m, src):
             samp = deformable_sample(val, ref, off, aw, h, w).reshape(B, Q, Dd)
             tgt = layer.norm2(tgt + layer.dropout2(ca.output_proj(samp)))
             tgt = layer.norm3(tgt + layer.dropout4(layer.linear2(layer.dropout3(F.relu(layer.linear1(tgt))))))
+            intermediate.append(tgt)
         hs = tgt
     else:
         hs = m.decoder(tgt.permute(1, 0, 2), src.permute(1, 0, 2)).transpose(0, 1)
-    return {"pred_logits": m.class_embed(hs), "pred_boxes": m.bbox_embed.mlp(hs).sigmoid()}
+
+    def heads(x):
+        return {"pred_logits": m.class_embed(x), "pred_boxes": m.bbox_embed.mlp(x).sigmoid()}
+    out = heads(hs)
+    if getattr(m, "aux_loss", False):                 # DETR's convention: layers 0 .. L-2, the shared heads on each
+        out["aux_outputs"] = [heads(x) for x in intermediate[:-1]]
+    return out

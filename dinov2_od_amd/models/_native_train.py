@@ -71,8 +71,9 @@ def _check(rc):
 
 
 # What tells the two decoder steps apart: the four entry points dod_<stem>_train_{tape_bytes, workspace_bytes, forward, backward}, the
-# builder of the parameter struct (tensors, cfg) -> (struct, keepalive), and whether d(memory) may be NULL when autograd does not ask for it
-_Step = collections.namedtuple("_Step", "stem struct null_d_memory")
+# builder of the parameter struct (tensors, cfg) -> (struct, keepalive), and whether d(memory) may be NULL when autograd does not ask for it.
+# aux: the dod_<stem>_train_aux_* form, whose detections are [L, B, Q, C+4] (every decoder layer's output through the shared heads)
+_Step = collections.namedtuple("_Step", "stem struct null_d_memory aux", defaults=(False,))
 
 
 class _DecoderStep(torch.autograd.Function):
@@ -80,7 +81,7 @@ class _DecoderStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, src, step, cfg, p, seed, *params):
-        fn = {k: getattr(nat.lib(), f"dod_{step.stem}_train_{k}") for k in ("tape_bytes", "workspace_bytes", "forward", "backward")}
+        fn = {k: getattr(nat.lib(), f"dod_{step.stem}_train_{'aux_' if step.aux else ''}{k}") for k in ("tape_bytes", "workspace_bytes", "forward", "backward")}
         B, N, _ = src.shape
         src = src.contiguous()
         params = [t.detach().contiguous() for t in params]
@@ -89,7 +90,7 @@ class _DecoderStep(torch.autograd.Function):
             ws = torch.empty(fn["workspace_bytes"](C.byref(cfg), B, N), dtype=torch.uint8, device=src.device)
             if tape.numel() == 0 or ws.numel() == 0:
                 raise ValueError("decoder configuration not supported by the native training kernels")
-            det = torch.empty(B, cfg.num_queries, cfg.num_classes + 4, dtype=torch.float32, device=src.device)
+            det = torch.empty(*((cfg.dec_layers,) if step.aux else ()), B, cfg.num_queries, cfg.num_classes + 4, dtype=torch.float32, device=src.device)
             ps, keep = step.struct(params, cfg)
             _check(fn["forward"](C.byref(cfg), C.byref(ps), nat.ptr(src), B, N, float(p), int(seed), nat.ptr(det), nat.ptr(tape), tape.numel(),
                                  nat.ptr(ws), ws.numel(), nat.stream_ptr()))
@@ -119,12 +120,14 @@ def _draw_seed():
 
 
 _DEFORMABLE = _Step("decoder", _struct, null_d_memory=True)
+_DEFORMABLE_AUX = _Step("decoder", _struct, null_d_memory=True, aux=True)
 
 
-def decoder_train(m, src, seed=None):
-    """DETRDecoder.forward in train() mode -> packed detections [B, Q, C+4] with the autograd edge to the native backward"""
+def decoder_train(m, src, seed=None, aux=False):
+    """DETRDecoder.forward in train() mode -> packed detections [B, Q, C+4] with the autograd edge to the native backward;
+    aux: [L, B, Q, C+4], slice j = the heads on decoder layer j's output (the last slice is the plain step's result)"""
     cfg = make_config(m._bb_cfg, m._dc_cfg, "fp32")
-    return _DecoderStep.apply(src, _DEFORMABLE, cfg, dropout_rate(m), _draw_seed() if seed is None else seed, *_param_list(m))
+    return _DecoderStep.apply(src, _DEFORMABLE_AUX if aux else _DEFORMABLE, cfg, dropout_rate(m), _draw_seed() if seed is None else seed, *_param_list(m))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

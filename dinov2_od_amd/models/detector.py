@@ -10,7 +10,8 @@ from .detr_decoder import DETRDecoder
 
 class DINOv2ObjectDetector(_EngineMixin, nn.Module):   # state-dict keys already carry "backbone." / "decoder."
     """Same constructor defaults as the reference (config.py:21-35 via detector.py:9-21).
-    Extra keyword arguments: `pretrained`, `precision`, `backbone_config` (micro test models)."""
+    Extra keyword arguments: `pretrained`, `precision`, `backbone_config` (micro test models), `aux_loss` (train() outputs
+    gain "aux_outputs": DETRDecoder)."""
 
     def __init__(self,
                  num_classes=REF_DEFAULTS["num_classes"],
@@ -25,7 +26,7 @@ class DINOv2ObjectDetector(_EngineMixin, nn.Module):   # state-dict keys already
                  dropout=REF_DEFAULTS["dropout"],
                  n_points=REF_DEFAULTS["n_points"],
                  use_deformable=REF_DEFAULTS["use_deformable"],
-                 pretrained=True, precision=None, backbone_config=None):
+                 pretrained=True, precision=None, backbone_config=None, aux_loss=False):
         super().__init__()
         if hidden_dim is None:                                  # detector.py:25-35
             hidden_dim = 768
@@ -40,7 +41,7 @@ class DINOv2ObjectDetector(_EngineMixin, nn.Module):   # state-dict keys already
         self.decoder = DETRDecoder(num_queries=num_queries, hidden_dim=hidden_dim, nheads=nheads,
                                    num_decoder_layers=num_decoder_layers, num_classes=num_classes,
                                    dim_feedforward=dim_feedforward, dropout=dropout, n_points=n_points,
-                                   use_deformable=use_deformable, precision=precision)
+                                   use_deformable=use_deformable, precision=precision, aux_loss=aux_loss)
         self.precision = precision
         self._dropout_p = float(dropout)
         self._bb_cfg = self.backbone._bb_cfg

@@ -70,11 +70,17 @@ class MLP(_Box):
 
 
 class DETRDecoder(_EngineMixin, nn.Module):
-    """dino_detector/models/detr_decoder.py:7-83; `precision` is the only extra argument."""
+    """dino_detector/models/detr_decoder.py:7-83; `precision` and `aux_loss` are the only extra arguments.
+    aux_loss=True (deformable branch): in train() the output dict gains "aux_outputs", DETR's list of L-1 dicts
+    {"pred_logits", "pred_boxes"} -- the shared heads on the outputs of decoder layers 0 .. L-2 -- for deep supervision
+    (losses.SetCriterion adds their losses as loss_*_{i}).  eval() never has the key.  No parameter is added."""
 
     def __init__(self, num_queries, hidden_dim, nheads, num_decoder_layers, num_classes,
-                 dim_feedforward=2048, dropout=0.1, n_points=4, use_deformable=True, precision=None):
+                 dim_feedforward=2048, dropout=0.1, n_points=4, use_deformable=True, precision=None, aux_loss=False):
         super().__init__()
+        if aux_loss and not use_deformable:
+            raise ValueError("aux_loss=True needs use_deformable=True: the dense nn.TransformerDecoder branch returns no per-layer states")
+        self.aux_loss = bool(aux_loss)
         self.num_queries = num_queries
         self.use_deformable = use_deformable
         self.query_embed = nn.Embedding(num_queries, hidden_dim)
@@ -111,7 +117,12 @@ class DETRDecoder(_EngineMixin, nn.Module):
             # take stay on the autograd composite
             if os.environ.get("DINODET_NATIVE_TRAIN", "1") != "0":
                 if _native_train.supported(self, src):
-                    return split_detections(_native_train.decoder_train(self, src), self._dc_cfg.num_classes)
+                    det = _native_train.decoder_train(self, src, aux=self.aux_loss)
+                    if not self.aux_loss:
+                        return split_detections(det, self._dc_cfg.num_classes)
+                    out = split_detections(det[-1], self._dc_cfg.num_classes)
+                    out["aux_outputs"] = [split_detections(d, self._dc_cfg.num_classes) for d in det[:-1].unbind(0)]
+                    return out
                 if _native_train.dense_supported(self, src):
                     return split_detections(_native_train.dense_decoder_train(self, src), self._dc_cfg.num_classes)
             return _autograd.decoder_forward(self, src)

@@ -424,6 +424,24 @@ int dod_set_criterion_backward(const float* pred_logits, int64_t logits_row_stri
                                int64_t boxes_row_stride, int B, int Q, int C, const int64_t* labels, const float* gt_boxes,
                                int G, const int32_t* match, int M, const float* num_boxes, float alpha, float gamma,
                                const float* d_losses, const float* d_elem, float* d_logits, float* d_boxes, void* stream);
+/* The same loss over `layers` decoder outputs against ONE set of targets (deep supervision: DETR's aux_outputs), all layers
+ * in the same two / one launches.  Row r = (l*B + b)*Q + q at base + r * row_stride -- the packed [L, B, Q, C+4] detections
+ * of dod_decoder_train_aux_forward are read in place; match int32 [M = layers*B*Q] holds each layer's own assignment as
+ * global target rows into the one labels / gt_boxes array; losses and d_losses are fp32 [layers, 3]; d_logits / d_boxes /
+ * elem_loss / d_elem are dense over all layers*B*Q rows.  Workgroups are partitioned per layer exactly as the single-layer
+ * call partitions B*Q rows, so layer l's losses and gradients are bit-identical to that call on the layer's slice
+ * (layers = 1 IS the single-layer call). */
+size_t dod_set_criterion_layers_workspace_bytes(int layers, int B, int Q, int C);
+int dod_set_criterion_layers_forward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
+                                     int64_t boxes_row_stride, int layers, int B, int Q, int C, const int64_t* labels,
+                                     const float* gt_boxes, int G, const int32_t* match, int M, const float* num_boxes,
+                                     float alpha, float gamma, float* losses, float* elem_loss, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int dod_set_criterion_layers_backward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
+                                      int64_t boxes_row_stride, int layers, int B, int Q, int C, const int64_t* labels,
+                                      const float* gt_boxes, int G, const int32_t* match, int M, const float* num_boxes,
+                                      float alpha, float gamma, const float* d_losses, const float* d_elem, float* d_logits,
+                                      float* d_boxes, void* stream);
 
 /* ---- native training step of the decoder + heads (first slice) ---------------------------------------
  * What `loss.backward()` at dino_detector/train.py:1101 needs from DETRDecoder.forward (detr_decoder.py:47-83) over the
@@ -455,6 +473,19 @@ int dod_decoder_train_backward(const dod_config* cfg, const dod_dec_train_params
                                float dropout_p, uint64_t seed, const float* d_detections, const void* tape, size_t tape_bytes,
                                const dod_dec_train_params* grads, float* d_memory, void* workspace, size_t workspace_bytes,
                                void* stream);
+/* The same step with every decoder layer's output supervised (DETR's aux_loss): detections / d_detections are
+ * [L, B, Q, C+4], slice j = the shared heads on decoder layer j's output, slice L-1 = what dod_decoder_train_forward
+ * returns.  Same schedule, dropout sites and keys; the heads run once over all L*B*Q rows in either direction.  Tape and
+ * workspace have their own sizes. */
+size_t dod_decoder_train_aux_tape_bytes(const dod_config* cfg, int B, int N);
+size_t dod_decoder_train_aux_workspace_bytes(const dod_config* cfg, int B, int N);
+int dod_decoder_train_aux_forward(const dod_config* cfg, const dod_dec_train_params* params, const float* memory, int B, int N,
+                                  float dropout_p, uint64_t seed, float* detections, void* tape, size_t tape_bytes,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int dod_decoder_train_aux_backward(const dod_config* cfg, const dod_dec_train_params* params, const float* memory, int B, int N,
+                                   float dropout_p, uint64_t seed, const float* d_detections, const void* tape, size_t tape_bytes,
+                                   const dod_dec_train_params* grads, float* d_memory, void* workspace, size_t workspace_bytes,
+                                   void* stream);
 const char* dod_decoder_train_last_error(void);
 
 /* The nn.TransformerDecoder branch of DETRDecoder (use_deformable = False; detr_decoder.py:28-35, 62-69) in train() mode:
@@ -625,7 +656,8 @@ const char* dod_version(void);
  * the tests use, the folded-LayerNorm operators arrived; revision 5: the dod_set_criterion_* entry points; revision 6: dod_match_assign*).
  * New entry points alone change no signature and no layout: dod_coco_eval_* and dod_op_sort_pairs_* joined revision 6, and a caller that
  * needs them resolves them by name (the Python binding fails at load when one is missing).  The training-step operators
- * (dod_op_layernorm_bwd ... dod_op_colsum_add) joined revision 6 the same way.  So did the optimizer step (dod_optim_*).
+ * (dod_op_layernorm_bwd ... dod_op_colsum_add) joined revision 6 the same way.  So did the optimizer step (dod_optim_*), the deep-supervision
+ * step (dod_decoder_train_aux_*) and the layered criterion (dod_set_criterion_layers_*).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);

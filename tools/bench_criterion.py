@@ -4,7 +4,9 @@ launches, one backward launch) against the torch composite of the same math on t
 losses.py drives it (num_boxes read back with .item(), then the per-term kernels), at B=16/Q=100/C=91 and B=64/Q=300/C=91;
 then one ViT-B/14 224x224 batch-16 train step (train()-mode forward, our matcher, criterion, backward) with each criterion.
 hipEvent pairs around every step, warm-up first, median and p10 / p90 over --steps steps.  One JSON line on stdout.
-    python tools/bench_criterion.py [--steps 30] [--warmup 5]"""
+    python tools/bench_criterion.py [--steps 30] [--warmup 5]
+--aux: instead, the layered criterion (deep supervision: L = 3 layers of a packed [L, B, Q, C+4] buffer through ONE
+dod_set_criterion_layers_* call) against L single-layer calls on the same slices, forward + backward, device-resident inputs."""
 import argparse
 import json
 import os
@@ -93,6 +95,27 @@ def criterion_legs(B, Q, C, steps, warmup):
             "composite": _time(step(comp), steps, warmup)}
 
 
+def layered_legs(B, Q, C, nl, steps, warmup):
+    rng = np.random.default_rng(B * Q + nl)
+    counts = [int(rng.integers(1, 21)) for _ in range(B)]
+    det = np.stack([cc.synth_inputs(B, Q, C, counts, seed=7 + l)[0] for l in range(nl)])
+    _, labels, gt, offs = cc.synth_inputs(B, Q, C, counts, seed=7)
+    tabs = [L.match_table([(torch.from_numpy(np.sort(rng.permutation(Q)[:n]).astype(np.int64)), torch.from_numpy(rng.permutation(n).astype(np.int64)))
+                           for n in counts], counts, Q).cuda() for _ in range(nl)]
+    d = torch.from_numpy(det).cuda().requires_grad_(True)
+    lab, g, nb = torch.from_numpy(labels).cuda(), torch.from_numpy(gt).cuda(), torch.tensor([float(sum(counts))], device="cuda")
+    match = torch.cat(tabs)
+
+    def layered():
+        d.grad = None
+        L.native_losses_layers([d[l, ..., :C] for l in range(nl)], [d[l, ..., C:] for l in range(nl)], lab, g, match, nb).sum().backward()
+
+    def singles():
+        d.grad = None
+        sum(L.native_losses(d[l, ..., :C], d[l, ..., C:], lab, g, tabs[l], nb).sum() for l in range(nl)).backward()
+    return {"layered_call": _time(layered, steps, warmup), f"{nl}_single_layer_calls": _time(singles, steps, warmup)}
+
+
 def train_step_legs(steps, warmup):
     from bench import build
     from dinov2_od_amd.matching import HungarianMatcher
@@ -122,9 +145,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--aux", action="store_true")
     a = ap.parse_args()
     assert a.steps >= 20
     out = {"tool": "bench_criterion", "device": torch.cuda.get_device_name(0), "torch": torch.__version__}
+    if a.aux:
+        for B, Q, C in ((16, 100, 91), (64, 300, 91)):
+            out[f"criterion_layers_fwd_bwd_L3_B{B}_Q{Q}_C{C}"] = layered_legs(B, Q, C, 3, a.steps, a.warmup)
+        print(json.dumps(out))
+        return
     for B, Q, C in ((16, 100, 91), (64, 300, 91)):
         out[f"criterion_fwd_bwd_B{B}_Q{Q}_C{C}"] = criterion_legs(B, Q, C, a.steps, a.warmup)
     out["train_step_vitb_224_b16"] = train_step_legs(a.steps, a.warmup)
