@@ -1,7 +1,7 @@
 // Native training step of the decoder + heads (first slice): train-mode forward with a tape and
 // the backward of DETRDecoder.forward (detr_decoder.py:47-83) -- what `loss.backward()` at train.py:1101 computes for the decoder, the
 // heads and d(memory) (which then flows into the projection / LoRA blocks, tail_train.hip).  fp32 throughout (master weights, exact-fp32
-// MFMA GEMMs).  Two schedules over shared sub-blocks; every kernel and launcher is in train_ops.hip.
+// MFMA GEMMs) unless the configuration asks for DOD_PREC_BF16X3 (Ctx::mm below).  Two schedules over shared sub-blocks; every kernel and launcher is in train_ops.hip.
 //
 // Deformable (weight-tied DeformableDecoderLayer, deformable_attention.py:215-268, :284):
 //   forward  : query tiling -> per layer { MHA self-attention (dropout on the probabilities, nn.MultiheadAttention) -> +dropout1
@@ -31,7 +31,10 @@ bool make_qdims(const dod_config* c, int B, int N, QDims* d) {
   return !(d->Dd % d->Hd || d->dh > 128 || d->dh % 4 || d->Dd % 4 || d->F % 4 || (d->Dd / 2) % 4 || d->Dd > 1024 || d->Q > MHA_MAXQ);
 }
 // one call of a step: shapes, the rate and seed both directions are given, the stream
-struct Ctx { QDims d; float eps, p, scale; unsigned long long seed; hipStream_t s; };
+// mm: the step's product mode (train_internal.h Mm), which every BACKWARD linear and the forward products over the B*N memory rows take.  The
+// query-side FORWARD linears pass MM_F32 whatever the mode: they feed the reference points and offsets, whose floor() (deformable_attention.py:114-115)
+// turns a last-bit difference into another sampling cell -- the rows eval() keeps in fp32 in every precision mode, for the same reason.
+struct Ctx { QDims d; float eps, p, scale; unsigned long long seed; hipStream_t s; Mm mm; };
 // gradients are written through the const-qualified structs' pointers (same layout as the parameters, float accumulators)
 inline float* G(const float* q) { return const_cast<float*>(q); }
 
@@ -66,7 +69,7 @@ int dropped_input(const Ctx& c, int j, int site, const float* x, int K, const QS
 // out = LN(resid + dropout_site(x W^T + b)), x [BQ, K].  t receives the pre-norm sum (taped); ybuf [BQ, Dd] is clobbered.
 int postnorm_fwd(const Ctx& c, int j, int site, const PostW& w, const float* x, int K, const float* resid, float* t, float* out, float* ybuf) {
   const int BQ = c.d.BQ, Dd = c.d.Dd;
-  TK(lin_fwd(x, K, w.w, w.b, BQ, Dd, K, ybuf, Dd, ACT_NONE, c.s));
+  TK(lin_fwd(x, K, w.w, w.b, BQ, Dd, K, ybuf, Dd, ACT_NONE, MM_F32, c.s));
   TK(dropout_add(resid, ybuf, t, (size_t)BQ * Dd, c.p, site_key(c.seed, j, site), c.s));
   TK(launch_layernorm(t, nullptr, w.norm_w, w.norm_b, c.eps, BQ, Dd, ln_out(out), c.s));
   return DOD_OK;
@@ -79,15 +82,15 @@ int postnorm_bwd(const Ctx& c, int j, int site, const PostW& w, const PostW& g, 
   TK(ln_bwd(t, w.norm_w, dy, c.eps, BQ, Dd, dt, G(g.norm_w), G(g.norm_b), c.s));
   TK(dropout_add(nullptr, dt, sc.dbr, (size_t)BQ * Dd, c.p, site_key(c.seed, j, site), c.s));      // d(linear output)
   if (in_site >= 0) { int rc = dropped_input(c, j, in_site, x, K, sc, &x); if (rc) return rc; }
-  TK(lin_bwd_w(sc.dbr, Dd, x, K, BQ, Dd, K, G(g.w), G(g.b), c.s));
-  TK(lin_bwd_x(sc.dbr, Dd, w.w, BQ, Dd, K, dx, false, c.s));
+  TK(lin_bwd_w(sc.dbr, Dd, x, K, BQ, Dd, K, G(g.w), G(g.b), c.mm, c.s));
+  TK(lin_bwd_x(sc.dbr, Dd, w.w, BQ, Dd, K, dx, false, c.mm, c.s));
   return DOD_OK;
 }
 
 // a.out = LN1(a.in + dropout1(out_proj(MHA(a.in)))); tapes a.qkv, a.att, a.t1.  Clobbers sc.Pd, sc.y.
 int self_attn_fwd(const Ctx& c, int j, const AttnW& w, const AttnTape& a, const QScratch& sc) {
   const QDims& d = c.d;
-  TK(lin_fwd(a.in, d.Dd, w.in_w, w.in_b, d.BQ, 3 * d.Dd, d.Dd, a.qkv, 3 * d.Dd, ACT_NONE, c.s));
+  TK(lin_fwd(a.in, d.Dd, w.in_w, w.in_b, d.BQ, 3 * d.Dd, d.Dd, a.qkv, 3 * d.Dd, ACT_NONE, MM_F32, c.s));
   TK(launch_mha_fwd_train(a.qkv, 3 * d.Dd, a.att, d.Dd, sc.Pd, d.B, d.Q, d.Hd, d.Dd, d.dh, c.scale, c.p, site_key(c.seed, j, 0), c.s));
   return postnorm_fwd(c, j, 1, w.post, a.att, d.Dd, a.in, a.t1, a.out, sc.y);
 }
@@ -96,8 +99,8 @@ int self_attn_bwd(const Ctx& c, int j, const AttnW& w, const AttnW& g, const Att
   const QDims& d = c.d;
   int rc = postnorm_bwd(c, j, 1, w.post, g.post, a.t1, a.att, d.Dd, -1, sc.dx, sc.dt, sc.dx, sc); if (rc) return rc;      // dt = d(t1), dx = d(att)
   TK(launch_mha_bwd(a.qkv, 3 * d.Dd, sc.dx, d.Dd, sc.dqkv, sc.dS, sc.Pd, d.B, d.Q, d.Hd, d.Dd, d.dh, c.scale, c.p, site_key(c.seed, j, 0), c.s));
-  TK(lin_bwd_w(sc.dqkv, 3 * d.Dd, a.in, d.Dd, d.BQ, 3 * d.Dd, d.Dd, G(g.in_w), G(g.in_b), c.s));
-  TK(lin_bwd_x(sc.dqkv, 3 * d.Dd, w.in_w, d.BQ, 3 * d.Dd, d.Dd, sc.dt, true, c.s));                                        // dt = d(in): residual + q | k | v input
+  TK(lin_bwd_w(sc.dqkv, 3 * d.Dd, a.in, d.Dd, d.BQ, 3 * d.Dd, d.Dd, G(g.in_w), G(g.in_b), c.mm, c.s));
+  TK(lin_bwd_x(sc.dqkv, 3 * d.Dd, w.in_w, d.BQ, 3 * d.Dd, d.Dd, sc.dt, true, c.mm, c.s));                                        // dt = d(in): residual + q | k | v input
   TH(hipMemcpyAsync(sc.dx, sc.dt, (size_t)d.BQ * d.Dd * 4, hipMemcpyDeviceToDevice, c.s));
   return DOD_OK;
 }
@@ -105,7 +108,7 @@ int self_attn_bwd(const Ctx& c, int j, const AttnW& w, const AttnW& g, const Att
 // out = LN3(f.in + dropout4(linear2(dropout3(relu(linear1(f.in)))))); tapes f.hid (post-ReLU, pre-dropout), f.t3.  Clobbers sc.y, sc.dbig.
 int ffn_fwd(const Ctx& c, int j, const FfnW& w, const FfnTape& f, float* out, const QScratch& sc) {
   const QDims& d = c.d;
-  TK(lin_fwd(f.in, d.Dd, w.lin1_w, w.lin1_b, d.BQ, d.F, d.Dd, f.hid, d.F, ACT_RELU, c.s));
+  TK(lin_fwd(f.in, d.Dd, w.lin1_w, w.lin1_b, d.BQ, d.F, d.Dd, f.hid, d.F, ACT_RELU, MM_F32, c.s));
   const float* hin;
   int rc = dropped_input(c, j, 3, f.hid, d.F, sc, &hin); if (rc) return rc;
   return postnorm_fwd(c, j, 4, w.post, hin, d.F, f.in, f.t3, out, sc.dbig);                                                // dbig: free during the forward
@@ -115,8 +118,8 @@ int ffn_bwd(const Ctx& c, int j, const FfnW& w, const FfnW& g, const FfnTape& f,
   const QDims& d = c.d;
   int rc = postnorm_bwd(c, j, 4, w.post, g.post, f.t3, f.hid, d.F, 3, sc.dx, sc.dt, sc.dbig, sc); if (rc) return rc;       // dt = d(t3), dbig = d(dropped hidden)
   TK(relu_drop_bwd(sc.dbig, f.hid, sc.dbig, (size_t)d.BQ * d.F, c.p, site_key(c.seed, j, 3), c.s));
-  TK(lin_bwd_w(sc.dbig, d.F, f.in, d.Dd, d.BQ, d.F, d.Dd, G(g.lin1_w), G(g.lin1_b), c.s));
-  TK(lin_bwd_x(sc.dbig, d.F, w.lin1_w, d.BQ, d.F, d.Dd, sc.dt, true, c.s));                                               // dt = d(in): residual + FFN input
+  TK(lin_bwd_w(sc.dbig, d.F, f.in, d.Dd, d.BQ, d.F, d.Dd, G(g.lin1_w), G(g.lin1_b), c.mm, c.s));
+  TK(lin_bwd_x(sc.dbig, d.F, w.lin1_w, d.BQ, d.F, d.Dd, sc.dt, true, c.mm, c.s));                                               // dt = d(in): residual + FFN input
   return DOD_OK;
 }
 
@@ -125,7 +128,7 @@ int ffn_bwd(const Ctx& c, int j, const FfnW& w, const FfnW& g, const FfnTape& f,
 int heads_fwd(const Ctx& c, const HeadW& w, int BQ, const float* hs, float* hb, float* boxes, float* det) {
   const int Dd = c.d.Dd, C = c.d.C;
   TK(launch_gemm_f32(hs, Dd, w.class_w, Dd, BQ, C, Dd, gepi(w.class_b, det, C + 4), c.s));
-  TK(lin_fwd(hs, Dd, w.bb0_w, w.bb0_b, BQ, Dd / 2, Dd, hb, Dd / 2, ACT_RELU, c.s));
+  TK(lin_fwd(hs, Dd, w.bb0_w, w.bb0_b, BQ, Dd / 2, Dd, hb, Dd / 2, ACT_RELU, MM_F32, c.s));
   TK(launch_gemm_f32(hb, Dd / 2, w.bb2_w, Dd / 2, BQ, 4, Dd / 2, gepi(w.bb2_b, det + C, C + 4, ACT_SIGMOID), c.s));
   TK(launch_copy2d(det + C, C + 4, boxes, 4, BQ, 4, 4, c.s));
   return DOD_OK;
@@ -134,13 +137,13 @@ int heads_fwd(const Ctx& c, const HeadW& w, int BQ, const float* hs, float* hb, 
 int heads_bwd(const Ctx& c, const HeadW& w, const HeadW& g, int BQ, const float* d_det, const float* hs, const float* hb, const float* boxes, float* dhs, const QScratch& sc) {
   const int Dd = c.d.Dd, C = c.d.C;
   TK(sigmoid_bwd4(d_det + C, C + 4, boxes, 4, sc.dz, BQ, c.s));
-  TK(lin_bwd_w(sc.dz, 4, hb, Dd / 2, BQ, 4, Dd / 2, G(g.bb2_w), G(g.bb2_b), c.s));
-  TK(lin_bwd_x(sc.dz, 4, w.bb2_w, BQ, 4, Dd / 2, sc.dhb, false, c.s));
+  TK(lin_bwd_w(sc.dz, 4, hb, Dd / 2, BQ, 4, Dd / 2, G(g.bb2_w), G(g.bb2_b), c.mm, c.s));
+  TK(lin_bwd_x(sc.dz, 4, w.bb2_w, BQ, 4, Dd / 2, sc.dhb, false, c.mm, c.s));
   TK(relu_drop_bwd(sc.dhb, hb, sc.dhb, (size_t)BQ * (Dd / 2), 0.f, 0ull, c.s));
-  TK(lin_bwd_w(sc.dhb, Dd / 2, hs, Dd, BQ, Dd / 2, Dd, G(g.bb0_w), G(g.bb0_b), c.s));
-  TK(lin_bwd_x(sc.dhb, Dd / 2, w.bb0_w, BQ, Dd / 2, Dd, dhs, false, c.s));
-  TK(lin_bwd_w(d_det, C + 4, hs, Dd, BQ, C, Dd, G(g.class_w), G(g.class_b), c.s));
-  TK(lin_bwd_x(d_det, C + 4, w.class_w, BQ, C, Dd, dhs, true, c.s));
+  TK(lin_bwd_w(sc.dhb, Dd / 2, hs, Dd, BQ, Dd / 2, Dd, G(g.bb0_w), G(g.bb0_b), c.mm, c.s));
+  TK(lin_bwd_x(sc.dhb, Dd / 2, w.bb0_w, BQ, Dd / 2, Dd, dhs, false, c.mm, c.s));
+  TK(lin_bwd_w(d_det, C + 4, hs, Dd, BQ, C, Dd, G(g.class_w), G(g.class_b), c.mm, c.s));
+  TK(lin_bwd_x(d_det, C + 4, w.class_w, BQ, C, Dd, dhs, true, c.mm, c.s));
   return DOD_OK;
 }
 
@@ -213,14 +216,14 @@ int deform_forward(const dod_config* cfg, bool aux, const dod_dec_train_params* 
   const int nh = aux ? d.L : 1;
   Tape t; Scratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
   int rc = entry_check("decoder train", p && memory && det && tape && ws, dropout_p, tape_bytes, carve_tape(d, nh, tape, t) + 256, ws_bytes, carve_scratch(d, nh, ws, sc) + 256); if (rc) return rc;
-  const Ctx c = {d, cfg->dec_ln_eps, dropout_p, 1.0f / sqrtf((float)d.dh), seed, (hipStream_t)stream};
+  const Ctx c = {d, cfg->dec_ln_eps, dropout_p, 1.0f / sqrtf((float)d.dh), seed, (hipStream_t)stream, mm_of(cfg)};
   hipStream_t s = c.s;
   const int BQ = d.BQ, Dd = d.Dd, Q = d.Q;
   const AttnW aw = attn_view(*p);
   const FfnW fw = ffn_view(*p);
   const PostW ow = {p->op_w, p->op_b, p->norm2_w, p->norm2_b};
   rc = build_cat(d, p, sc, s); if (rc) return rc;
-  TK(lin_fwd(memory, Dd, p->vp_w, p->vp_b, d.M, Dd, Dd, t.values, Dd, ACT_NONE, s));                     // tied layers: once
+  TK(lin_fwd(memory, Dd, p->vp_w, p->vp_b, d.M, Dd, Dd, t.values, Dd, ACT_NONE, c.mm, s));                       // tied layers: once.  The B*N memory rows: the step's mode
   TK(launch_bcast_rows(p->query_embed, t.l[0].sa.in, B, Q, Dd, s));
   for (int j = 0; j < d.L; ++j) {
     auto& L = t.l[j];
@@ -243,7 +246,7 @@ int deform_backward(const dod_config* cfg, bool aux, const dod_dec_train_params*
   const int nh = aux ? d.L : 1;
   Tape t; Scratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
   int rc = entry_check("decoder train", p && memory && d_det && tape && grads && ws, 0.f, tape_bytes, carve_tape(d, nh, tape, t) + 256, ws_bytes, carve_scratch(d, nh, ws, sc) + 256); if (rc) return rc;
-  const Ctx c = {d, cfg->dec_ln_eps, dropout_p, 1.0f / sqrtf((float)d.dh), seed, (hipStream_t)stream};
+  const Ctx c = {d, cfg->dec_ln_eps, dropout_p, 1.0f / sqrtf((float)d.dh), seed, (hipStream_t)stream, mm_of(cfg)};
   hipStream_t s = c.s;
   const int BQ = d.BQ, Dd = d.Dd, Q = d.Q, HP = d.Hd * d.P;
   // weights tied: every layer adds into the same gradient tensors
@@ -264,8 +267,8 @@ int deform_backward(const dod_config* cfg, bool aux, const dod_dec_train_params*
     rc = postnorm_bwd(c, j, 2, ow, og, L.t2, L.samp, Dd, -1, sc.dt, sc.dx, sc.dt, sc); if (rc) return rc;
     TH(hipMemsetAsync(sc.dproj, 0, (size_t)BQ * d.ncp * 4, s));
     rc = launch_deform_bwd(L.proj, d.ncp, t.values, sc.dt, B, Q, N, d.Hd, d.P, d.dh, d.fh, d.fw, sc.dproj, sc.dvalues, s); if (rc) return rc;
-    TK(lin_bwd_w(sc.dproj, d.ncp, L.sa.out, Dd, BQ, d.ncat, Dd, sc.dcat_w, sc.dcat_b, s));
-    TK(lin_bwd_x(sc.dproj, d.ncp, sc.cat_w, BQ, d.ncat, Dd, sc.dx, true, s));                                   // dx = d(tgt1)
+    TK(lin_bwd_w(sc.dproj, d.ncp, L.sa.out, Dd, BQ, d.ncat, Dd, sc.dcat_w, sc.dcat_b, c.mm, s));
+    TK(lin_bwd_x(sc.dproj, d.ncp, sc.cat_w, BQ, d.ncat, Dd, sc.dx, true, c.mm, s));                                   // dx = d(tgt1)
     rc = self_attn_bwd(c, j, aw, ag, L.sa, sc); if (rc) return rc;                                              // dx = d(tgt_in)
   }
   TK(batch_sum(sc.dx, G(grads->query_embed), B, (size_t)Q * Dd, s));      // tgt_0[b] = query_embed for every image (detr_decoder.py:59)
@@ -278,8 +281,8 @@ int deform_backward(const dod_config* cfg, bool aux, const dod_dec_train_params*
   TK(add_inplace(G(grads->off_b), dbv + 2, (size_t)HP * 2, s));
   TK(add_inplace(G(grads->aw_b), dbv + 2 + HP * 2, (size_t)HP, s));
   // value projection (computed once for the tied layers: d(values) is the sum over layers)
-  TK(lin_bwd_w(sc.dvalues, Dd, memory, Dd, d.M, Dd, Dd, G(grads->vp_w), G(grads->vp_b), s));
-  if (d_memory) TK(lin_bwd_x(sc.dvalues, Dd, p->vp_w, d.M, Dd, Dd, d_memory, false, s));
+  TK(lin_bwd_w(sc.dvalues, Dd, memory, Dd, d.M, Dd, Dd, G(grads->vp_w), G(grads->vp_b), c.mm, s));
+  if (d_memory) TK(lin_bwd_x(sc.dvalues, Dd, p->vp_w, d.M, Dd, Dd, d_memory, false, c.mm, s));
   return DOD_OK;
 }
 size_t deform_bytes(const dod_config* cfg, bool aux, bool tape, int B, int N) {
@@ -371,7 +374,7 @@ int dod_dense_decoder_train_forward(const dod_config* cfg, const dod_dense_dec_t
   DTape t; DScratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
   int rc = entry_check("dense decoder train", dense_params_ok(p, d.L) && memory && det && tape && ws, dropout_p, tape_bytes, carve_dtape(d, tape, t) + 256, ws_bytes,
                        carve_dscratch(d, ws, sc) + 256); if (rc) return rc;
-  const Ctx c = {d, cfg->dec_ln_eps, dropout_p, 1.0f / sqrtf((float)d.dh), seed, (hipStream_t)stream};
+  const Ctx c = {d, cfg->dec_ln_eps, dropout_p, 1.0f / sqrtf((float)d.dh), seed, (hipStream_t)stream, mm_of(cfg)};
   hipStream_t s = c.s;
   const int BQ = d.BQ, Dd = d.Dd, Q = d.Q;
   TK(launch_bcast_rows(p->query_embed, t.l[0].sa.in, B, Q, Dd, s));
@@ -380,8 +383,8 @@ int dod_dense_decoder_train_forward(const dod_config* cfg, const dod_dense_dec_t
     auto& L = t.l[j];
     rc = self_attn_fwd(c, j, attn_view(W), L.sa, sc); if (rc) return rc;
     // dense cross-attention: q from the queries, k | v from the memory (in_proj rows 0..Dd-1 / Dd..3Dd-1)
-    TK(lin_fwd(L.sa.out, Dd, W.ca_in_w, W.ca_in_b, BQ, Dd, Dd, L.cq, Dd, ACT_NONE, s));
-    TK(lin_fwd(memory, Dd, W.ca_in_w + (size_t)Dd * Dd, W.ca_in_b + Dd, d.M, 2 * Dd, Dd, L.ckv, 2 * Dd, ACT_NONE, s));
+    TK(lin_fwd(L.sa.out, Dd, W.ca_in_w, W.ca_in_b, BQ, Dd, Dd, L.cq, Dd, ACT_NONE, MM_F32, s));
+    TK(lin_fwd(memory, Dd, W.ca_in_w + (size_t)Dd * Dd, W.ca_in_b + Dd, d.M, 2 * Dd, Dd, L.ckv, 2 * Dd, ACT_NONE, c.mm, s));      // the B*N memory rows: the step's mode
     TK(launch_mha_fwd_rect(L.cq, Dd, L.ckv, L.ckv + Dd, 2 * Dd, L.catt, Dd, sc.Pd, B, Q, N, d.Hd, d.dh, c.scale, dropout_p, site_key(seed, j, 5), s));
     rc = postnorm_fwd(c, j, 2, {W.ca_out_w, W.ca_out_b, W.norm2_w, W.norm2_b}, L.catt, Dd, L.sa.out, L.t2, L.ffn.in, sc.y); if (rc) return rc;
     rc = ffn_fwd(c, j, ffn_view(W), L.ffn, j + 1 < d.L ? t.l[j + 1].sa.in : t.hs, sc); if (rc) return rc;
@@ -397,7 +400,7 @@ int dod_dense_decoder_train_backward(const dod_config* cfg, const dod_dense_dec_
   DTape t; DScratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
   int rc = entry_check("dense decoder train", dense_params_ok(p, d.L) && dense_params_ok(grads, d.L) && memory && d_det && tape && ws, 0.f, tape_bytes,
                        carve_dtape(d, tape, t) + 256, ws_bytes, carve_dscratch(d, ws, sc) + 256); if (rc) return rc;
-  const Ctx c = {d, cfg->dec_ln_eps, dropout_p, 1.0f / sqrtf((float)d.dh), seed, (hipStream_t)stream};
+  const Ctx c = {d, cfg->dec_ln_eps, dropout_p, 1.0f / sqrtf((float)d.dh), seed, (hipStream_t)stream, mm_of(cfg)};
   hipStream_t s = c.s;
   const int BQ = d.BQ, Dd = d.Dd, Q = d.Q;
   float* dmem = d_memory ? d_memory : sc.dmem;                 // d(memory): the sum over the layers' k | v projections
@@ -415,10 +418,10 @@ int dod_dense_decoder_train_backward(const dod_config* cfg, const dod_dense_dec_
     TK(launch_mha_bwd_rect(L.cq, Dd, L.ckv, L.ckv + Dd, 2 * Dd, sc.dt, Dd, sc.dcq, Dd, sc.dckv, sc.dckv + Dd, 2 * Dd, sc.dS, sc.Pd, B, Q, N, d.Hd, d.dh,
                            c.scale, dropout_p, site_key(seed, j, 5), s));
     // in_proj of the cross-attention: rows 0..Dd-1 see the queries, rows Dd..3Dd-1 the memory
-    TK(lin_bwd_w(sc.dcq, Dd, L.sa.out, Dd, BQ, Dd, Dd, G(Gw.ca_in_w), G(Gw.ca_in_b), s));
-    TK(lin_bwd_w(sc.dckv, 2 * Dd, memory, Dd, d.M, 2 * Dd, Dd, G(Gw.ca_in_w) + (size_t)Dd * Dd, G(Gw.ca_in_b) + Dd, s));
-    TK(lin_bwd_x(sc.dckv, 2 * Dd, W.ca_in_w + (size_t)Dd * Dd, d.M, 2 * Dd, Dd, dmem, true, s));                // d(memory) += d(k | v) W_kv
-    TK(lin_bwd_x(sc.dcq, Dd, W.ca_in_w, BQ, Dd, Dd, sc.dx, true, s));                                           // dx = d(x1): residual + query input
+    TK(lin_bwd_w(sc.dcq, Dd, L.sa.out, Dd, BQ, Dd, Dd, G(Gw.ca_in_w), G(Gw.ca_in_b), c.mm, s));
+    TK(lin_bwd_w(sc.dckv, 2 * Dd, memory, Dd, d.M, 2 * Dd, Dd, G(Gw.ca_in_w) + (size_t)Dd * Dd, G(Gw.ca_in_b) + Dd, c.mm, s));
+    TK(lin_bwd_x(sc.dckv, 2 * Dd, W.ca_in_w + (size_t)Dd * Dd, d.M, 2 * Dd, Dd, dmem, true, c.mm, s));                // d(memory) += d(k | v) W_kv
+    TK(lin_bwd_x(sc.dcq, Dd, W.ca_in_w, BQ, Dd, Dd, sc.dx, true, c.mm, s));                                           // dx = d(x1): residual + query input
     rc = self_attn_bwd(c, j, attn_view(W), attn_view(Gw), L.sa, sc); if (rc) return rc;                         // dx = d(x_in)
   }
   TK(batch_sum(sc.dx, G(grads->query_embed), B, (size_t)Q * Dd, s));      // x_0[b] = query_embed for every image (detr_decoder.py:59)

@@ -37,10 +37,10 @@ static bool check_common(dod_handle* h, int B, int H, int W, int* rc) {
 }
 
 // ---- test hooks (dod_common.h DOD_OPT_*)
-static std::atomic<int> g_options[DOD_OPT_COUNT] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+static std::atomic<int> g_options[DOD_OPT_COUNT] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
 int dod_option(int which) { return which >= 0 && which < DOD_OPT_COUNT ? g_options[which].load() : -1; }
 static const char* const k_option_names[DOD_OPT_COUNT] = {"tailsplit", "dec_fused_split", "mha_chunk_images", "no_fused_patch", "ln_fold", "deterministic", "f32_ksplit",
-                                                       "attn_bwd_flash", "epi_regmath"};
+                                                       "attn_bwd_flash", "epi_regmath", "f32x3_tile"};
 
 extern "C" {
 
@@ -55,6 +55,8 @@ long dod_test_counter(const char* name) {
   if (name && !strcmp(name, "rem_cuts")) return gemm_rem_cut_count();
   if (name && !strcmp(name, "f32_ksplits")) return gemm_f32_ksplit_count();
   if (name && !strcmp(name, "epi_regmath")) return gemm_epi_regmath_count();
+  if (name && !strcmp(name, "f32x3_launches")) return gemm_f32x3_count(0);
+  if (name && !strcmp(name, "f32x3_wide_launches")) return gemm_f32x3_count(1);
   if (name && !strcmp(name, "optim_launches")) return optim_launch_count();
   if (name && !strcmp(name, "optim_chunk_elems")) return optim_constant(0);
   if (name && !strcmp(name, "optim_table_tensors")) return optim_constant(1);
@@ -305,6 +307,26 @@ int dod_op_gemm_f32x(const float* A, int lda, int a_kmajor, long long a_sb, long
   g.C = C; g.ldc = ldc; g.c_sb = c_sb; g.c_sh = c_sh;
   g.M = M; g.N = N; g.K = K; g.batch = batch; g.hb = hb; g.alpha = alpha; g.accumulate = accumulate; g.ksplit = ksplit;
   return rejected(nullptr, launch_gemm_f32x(g, (hipStream_t)stream), "dod_op_gemm_f32x M=%d N=%d K=%d batch=%d", M, N, K, batch);
+}
+int dod_op_gemm_f32x3(const float* A, int lda, int a_kmajor, long long a_sb, long long a_sh, const float* W, int ldw, int w_kmajor, long long w_sb,
+                      long long w_sh, float* C, int ldc, long long c_sb, long long c_sh, int M, int N, int K, int batch, int hb, float alpha,
+                      int accumulate, int ksplit, void* stream) {
+  if (!A || !W || !C) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
+  GemmF32X g; memset(&g, 0, sizeof g);
+  g.A = A; g.lda = lda; g.a_kmajor = a_kmajor; g.a_sb = a_sb; g.a_sh = a_sh;
+  g.W = W; g.ldw = ldw; g.w_kmajor = w_kmajor; g.w_sb = w_sb; g.w_sh = w_sh;
+  g.C = C; g.ldc = ldc; g.c_sb = c_sb; g.c_sh = c_sh;
+  g.M = M; g.N = N; g.K = K; g.batch = batch; g.hb = hb; g.alpha = alpha; g.accumulate = accumulate; g.ksplit = ksplit;
+  return rejected(nullptr, launch_gemm_f32x3(g, (hipStream_t)stream), "dod_op_gemm_f32x3 M=%d N=%d K=%d batch=%d", M, N, K, batch);
+}
+int dod_op_linear_f32x3(const float* X, int ldx, const float* W, const float* bias, const float* scale, const float* resid, int ldr, int M, int N, int K,
+                        float* Y, int ldy, int act, void* stream) {
+  if (!X || !W || !Y) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
+  if (act < DOD_ACT_NONE || act > DOD_ACT_SIGMOID) return fail(nullptr, DOD_ERR_INVALID, "dod_op_linear_f32x3: activation %d", act);
+  GemmF32X g; memset(&g, 0, sizeof g);
+  g.A = X; g.lda = ldx; g.W = W; g.ldw = K; g.C = Y; g.ldc = ldy; g.M = M; g.N = N; g.K = K; g.batch = 1; g.hb = 1; g.alpha = 1.0f; g.ksplit = 1;
+  g.bias = bias; g.scale = scale; g.resid = resid; g.ldr = ldr; g.act = act;
+  return rejected(nullptr, launch_gemm_f32x3(g, (hipStream_t)stream), "dod_op_linear_f32x3 M=%d N=%d K=%d", M, N, K);
 }
 int dod_op_linear_fp8(const void* A, int lda, const float* a_scale, const void* W, int ldw, const float* w_scale, int M, int N, int K,
                       const float* bias, const float* scale, const float* resid, int ldr, void* out, int out_dtype, int ldc, int act,

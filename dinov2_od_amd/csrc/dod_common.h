@@ -28,6 +28,7 @@ enum { DOD_OPT_TAILSPLIT = 0,         // GEMM wave-quantisation tail split: 0 of
        DOD_OPT_F32_KSPLIT,            // fp32 GEMM K split across workgroups (gemm_f32.hip): 0 = never, 1 = also for the operator dod_op_linear
        DOD_OPT_ATTN_BWD_FLASH,        // backbone-tail attention adjoint (tail_train.hip tail_flash_bwd): 0 = never the flash form, 1 = whenever head_dim is 64
        DOD_OPT_EPI_REGMATH,           // 16-wave bf16 GEMM, plain bf16 rows (gemm_x3.hip): 0 = the LDS-staged epilogue, 1 = epilogue math on the accumulators (shipped)
+       DOD_OPT_F32X3_TILE,            // fp32-in bf16 split GEMM (gemm_f32x3.hip): 64 / 128 = that tile for every product (0 = the shipped rule)
        DOD_OPT_COUNT };
 int dod_option(int which);            // dod_api.hip; -1 when unset
 long gemm_tail_split_count();         // gemm_pp.hip: GEMM calls that took the tail-split path so far
@@ -223,9 +224,12 @@ long gemm_f32_ksplit_count();
 // The same exact-fp32 MFMA main loop for the training step's products (train_ops.hip): either operand may be given k-major
 // ([K, rows]: the transposed products of a backward need no transposed copies), a two-level batch (image, head) walks strided views
 // (attention scores / context / their adjoints as batched GEMMs), the K range may be split over grid.z with an atomic accumulate.
-//   C[z] (+)= alpha * A[z] W[z]^T (+ bias, activation);   z = zb * hb + zh,  X[z] = X + zb * x_sb + zh * x_sh   (strides in floats)
+//   C[z] (+)= act(alpha * A[z] W[z]^T + bias) (* scale[n]) (+ resid);   z = zb * hb + zh,  X[z] = X + zb * x_sb + zh * x_sh   (strides in floats)
 struct GemmF32X {
   const float* A; const float* W; float* C; const float* bias;
+  const float* scale;       // [N] LayerScale lambda or null
+  const float* resid;       // [M, ldr] or null (same for every z; not with ksplit > 1, like scale)
+  int ldr;
   int lda, ldw, ldc, M, N, K;
   long long a_sb, a_sh, w_sb, w_sh, c_sb, c_sh;
   int batch, hb;            // batch = number of z, hb = inner (head) count; 1, 1 for a plain product
@@ -236,6 +240,11 @@ struct GemmF32X {
   int ksplit;               // > 1: K split over grid.z, partial products added atomically (implies accumulate; C must hold the addend)
 };
 int launch_gemm_f32x(const GemmF32X& g, hipStream_t s);
+// The same contract on the bf16 cores (gemm_f32x3.hip): both fp32 operands are split x = h + l (h = bf16_rne(x), l = bf16_rne(x - h), the
+// definition of dod_op_split_pair) on their way into LDS and C = alpha (Ah Wh^T + Ah Wl^T + Al Wh^T), accumulated in fp32 on
+// v_mfma_f32_32x32x16_bf16 -- the arithmetic of the bf16x3 forward mode for the training step's products (DOD_PREC_BF16X3 in a training config).
+int launch_gemm_f32x3(const GemmF32X& g, hipStream_t s);
+long gemm_f32x3_count(int wide);      // launches so far: all (0) / those that took the 128x128 tile (1)
 // fp8 (OCP e4m3) operands, one byte per element, K contiguous; e.a_scale / e.w_scale are the dequant scales
 // (e.a_bs instead of e.a_scale: block-scaled activations, K % 256 == 0)
 int launch_quant_mx_fp8(const void* x, int in_bf16, int ld, int rows, int cols, unsigned char* q, int ldq, unsigned char* bs, hipStream_t s);

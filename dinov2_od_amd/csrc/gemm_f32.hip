@@ -15,6 +15,7 @@
 // k-tiles per LDS stage and barrier -- a lone workgroup's k-tile takes ~1 us whatever is in flight behind it, co-resident
 // workgroups are what overlap it.
 #include "dod_common.h"
+#include "gemm_f32x_epi.h"
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -288,8 +289,7 @@ int launch_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int
 template <bool AKM, bool WKM, bool VEC>
 __global__ __launch_bounds__(256) void gemm_f32x_kernel(GemmF32X g) {
   __shared__ __attribute__((aligned(16))) float f32_smem[4 * FBK * FLD];     // sA[2] | sW[2]; the split-K epilogue's [64][65] tile
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid >> 1, wn = wid & 1;
+  const int tid = threadIdx.x;
   const int tiles_m = (g.M + FBM - 1) / FBM;
   const int tn = blockIdx.x / tiles_m, tm = blockIdx.x - tn * tiles_m;
   const int m0 = tm * FBM, n0 = tn * FBN;
@@ -312,43 +312,9 @@ __global__ __launch_bounds__(256) void gemm_f32x_kernel(GemmF32X g) {
   f32_mainloop(la, lw, kt0, kt1, reinterpret_cast<float (*)[FBK * FLD]>(f32_smem),
                reinterpret_cast<float (*)[FBK * FLD]>(f32_smem + 2 * FBK * FLD), acc);
 
-  const int lr = lane & 31, lh = lane >> 5;
   float* cz = g.C + zb * g.c_sb + zh * g.c_sh;
-  if (g.ksplit > 1) {
-    // atomic accumulate of the slice's partial tile, staged through LDS so that one wave instruction covers 64 consecutive
-    // columns of one row (a lane-owns-a-row scatter of 4-byte atomics ran at ~40 per ns: 80 us for a 384 x 768 gradient)
-    __syncthreads();                                   // every wave is done reading the last stage
-    float* T = f32_smem;                               // [64][65]
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) T[(wm * 32 + lr) * 65 + wn * 32 + 8 * q + 4 * lh + t] = acc[4 * q + t] * g.alpha;
-    __syncthreads();
-    const int n = n0 + lane;
-    const float bv = (g.bias && blockIdx.z == 0 && n < g.N) ? g.bias[n] : 0.f;
-    for (int rr = 0; rr < 16; ++rr) {
-      const int row = wid * 16 + rr, m = m0 + row;
-      if (m < g.M && n < g.N) unsafeAtomicAdd(cz + (size_t)m * g.ldc + n, T[row * 65 + lane] + bv);
-    }
-    return;
-  }
-  const int m = m0 + wm * 32 + lr;
-  if (m >= g.M) return;
-  float* crow = cz + (size_t)m * g.ldc;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int n = n0 + wn * 32 + 8 * q + 4 * lh + t;
-      if (n >= g.N) continue;
-      float v = acc[4 * q + t] * g.alpha;
-      if (g.bias) v += g.bias[n];
-      if (g.act == ACT_GELU) v = gelu_erf(v);
-      else if (g.act == ACT_RELU) v = fmaxf(v, 0.f);
-      else if (g.act == ACT_SIGMOID) v = sigmoidf_(v);
-      crow[n] = g.accumulate ? crow[n] + v : v;
-    }
-  }
+  if (g.ksplit > 1) f32x_epi_atomic(g, cz, m0, n0, acc, f32_smem, blockIdx.z == 0);      // gemm_f32x_epi.h: shared with gemm_f32x3.hip
+  else f32x_epi_direct(g, cz, m0, n0, acc);
 }
 
 int launch_gemm_f32x(const GemmF32X& g_, hipStream_t s) {
@@ -358,7 +324,7 @@ int launch_gemm_f32x(const GemmF32X& g_, hipStream_t s) {
   if (g.hb < 1) g.hb = 1;
   if (g.batch % g.hb || g.batch > 65535) return 2;
   if (g.ksplit < 1) g.ksplit = 1;
-  if (g.ksplit > 1 && g.act != ACT_NONE) return 2;
+  if (g.ksplit > 1 && (g.act != ACT_NONE || g.scale || g.resid)) return 2;
   const int nkt = (g.K + FBK - 1) / FBK;
   if (g.ksplit > nkt) g.ksplit = nkt;
   const int tiles = ((g.M + FBM - 1) / FBM) * ((g.N + FBN - 1) / FBN);

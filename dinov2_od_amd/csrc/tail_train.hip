@@ -6,7 +6,7 @@
 // fc1 / fc2 slots of dod_bb_block_params then hold mlp.weights_in [2F, D] / mlp.weights_out [D, F]).
 //   forward : x -> LN1 -> q|k|v (W' = W + alpha B A, merged in fp32 as the eval path does) -> softmax(q k^T / sqrt(dh)) v -> dense
 //             -> x + ls1 * . -> LN2 -> fc1 -> GELU(erf) -> fc2 -> + ls2 * .  ->  final LN -> projection
-//   backward: dX = dY W' on the fp32 MFMA GEMM; per LoRA linear  dB += alpha dY^T (X A^T),  dA += alpha (dY B)^T X  (rank-r GEMMs);
+//   backward: dX = dY W' on the fp32 MFMA GEMM (the bf16 split GEMM under DOD_PREC_BF16X3, like every linear here: train_internal.h Mm); per LoRA linear  dB += alpha dY^T (X A^T),  dA += alpha (dY B)^T X  (rank-r GEMMs);
 //             attention backward = the row / column passes of the decoder's self-attention with Q := N tokens.
 // Schedule only: the kernels and their launchers are in train_ops.hip, attn_f32m.hip and gemm_f32.hip.
 #include "train_internal.h"
@@ -93,6 +93,7 @@ int dod_backbone_tail_train_forward(const dod_config* cfg, const dod_bb_tail_par
   int rc = entry_check("backbone tail", x_in && mem_out && tape && ws, 0.f, tape_bytes, carve_ttape(d, tape, t) + 256, ws_bytes, carve_tscratch(d, ws, sc) + 256); if (rc) return rc;
   if (cfg->target_dim && (!p->proj_w || !p->proj_b)) return tfail(DOD_ERR_MISSING, "backbone tail: projection weights missing");
   hipStream_t s = (hipStream_t)stream;
+  const Mm mm = mm_of(cfg);      // DOD_PREC_BF16X3: every linear of the tail, forward and backward, as a bf16 split product (attention, LoRA rank-r products and LayerNorm stay)
   const int M = d.M, D = d.D, F = d.F, F1 = d.F1;
   const float scale = 1.0f / sqrtf((float)d.dh);
   TH(hipMemcpyAsync(t.b[0].x, x_in, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
@@ -109,30 +110,24 @@ int dod_backbone_tail_train_forward(const dod_config* cfg, const dod_bb_tail_par
     TK(launch_lora_merge(bp.fc1.w, bp.fc1.A, bp.fc1.Bm, d.alpha, F1, D, d.r, tb.W1, s));
     TK(launch_lora_merge(bp.fc2.w, bp.fc2.A, bp.fc2.Bm, d.alpha, D, F, d.r, tb.W2, s));
     TK(launch_layernorm(tb.x, nullptr, bp.ln1_w, bp.ln1_b, d.eps, M, D, ln_out(tb.y1), s));
-    TK(lin_fwd(tb.y1, D, tb.Wqkv, tb.bqkv, M, 3 * D, D, tb.qkv, 3 * D, ACT_NONE, s));
+    TK(lin_fwd(tb.y1, D, tb.Wqkv, tb.bqkv, M, 3 * D, D, tb.qkv, 3 * D, ACT_NONE, mm, s));
     {
       AttnF32 a; a.q = tb.qkv; a.k = tb.qkv + D; a.v = tb.qkv + 2 * D; a.o = tb.ctx; a.ldq = a.ldk = a.ldv = 3 * D; a.ldo = D;
       a.Lq = a.Lk = N; a.B = B; a.heads = d.H; a.dh = d.dh; a.scale = scale;
       if (d.dh == 64) a.lse = tb.lse;            // fp32-MFMA flash kernel: the adjoint's log-sum-exp comes for free
       TK(launch_attn_f32(a, s));
     }
-    {   // x1 = x + ls1 * (ctx Wo'^T + bo)
-      GemmEpi e = gepi(bp.o.b, tb.x1, D, ACT_NONE, tb.x, D); e.scale = bp.ls1;
-      TK(launch_gemm_f32(tb.ctx, D, tb.Wo, D, M, D, D, e, s));
-    }
+    TK(lin_fwd(tb.ctx, D, tb.Wo, bp.o.b, M, D, D, tb.x1, D, ACT_NONE, mm, s, bp.ls1, tb.x, D));      // x1 = x + ls1 * (ctx Wo'^T + bo)
     TK(launch_layernorm(tb.x1, nullptr, bp.ln2_w, bp.ln2_b, d.eps, M, D, ln_out(tb.y2), s));
-    TK(lin_fwd(tb.y2, D, tb.W1, bp.fc1.b, M, F1, D, tb.pre, F1, ACT_NONE, s));      // taped: the backward needs the pre-activation
+    TK(lin_fwd(tb.y2, D, tb.W1, bp.fc1.b, M, F1, D, tb.pre, F1, ACT_NONE, mm, s));      // taped: the backward needs the pre-activation
     if (d.swiglu) TK(swiglu_fwd(tb.pre, tb.h, (size_t)M, F, s));      // fc1 / fc2 = weights_in / weights_out
     else TK(gelu_fwd(tb.pre, tb.h, (size_t)M * F, s));
     float* xnext = i + 1 < d.nb ? t.b[i + 1].x : t.xout;
-    {
-      GemmEpi e = gepi(bp.fc2.b, xnext, D, ACT_NONE, tb.x1, D); e.scale = bp.ls2;
-      TK(launch_gemm_f32(tb.h, F, tb.W2, F, M, D, F, e, s));
-    }
+    TK(lin_fwd(tb.h, F, tb.W2, bp.fc2.b, M, D, F, xnext, D, ACT_NONE, mm, s, bp.ls2, tb.x1, D));     // x2 = x1 + ls2 * (h W2'^T + b2)
   }
   if (cfg->target_dim) {
     TK(launch_layernorm(t.xout, nullptr, p->lnf_w, p->lnf_b, d.eps, M, D, ln_out(t.f), s));
-    TK(lin_fwd(t.f, D, p->proj_w, p->proj_b, M, d.Dd, D, mem_out, d.Dd, ACT_NONE, s));
+    TK(lin_fwd(t.f, D, p->proj_w, p->proj_b, M, d.Dd, D, mem_out, d.Dd, ACT_NONE, mm, s));
   } else {
     TK(launch_layernorm(t.xout, nullptr, p->lnf_w, p->lnf_b, d.eps, M, D, ln_out(mem_out), s));
   }
@@ -147,14 +142,15 @@ int dod_backbone_tail_train_backward(const dod_config* cfg, const dod_bb_tail_pa
   TTape t; TScratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
   int rc = entry_check("backbone tail", d_mem && tape && ws, 0.f, tape_bytes, carve_ttape(d, tape, t) + 256, ws_bytes, carve_tscratch(d, ws, sc) + 256); if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
+  const Mm mm = mm_of(cfg);
   auto G = [](const float* q) { return const_cast<float*>(q); };
   const int M = d.M, D = d.D, F = d.F, F1 = d.F1;
   const size_t nMD = (size_t)M * D;
   const float scale = 1.0f / sqrtf((float)d.dh);
   // ---- projection + final LayerNorm (frozen affine: its parameter gradients go to a dump)
   if (cfg->target_dim) {
-    TK(lin_bwd_w(d_mem, d.Dd, t.f, D, M, d.Dd, D, G(grads->proj_w), G(grads->proj_b), s));
-    TK(lin_bwd_x(d_mem, d.Dd, p->proj_w, M, d.Dd, D, sc.da, false, s));
+    TK(lin_bwd_w(d_mem, d.Dd, t.f, D, M, d.Dd, D, G(grads->proj_w), G(grads->proj_b), mm, s));
+    TK(lin_bwd_x(d_mem, d.Dd, p->proj_w, M, d.Dd, D, sc.da, false, mm, s));
     TK(ln_bwd(t.xout, p->lnf_w, sc.da, d.eps, M, D, sc.dx, sc.dump, sc.dump + D, s));
   } else {
     TK(ln_bwd(t.xout, p->lnf_w, d_mem, d.eps, M, D, sc.dx, sc.dump, sc.dump + D, s));
@@ -168,20 +164,20 @@ int dod_backbone_tail_train_backward(const dod_config* cfg, const dod_bb_tail_pa
     TK(colscale(sc.dx, bp.ls2, sc.da, nMD, D, s));                                                                        // da = d(fc2 out)
     TK(lora_grads(tb.h, F, sc.da, D, D, bp.fc2.A, bp.fc2.Bm, M, d.r, d.alpha, G(gp.fc2.A), G(gp.fc2.Bm), sc.T, sc.U, s));
     if (d.swiglu) {     // d(h) [M, F], then d(pre) = [d(x1) | d(x2)] in dbig
-      TK(lin_bwd_x(sc.da, D, tb.W2, M, D, F, sc.dh, false, s));
+      TK(lin_bwd_x(sc.da, D, tb.W2, M, D, F, sc.dh, false, mm, s));
       TK(swiglu_bwd(sc.dh, tb.pre, sc.dbig, (size_t)M, F, s));
     } else {
-      TK(lin_bwd_x(sc.da, D, tb.W2, M, D, F, sc.dbig, false, s));                                                     // d(h)
+      TK(lin_bwd_x(sc.da, D, tb.W2, M, D, F, sc.dbig, false, mm, s));                                                     // d(h)
       TK(gelu_bwd(sc.dbig, tb.pre, sc.dbig, (size_t)M * F, s));
     }
     TK(lora_grads(tb.y2, D, sc.dbig, F1, F1, bp.fc1.A, bp.fc1.Bm, M, d.r, d.alpha, G(gp.fc1.A), G(gp.fc1.Bm), sc.T, sc.U, s));
-    TK(lin_bwd_x(sc.dbig, F1, tb.W1, M, F1, D, sc.da, false, s));                                                     // d(y2)
+    TK(lin_bwd_x(sc.dbig, F1, tb.W1, M, F1, D, sc.da, false, mm, s));                                                     // d(y2)
     TK(ln_bwd(tb.x1, bp.ln2_w, sc.da, d.eps, M, D, sc.db, sc.dump, sc.dump + D, s));
     TK(add_inplace(sc.dx, sc.db, nMD, s));                                                                                // dx = d(x1)
     // x1 = x + ls1 * (ctx Wo'^T + bo)
     TK(colscale(sc.dx, bp.ls1, sc.da, nMD, D, s));
     TK(lora_grads(tb.ctx, D, sc.da, D, D, bp.o.A, bp.o.Bm, M, d.r, d.alpha, G(gp.o.A), G(gp.o.Bm), sc.T, sc.U, s));
-    TK(lin_bwd_x(sc.da, D, tb.Wo, M, D, D, sc.db, false, s));                                                         // db = d(ctx)
+    TK(lin_bwd_x(sc.da, D, tb.Wo, M, D, D, sc.db, false, mm, s));                                                         // db = d(ctx)
     if (tail_flash_bwd(d)) {
       AttnF32Bwd g;
       g.q = tb.qkv; g.k = tb.qkv + D; g.v = tb.qkv + 2 * D; g.o = tb.ctx; g.d_o = sc.db; g.lse = tb.lse;
@@ -197,7 +193,7 @@ int dod_backbone_tail_train_backward(const dod_config* cfg, const dod_bb_tail_pa
     for (int c = 0; c < 3; ++c)
       TK(lora_grads(tb.y1, D, sc.dqkv + (size_t)c * D, 3 * D, D, qkv3[c]->A, qkv3[c]->Bm, M, d.r, d.alpha, G(gqkv3[c]->A), G(gqkv3[c]->Bm), sc.T, sc.U, s));
     if (i > 0) {        // the tail's input is the frozen prefix's output: nothing below block 0 needs a gradient
-      TK(lin_bwd_x(sc.dqkv, 3 * D, tb.Wqkv, M, 3 * D, D, sc.da, false, s));                                           // d(y1)
+      TK(lin_bwd_x(sc.dqkv, 3 * D, tb.Wqkv, M, 3 * D, D, sc.da, false, mm, s));                                           // d(y1)
       TK(ln_bwd(tb.x, bp.ln1_w, sc.da, d.eps, M, D, sc.db, sc.dump, sc.dump + D, s));
       TK(add_inplace(sc.dx, sc.db, nMD, s));                                                                              // dx = d(x): the block below's output
     }

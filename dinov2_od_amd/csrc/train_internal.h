@@ -72,10 +72,18 @@ inline GemmF32X xgemm(const float* A, int lda, bool a_km, const float* W, int ld
 }
 
 // ------------------------------------------------------------------------------------------------ launchers (train_ops.hip)
-// fp32 linears.  Y[M,N] = act(X[M,K] W[N,K]^T + b), never K-split;  dX[M,K] (+)= dY[M,N] W[N,K];  dW[N,K] += dY^T X, db[N] += colsum(dY)
-int lin_fwd(const float* X, int ldx, const float* W, const float* b, int M, int N, int K, float* Y, int ldy, int act, hipStream_t s);
-int lin_bwd_x(const float* dY, int ldy, const float* W, int M, int N, int K, float* dX, bool accumulate, hipStream_t s);
-int lin_bwd_w(const float* dY, int ldy, const float* X, int ldx, int M, int N, int K, float* dW, float* db, hipStream_t s);
+// The arithmetic of a linear's product: the exact-fp32 MFMA kernels (gemm_f32.hip), or -- DOD_PREC_BF16X3 in the step's configuration -- the
+// bf16 split product on fp32 operands (gemm_f32x3.hip: same operands, tape and scratch; a few 1e-6 from the exact product).  An ARGUMENT of every
+// linear, taken from the configuration each entry point is given: forward and backward of one step run on different threads, and two models of
+// one process may train in different modes -- nothing thread-local or global could carry it.
+enum Mm { MM_F32 = 0, MM_X3 = 1 };
+inline Mm mm_of(const dod_config* c) { return c && c->precision == DOD_PREC_BF16X3 ? MM_X3 : MM_F32; }
+// Linears.  Y[M,N] = act(X[M,K] W[N,K]^T + b) (* scale[n]) (+ resid[M, ldr]), never K-split;  dX[M,K] (+)= dY[M,N] W[N,K];
+// dW[N,K] += dY^T X, db[N] += colsum(dY)
+int lin_fwd(const float* X, int ldx, const float* W, const float* b, int M, int N, int K, float* Y, int ldy, int act, Mm mm, hipStream_t s,
+            const float* scale = nullptr, const float* resid = nullptr, int ldr = 0);
+int lin_bwd_x(const float* dY, int ldy, const float* W, int M, int N, int K, float* dX, bool accumulate, Mm mm, hipStream_t s);
+int lin_bwd_w(const float* dY, int ldy, const float* X, int ldx, int M, int N, int K, float* dW, float* db, Mm mm, hipStream_t s);
 // pointwise: each wrapper owns its kernel's grid formula
 int colsum_add(const float* src, int ld, int rows, int cols, float* dst, hipStream_t s);                                         // dst[c] += sum_r src[r][c]
 int dropout_add(const float* a, const float* b, float* out, size_t n, float p, unsigned long long key, hipStream_t s);            // out = a + keep(b) / (1 - p); a may be null

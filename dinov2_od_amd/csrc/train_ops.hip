@@ -591,43 +591,50 @@ int launch_deform_bwd(const float* proj, int ldp, const float* values, const flo
   return DOD_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ fp32 linears
+// ------------------------------------------------------------------------------------------------ linears
 // K slices for a product whose 64x64 tiles leave most of the chip idle (the decoder's 1 600-row linears: 300 tiles, a lone
-// workgroup's 16-k tile takes ~1 us): target ~768 workgroups of at least 8 k-tiles each; 1 = do not split
-int ksplit_for(int rows, int cols, int K) {
+// workgroup's 16-k tile takes ~1 us): target ~768 workgroups of at least 8 k-tiles each; 1 = do not split.  The split kernel's k-tile is 32.
+int ksplit_for(int rows, int cols, int K, Mm mm) {
   if (det_mode()) return 1;      // one workgroup owns an output tile: no atomic merge of K slices
   static const int target = [] { const char* e = DOD_TUNE_ENV("DINODET_F32_KSPLIT_WGS"); return e && atoi(e) > 0 ? atoi(e) : 768; }();
-  const int tiles = ((rows + 63) / 64) * ((cols + 63) / 64), nkt = (K + 15) / 16;
+  const int tiles = ((rows + 63) / 64) * ((cols + 63) / 64), nkt = mm == MM_X3 ? (K + 31) / 32 : (K + 15) / 16;
   if (tiles >= target) return 1;
   int ks = (target + tiles - 1) / tiles;
   const int cap = nkt / 8 > 1 ? nkt / 8 : 1;
   return ks > cap ? cap : ks;
 }
-// Y[M,N] = act(X[M,K] W[N,K]^T + b).  Never K-split: the forward stays a bit-reproducible function of (inputs, seed).
-int lin_fwd(const float* X, int ldx, const float* W, const float* b, int M, int N, int K, float* Y, int ldy, int act, hipStream_t s) {
-  return launch_gemm_f32(X, ldx, W, K, M, N, K, gepi(b, Y, ldy, act), s);
+inline int xlaunch(const GemmF32X& g, Mm mm, hipStream_t s) { return mm == MM_X3 ? launch_gemm_f32x3(g, s) : launch_gemm_f32x(g, s); }
+// Y[M,N] = act(X[M,K] W[N,K]^T + b) (* scale) (+ resid).  Never K-split: the forward stays a bit-reproducible function of (inputs, seed).
+int lin_fwd(const float* X, int ldx, const float* W, const float* b, int M, int N, int K, float* Y, int ldy, int act, Mm mm, hipStream_t s,
+            const float* scale, const float* resid, int ldr) {
+  if (mm == MM_X3) {
+    GemmF32X g = xgemm(X, ldx, false, W, K, false, Y, ldy, M, N, K, 1.0f, false);
+    g.bias = b; g.act = act; g.scale = scale; g.resid = resid; g.ldr = ldr;
+    return launch_gemm_f32x3(g, s);
+  }
+  GemmEpi e = gepi(b, Y, ldy, act, resid, ldr); e.scale = scale;
+  return launch_gemm_f32(X, ldx, W, K, M, N, K, e, s);
 }
 // dX[M,K] (+)= dY[M,N] W[N,K]: W [N, K] is the k-major operand of the product over n
-int lin_bwd_x(const float* dY, int ldy, const float* W, int M, int N, int K, float* dX, bool accumulate, hipStream_t s) {
+int lin_bwd_x(const float* dY, int ldy, const float* W, int M, int N, int K, float* dX, bool accumulate, Mm mm, hipStream_t s) {
   GemmF32X g = xgemm(dY, ldy, false, W, K, true, dX, K, M, K, N, 1.0f, accumulate);
-  g.ksplit = ksplit_for(M, K, N);
+  g.ksplit = ksplit_for(M, K, N, mm);
   if (g.ksplit > 1 && !accumulate) {
     if (hipMemsetAsync(dX, 0, (size_t)M * K * 4, s) != hipSuccess) return 3;
     g.accumulate = 1;
   }
-  return launch_gemm_f32x(g, s);
+  return xlaunch(g, mm, s);
 }
 // C[R,Cc] += alpha * Y[M,R]^T X[M,Cc]: both operands k-major over the M rows.  A small output (weight gradients: a few dozen to
 // a few hundred tiles against a reduction over thousands of rows) splits the rows over grid.z and accumulates atomically.
-int gemm_tn_acc(const float* Y, int ldy, const float* X, int ldx, int M, int R, int Cc, float* C, int ldc, float alpha, hipStream_t s) {
+int gemm_tn_acc(const float* Y, int ldy, const float* X, int ldx, int M, int R, int Cc, float* C, int ldc, float alpha, Mm mm, hipStream_t s) {
   GemmF32X g = xgemm(Y, ldy, true, X, ldx, true, C, ldc, R, Cc, M, alpha, true);
-  const int ks = ksplit_for(R, Cc, M);
-  g.ksplit = ks;
-  return launch_gemm_f32x(g, s);
+  g.ksplit = ksplit_for(R, Cc, M, mm);
+  return xlaunch(g, mm, s);
 }
 // dW[N,K] += dY[M,N]^T X[M,K];  db[N] += colsum(dY)
-int lin_bwd_w(const float* dY, int ldy, const float* X, int ldx, int M, int N, int K, float* dW, float* db, hipStream_t s) {
-  int r = gemm_tn_acc(dY, ldy, X, ldx, M, N, K, dW, K, 1.0f, s);
+int lin_bwd_w(const float* dY, int ldy, const float* X, int ldx, int M, int N, int K, float* dW, float* db, Mm mm, hipStream_t s) {
+  int r = gemm_tn_acc(dY, ldy, X, ldx, M, N, K, dW, K, 1.0f, mm, s);
   if (r) return r;
   return db ? colsum_add(dY, ldy, M, N, db, s) : 0;
 }
@@ -714,9 +721,9 @@ int lora_grads(const float* X, int in_f, const float* dY, int ldy, int out_f, co
     return lora_up(X, in_f, U, rp, M, in_f, r, dA, 1, in_f, s);                                       // dA += U^T X
   }
   rc = launch_gemm_f32x(xgemm(X, in_f, false, A, in_f, false, T, rp, M, r, in_f, alpha, false), s); if (rc) return rc;
-  rc = gemm_tn_acc(dY, ldy, T, rp, M, out_f, r, dB, r, 1.0f, s); if (rc) return rc;
+  rc = gemm_tn_acc(dY, ldy, T, rp, M, out_f, r, dB, r, 1.0f, MM_F32, s); if (rc) return rc;
   rc = launch_gemm_f32x(xgemm(dY, ldy, false, Bm, r, true, U, rp, M, r, out_f, alpha, false), s); if (rc) return rc;
-  return gemm_tn_acc(U, rp, X, in_f, M, r, in_f, dA, in_f, 1.0f, s);
+  return gemm_tn_acc(U, rp, X, in_f, M, r, in_f, dA, in_f, 1.0f, MM_F32, s);
 }
 
 }  // namespace dtrain

@@ -20,6 +20,18 @@ def default_precision():
     return os.environ.get("DINODET_PRECISION", "bf16x3")
 
 
+# What the native training steps can run their linears on (include/dinodet.h "training precision"): exact fp32, or the bf16 split product
+# on the fp32 operands (csrc/gemm_f32x3.hip).  The autograd composite that stands in where a native step does not take a configuration is
+# fp32 whatever this says.
+TRAIN_PRECISIONS = ("fp32", "bf16x3")
+
+
+def check_train_precision(value):
+    if value not in TRAIN_PRECISIONS:
+        raise ValueError(f"train_precision must be 'fp32' or 'bf16x3', got {value!r}")
+    return value
+
+
 def make_config(bb: BackboneConfig, dc: DecoderConfig, precision: str) -> nat.DodConfig:
     if precision not in nat.PREC:
         raise ValueError(f"precision must be one of {sorted(nat.PREC)}, got {precision!r}")

@@ -14,9 +14,14 @@ import ctypes as C
 import torch
 
 from .. import _native as nat
-from ..engine import make_config
+from ..engine import check_train_precision, make_config
 
 _seed_counter = [0]
+
+def train_config(m, bb, dc):
+    """the dod_config every native training entry point (the size queries behind supported() / tail_supported() / dense_supported()
+    included) is given: the module's shapes with its `train_precision` -- NOT its `precision`, which governs eval() and the frozen prefix"""
+    return make_config(bb, dc, check_train_precision(getattr(m, "train_precision", "fp32")))
 
 
 def _param_list(m):
@@ -53,7 +58,7 @@ def supported(m, src):
     if not all(p.is_cuda and p.dtype == torch.float32 for p in _param_list(m)) or src.dim() != 3 or dropout_rate(m) is None:
         return False
     # the shape limits are the native side's own (make_dims in dec_train.hip): 0 bytes = not taken -> the composite runs instead
-    cfg = make_config(m._bb_cfg, m._dc_cfg, "fp32")
+    cfg = train_config(m, m._bb_cfg, m._dc_cfg)
     return nat.lib().dod_decoder_train_tape_bytes(C.byref(cfg), int(src.shape[0]), int(src.shape[1])) > 0
 
 
@@ -126,7 +131,7 @@ _DEFORMABLE_AUX = _Step("decoder", _struct, null_d_memory=True, aux=True)
 def decoder_train(m, src, seed=None, aux=False):
     """DETRDecoder.forward in train() mode -> packed detections [B, Q, C+4] with the autograd edge to the native backward;
     aux: [L, B, Q, C+4], slice j = the heads on decoder layer j's output (the last slice is the plain step's result)"""
-    cfg = make_config(m._bb_cfg, m._dc_cfg, "fp32")
+    cfg = train_config(m, m._bb_cfg, m._dc_cfg)
     return _DecoderStep.apply(src, _DEFORMABLE_AUX if aux else _DEFORMABLE, cfg, dropout_rate(m), _draw_seed() if seed is None else seed, *_param_list(m))
 
 
@@ -177,7 +182,7 @@ def dense_supported(m, src):
             return False
     if not all(p.is_cuda and p.dtype == torch.float32 for p in _dense_param_list(m)) or dense_dropout_rate(m) is None:
         return False
-    cfg = make_config(m._bb_cfg, m._dc_cfg, "fp32")
+    cfg = train_config(m, m._bb_cfg, m._dc_cfg)
     return nat.lib().dod_dense_decoder_train_tape_bytes(C.byref(cfg), int(src.shape[0]), int(src.shape[1])) > 0
 
 
@@ -200,7 +205,7 @@ _DENSE = _Step("dense_decoder", _dense_struct, null_d_memory=False)
 
 def dense_decoder_train(m, src, seed=None):
     """DETRDecoder.forward (use_deformable=False) in train() mode -> packed detections [B, Q, C+4] with the autograd edge to the native backward"""
-    cfg = make_config(m._bb_cfg, m._dc_cfg, "fp32")
+    cfg = train_config(m, m._bb_cfg, m._dc_cfg)
     return _DecoderStep.apply(src, _DENSE, cfg, dense_dropout_rate(m), _draw_seed() if seed is None else seed, *_dense_param_list(m))
 
 
@@ -237,7 +242,7 @@ def tail_supported(m, layers, x):
     if any(q.requires_grad for q in m.dino.layernorm.parameters()):
         return False
     from ..config import DecoderConfig
-    cfg = make_config(bb, getattr(m, "_dc_cfg", None) or DecoderConfig(), "fp32")
+    cfg = train_config(m, bb, getattr(m, "_dc_cfg", None) or DecoderConfig())
     return nat.lib().dod_backbone_tail_tape_bytes(C.byref(cfg), int(x.shape[0]), int(x.shape[1]), len(layers)) > 0
 
 
@@ -316,5 +321,5 @@ def backbone_tail(m, x_in, layers):
     native backward (gradients of lora_A / lora_B and of the projection)"""
     from ..config import DecoderConfig
     dc = getattr(m, "_dc_cfg", None) or DecoderConfig()
-    cfg = make_config(m._bb_cfg, dc, "fp32")
+    cfg = train_config(m, m._bb_cfg, dc)
     return _BackboneTail.apply(x_in, m, list(layers), cfg, *_tail_trainables(m, layers))

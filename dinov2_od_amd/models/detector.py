@@ -3,7 +3,7 @@ import torch
 import torch.nn as nn
 
 from ..config import REF_DEFAULTS
-from ..engine import default_precision, split_detections
+from ..engine import check_train_precision, default_precision, split_detections
 from .dinov2_backbone import DINOv2Backbone, _EngineMixin
 from .detr_decoder import DETRDecoder
 
@@ -11,7 +11,9 @@ from .detr_decoder import DETRDecoder
 class DINOv2ObjectDetector(_EngineMixin, nn.Module):   # state-dict keys already carry "backbone." / "decoder."
     """Same constructor defaults as the reference (config.py:21-35 via detector.py:9-21).
     Extra keyword arguments: `pretrained`, `precision`, `backbone_config` (micro test models), `aux_loss` (train() outputs
-    gain "aux_outputs": DETRDecoder)."""
+    gain "aux_outputs": DETRDecoder), `train_precision` ("fp32" | "bf16x3": the linears of the native train() steps as bf16 split
+    products on their fp32 operands; it acts on the native steps only -- the autograd composite stays fp32 -- and `precision` keeps
+    governing eval() and the frozen prefix.  set_train_precision() changes it later)."""
 
     def __init__(self,
                  num_classes=REF_DEFAULTS["num_classes"],
@@ -26,8 +28,9 @@ class DINOv2ObjectDetector(_EngineMixin, nn.Module):   # state-dict keys already
                  dropout=REF_DEFAULTS["dropout"],
                  n_points=REF_DEFAULTS["n_points"],
                  use_deformable=REF_DEFAULTS["use_deformable"],
-                 pretrained=True, precision=None, backbone_config=None, aux_loss=False):
+                 pretrained=True, precision=None, backbone_config=None, train_precision="fp32", aux_loss=False):
         super().__init__()
+        self.train_precision = check_train_precision(train_precision)
         if hidden_dim is None:                                  # detector.py:25-35
             hidden_dim = 768
             for key, dim in (("small", 384), ("base", 768), ("large", 1024), ("giant", 1536)):
@@ -37,11 +40,12 @@ class DINOv2ObjectDetector(_EngineMixin, nn.Module):   # state-dict keys already
         precision = precision or default_precision()
         self.backbone = DINOv2Backbone(model_name=dino_model_name, lora_r=lora_r, lora_alpha=lora_alpha,
                                        target_dim=hidden_dim, pretrained=pretrained, precision=precision,
-                                       config=backbone_config)
+                                       config=backbone_config, train_precision=train_precision)
         self.decoder = DETRDecoder(num_queries=num_queries, hidden_dim=hidden_dim, nheads=nheads,
                                    num_decoder_layers=num_decoder_layers, num_classes=num_classes,
                                    dim_feedforward=dim_feedforward, dropout=dropout, n_points=n_points,
-                                   use_deformable=use_deformable, precision=precision, aux_loss=aux_loss)
+                                   use_deformable=use_deformable, precision=precision, aux_loss=aux_loss,
+                                   train_precision=train_precision)
         self.precision = precision
         self._dropout_p = float(dropout)
         self._bb_cfg = self.backbone._bb_cfg

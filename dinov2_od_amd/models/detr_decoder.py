@@ -4,7 +4,7 @@ import torch
 import torch.nn as nn
 
 from ..config import BackboneConfig, DecoderConfig
-from ..engine import default_precision, split_detections
+from ..engine import check_train_precision, default_precision, split_detections
 from .dinov2_backbone import _Box, _EngineMixin
 
 
@@ -70,14 +70,18 @@ class MLP(_Box):
 
 
 class DETRDecoder(_EngineMixin, nn.Module):
-    """dino_detector/models/detr_decoder.py:7-83; `precision` and `aux_loss` are the only extra arguments.
+    """dino_detector/models/detr_decoder.py:7-83; `precision`, `aux_loss` and `train_precision` are the only extra arguments.
+    train_precision="bf16x3": the native train() step runs its backward linears and the forward products over the memory rows as bf16
+    split products (the query-side forward stays fp32); it acts on the native steps only -- the autograd composite is fp32.
     aux_loss=True (deformable branch): in train() the output dict gains "aux_outputs", DETR's list of L-1 dicts
     {"pred_logits", "pred_boxes"} -- the shared heads on the outputs of decoder layers 0 .. L-2 -- for deep supervision
     (losses.SetCriterion adds their losses as loss_*_{i}).  eval() never has the key.  No parameter is added."""
 
     def __init__(self, num_queries, hidden_dim, nheads, num_decoder_layers, num_classes,
-                 dim_feedforward=2048, dropout=0.1, n_points=4, use_deformable=True, precision=None, aux_loss=False):
+                 dim_feedforward=2048, dropout=0.1, n_points=4, use_deformable=True, precision=None,
+                 train_precision="fp32", aux_loss=False):
         super().__init__()
+        self.train_precision = check_train_precision(train_precision)
         if aux_loss and not use_deformable:
             raise ValueError("aux_loss=True needs use_deformable=True: the dense nn.TransformerDecoder branch returns no per-layer states")
         self.aux_loss = bool(aux_loss)

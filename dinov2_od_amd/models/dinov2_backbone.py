@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from ..config import BackboneConfig, DecoderConfig, variant_of
-from ..engine import Engine, default_precision
+from ..engine import Engine, check_train_precision, default_precision
 
 
 class _Box(nn.Module):
@@ -169,15 +169,27 @@ class _EngineMixin:
         self.precision = precision
         self.__dict__.pop("_engine", None)
 
+    def set_train_precision(self, train_precision):
+        """"fp32" | "bf16x3": what the NATIVE train() steps (models/_native_train.py) run their linears on, for this module and the
+        engine modules below it.  `precision` -- eval() and the frozen prefix -- is not touched, and neither is the autograd composite
+        (fp32), which still runs whatever the native steps do not take."""
+        self.train_precision = check_train_precision(train_precision)
+        for m in self.children():
+            if isinstance(m, _EngineMixin):
+                m.set_train_precision(train_precision)
+        return self
+
 
 class DINOv2Backbone(_EngineMixin, nn.Module):
     """dino_detector/models/dinov2_backbone.py:7-67.  Extra keyword arguments (not in the
-    reference): `pretrained` (default True, like from_pretrained) and `precision`
-    ("bf16" fast path | "fp32" strict parity)."""
+    reference): `pretrained` (default True, like from_pretrained), `precision`
+    ("bf16" fast path | "fp32" strict parity) and `train_precision` ("fp32" | "bf16x3": the linears of the native
+    train() step of the LoRA tail as bf16 split products; acts on the native step only, see set_train_precision)."""
 
     def __init__(self, model_name="facebook/dinov2-base", lora_r=4, lora_alpha=1.0, target_dim=None,
-                 pretrained=True, precision=None, config: BackboneConfig = None):
+                 pretrained=True, precision=None, config: BackboneConfig = None, train_precision="fp32"):
         super().__init__()
+        self.train_precision = check_train_precision(train_precision)
         self.model_variant = model_name.split('/')[-1]
         bb = config if config is not None else BackboneConfig.from_name(model_name, lora_r, lora_alpha, target_dim)
         if config is not None:

@@ -167,6 +167,18 @@ int dod_op_gemm_f32x(const float* A, int lda, int a_kmajor, long long a_sb, long
                      const float* W, int ldw, int w_kmajor, long long w_sb, long long w_sh,
                      float* C, int ldc, long long c_sb, long long c_sh,
                      int M, int N, int K, int batch, int hb, float alpha, int accumulate, int ksplit, void* stream);
+/* The same product, argument for argument, as a bf16 split product on the fp32 operands (csrc/gemm_f32x3.hip): each operand is split
+ * x = h + l (h = bf16_rne(x), l = bf16_rne(x - h), as dod_op_split_pair) on its way into LDS and
+ *   C[z] (+)= alpha * (Ah Wh^T + Ah Wl^T + Al Wh^T),  fp32 accumulation on the bf16 MFMA
+ * -- what the training step's linears run on when its configuration says DOD_PREC_BF16X3 (see "training precision" below). */
+int dod_op_gemm_f32x3(const float* A, int lda, int a_kmajor, long long a_sb, long long a_sh,
+                      const float* W, int ldw, int w_kmajor, long long w_sb, long long w_sh,
+                      float* C, int ldc, long long c_sb, long long c_sh,
+                      int M, int N, int K, int batch, int hb, float alpha, int accumulate, int ksplit, void* stream);
+/* The forward linear of that mode, with the kernel's whole epilogue: Y[M,N] = act(X[M,K] W[N,K]^T + bias) * scale + resid (bias / scale / resid
+ * fp32 or NULL; ldw = K; act: DOD_ACT_NONE / RELU / GELU / SIGMOID). */
+int dod_op_linear_f32x3(const float* X, int ldx, const float* W, const float* bias, const float* scale, const float* resid, int ldr,
+                        int M, int N, int K, float* Y, int ldy, int act, void* stream);
 /* fp8 (OCP e4m3) operands, one byte per element: out = act((Aq Wq^T) * a_scale[m] * w_scale[n] + bias) * scale + resid.
  * K % 64 == 0, lda / ldw in bytes, % 16 == 0.  The ViT-g fp8 configuration's linears (BASELINE configs[4]). */
 int dod_op_linear_fp8(const void* A, int lda, const float* a_scale, const void* W, int ldw, const float* w_scale,
@@ -450,7 +462,12 @@ int dod_set_criterion_layers_backward(const float* pred_logits, int64_t logits_r
  * the gradients of every decoder / head parameter and of `memory` (which the caller feeds on into the projection and the
  * LoRA-adapted blocks).  Stateless: the shapes come from `cfg`, the fp32 parameters from the caller's own tensors.
  * All pointers are device pointers.  `grads` has the layout of the parameters; its tensors are float ACCUMULATORS (the layers
- * share one set of weights; zero them for a plain gradient).  The same `dropout_p` / `seed` must be given to both calls. */
+ * share one set of weights; zero them for a plain gradient).  The same `dropout_p` / `seed` must be given to both calls.
+ * Training precision: cfg->precision = DOD_PREC_BF16X3 runs the linears of every training step below as bf16 split products on their fp32
+ * operands (dod_op_gemm_f32x3) -- the backbone tail's every linear, forward and backward; the decoders' every backward linear and their
+ * forward products over the B*N memory rows (value_proj / the cross-attention k | v projection; the query-side forward stays fp32, it feeds
+ * floor()).  Attention, the deformable gather, LayerNorm, the LoRA rank-r products, dropout and the deterministic mode are the fp32 step's.
+ * Every other precision value behaves as DOD_PREC_FP32, and the *_tape_bytes / *_workspace_bytes answers do not depend on it. */
 typedef struct dod_dec_train_params {
   const float *query_embed;                      /* [Q, Dd]            detr_decoder.py:15 */
   const float *class_w, *class_b;                /* [C, Dd], [C]       :40 */
@@ -642,9 +659,12 @@ int dod_reserve_gemm_scratch(size_t bytes);
  *                      wins over DINODET_ATTN_BWD_FLASH).  Read when the tape and workspace are sized and in both passes: set it around a whole step
  *   "epi_regmath"      16-wave bf16 GEMM with plain bf16 output rows (QKV, fc1 of the bf16 mode; gemm_x3.hip): 0 = the LDS-staged fp32 epilogue,
  *                      1 = the epilogue math on the accumulators (shipped; bit-identical).  Read once per launch
+ *   "f32x3_tile"       fp32-in bf16 split GEMM (gemm_f32x3.hip): 64 / 128 = that tile for every product; 0 = the shipped rule (128x128 from 256 such
+ *                      tiles up, one per CU)
  * dod_test_counter("tail_splits"): GEMM calls that took the tail-split path so far; "rem_cuts": GEMM calls whose short last round ran as a
  * launch of its own (gemm_bf16.hip); "f32_ksplits": fp32 GEMM launches that split K across workgroups (gemm_f32.hip); "epi_regmath": launches
- * of the 16-wave bf16 GEMM that took the register epilogue; -1 for an unknown name.
+ * of the 16-wave bf16 GEMM that took the register epilogue; "f32x3_launches": launches of the fp32-in bf16 split GEMM, "f32x3_wide_launches": those
+ * that took its 128x128 tile; -1 for an unknown name.
  * The in-kernel time stamps, the register-only MFMA probes and every tile / schedule override of the tuning rounds exist only in
  * -DDINODET_TUNING builds (include/dinodet_tuning.h); the release library exports none of them. */
 int dod_test_set_option(const char* name, int value);
@@ -657,7 +677,8 @@ const char* dod_version(void);
  * New entry points alone change no signature and no layout: dod_coco_eval_* and dod_op_sort_pairs_* joined revision 6, and a caller that
  * needs them resolves them by name (the Python binding fails at load when one is missing).  The training-step operators
  * (dod_op_layernorm_bwd ... dod_op_colsum_add) joined revision 6 the same way.  So did the optimizer step (dod_optim_*), the deep-supervision
- * step (dod_decoder_train_aux_*) and the layered criterion (dod_set_criterion_layers_*).
+ * step (dod_decoder_train_aux_*), the layered criterion (dod_set_criterion_layers_*) and the split-product operators (dod_op_gemm_f32x3,
+ * dod_op_linear_f32x3; the training entry points reading cfg->precision changes no signature either).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);

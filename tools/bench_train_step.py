@@ -6,7 +6,9 @@ against the all-composite evaluation (selected by an input that requires grad).
 --aux: deep supervision (aux_loss=True, the loss reads every decoder layer's outputs) instead: the native step without aux, the
 native step with aux and the composite with aux (DINODET_NATIVE_TRAIN=0), alternated round by round, device events around each step,
 median and p10 / p90 over 30 steps per leg after a warm-up of each.
-    python tools/bench_train_step.py --aux [resolution] [batch]"""
+    python tools/bench_train_step.py --aux [resolution] [batch]
+--train-precision fp32|bf16x3: what the native step's linears run on (DINOv2ObjectDetector.set_train_precision; default fp32).
+    python tools/bench_train_step.py --train-precision bf16x3 [resolution] [batch]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,6 +17,12 @@ m, bb, dc = build("facebook/dinov2-base", 100, os.environ.get("DINODET_PRECISION
 m.train()
 AUX = "--aux" in sys.argv
 argv = [a for a in sys.argv[1:] if a != "--aux"]
+TP = "fp32"
+if "--train-precision" in argv:
+    i = argv.index("--train-precision")
+    TP = argv[i + 1]
+    del argv[i:i + 2]
+m.set_train_precision(TP)
 R = int(argv[0]) if len(argv) > 0 else 224
 B = int(argv[1]) if len(argv) > 1 else 16
 x = torch.rand(B, 3, R, R, device="cuda")
@@ -47,7 +55,7 @@ def step(inp):
     m.zero_grad(set_to_none=True)
     o = m(inp)
     (o["pred_logits"].square().mean() + o["pred_boxes"].mean()).backward()
-first = "native prefix + composite" if os.environ.get("DINODET_NATIVE_TRAIN", "1") == "0" else "native step"
+first = "native prefix + composite" if os.environ.get("DINODET_NATIVE_TRAIN", "1") == "0" else f"native step ({TP})"
 for name, mk in ((first, lambda: x), ("all-composite", lambda: x.clone().requires_grad_(True))):
     for _ in range(2): step(mk())
     torch.cuda.synchronize(); t = time.perf_counter()
