@@ -11,9 +11,11 @@
 //   S^T = K Q^T   (A = K tile rows from LDS via ds_read_b128, B = Q fragments held in registers)
 //   O^T += V^T P^T (A = V^T via ds_read_b64_tr_b16 from the row-major V tile, B = the S^T accumulator
 //                  registers themselves, converted to bf16 - no LDS round trip for P)
-// N = 1370 is not a multiple of 64: the last tile's keys >= N get -inf before the row max; loads of
-// rows >= N are clamped to row N-1 (finite values times p = 0).
+// N = 1370 is not a multiple of 64: the last tile's keys >= N get -inf before the row max; rows >= N
+// lie past the staging descriptor's bound and arrive as zeros (p = 0 times 0).  The last tile runs behind
+// the loop of full tiles, at half width when it holds at most 32 keys.
 #include "dod_common.h"
+#include <atomic>
 #include <cstdlib>
 
 #define AT_WAVES 4
@@ -26,19 +28,22 @@ __device__ __forceinline__ int vswz(int row, int chunk) { return chunk ^ (((row 
 
 typedef bf16x4 __attribute__((address_space(3))) * lds_bf16x4_ptr;
 
-// One K/V tile (64 keys) for one wave and NQ blocks of 32 query rows (query on the lane).  TAIL masks keys >= N
-// (last tile only, so the full tiles carry no compare/select).  Softmax in the exp2 domain with the scale folded
-// into one FMA: p = exp2(s*c - m*c), m = running max of the raw scores (c > 0).
+// One K/V tile (64 keys) for one wave and NQ blocks of 32 query rows (query on the lane).  TAIL != 0 masks keys >= N
+// (last tile only, so the full tiles carry no compare/select).  TAIL == 2: the last tile holds at most 32 keys (N = 1370: 26), so its
+// second 32-key block is all masked -- scores of -inf, p = +0, +0 into l and O -- and is not computed at all: KB = 1 key block, half the
+// S MFMAs, exps and packs, no V^T read past row 31, two P V k-steps instead of four.  The bits equal the full-width tile's.
+// Softmax in the exp2 domain with the scale folded into one FMA: p = exp2(s*c - m*c), m = running max of the raw scores (c > 0).
 // NQ = 2 gives the scheduler two independent MFMA -> VALU -> MFMA chains to interleave (PMC on NQ = 1: 42 % of wave
 // cycles stalled on instruction dependencies, MFMA pipe 34 % busy) and halves the K/V fragment reads per MFMA.
-template <bool TAIL, int NQ>
+template <int TAIL, int NQ>
 __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, const bf16x8 (&qf)[NQ][4], f32x16 (&o)[NQ][2],
                                           float (&m_run)[NQ], float (&l_run)[NQ], float c, int kbase, int N,
                                           int lr, int lh, int g16, int tq, int tp) {
-  f32x16 s[NQ][2];
+  constexpr int KB = TAIL == 2 ? 1 : 2;      // 32-key blocks computed
+  f32x16 s[NQ][KB];
   const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int kb = 0; kb < 2; ++kb) {
+  for (int kb = 0; kb < KB; ++kb) {
     const int row = kb * 32 + lr;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -53,7 +58,7 @@ __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, const 
   for (int q = 0; q < NQ; ++q) {
     if (TAIL) {
 #pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
+      for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = kbase + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -63,8 +68,10 @@ __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, const 
     float mx = s[q][0][0];
 #pragma unroll
     for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[q][0][r]);
+    if (KB == 2) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[q][1][r]);
+      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[q][KB - 1][r]);
+    }
     {   // other half's max by v_permlane32_swap (VALU; __shfl_xor goes through the LDS crossbar and an lgkmcnt wait)
       const unsigned mb = __float_as_uint(mx);
       const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
@@ -83,7 +90,7 @@ __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, const 
            // instructions: 376 against 420 per tile); this form is 4 % faster (6.06 -> 5.83 ms of attention per batch-64 step).
       float l0 = 0.f, l1 = 0.f, l2 = 0.f, l3 = 0.f;
 #pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
+      for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; r += 4) {
           const float e0 = __builtin_amdgcn_exp2f(fmaf(s[q][kb][r], c, nm)), e1 = __builtin_amdgcn_exp2f(fmaf(s[q][kb][r + 1], c, nm));
@@ -101,7 +108,7 @@ __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, const 
     for (int r = 0; r < 16; ++r) { o[q][0][r] *= alpha; o[q][1][r] *= alpha; }
     // P^T fragments: accumulator registers 8u..8u+7 of key block kb are the B operand of k-step 2kb+u
 #pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
+    for (int s4 = 0; s4 < 2 * KB; ++s4) {
       const f32x16& pp = s[q][s4 >> 1];
       const int u = (s4 & 1) * 8;
       uint4 pk;
@@ -126,6 +133,25 @@ __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, const 
 #pragma unroll
     for (int db = 0; db < 2; ++db) {
       bf16x4 v0, v1, v2, v3, v4, v5, v6, v7;
+      if (KB == 1) {      // keys 0..31 only
+        asm volatile(
+            "ds_read_b64_tr_b16 %0, %4\n\t"
+            "ds_read_b64_tr_b16 %1, %4 offset:1024\n\t"
+            "ds_read_b64_tr_b16 %2, %4 offset:2048\n\t"
+            "ds_read_b64_tr_b16 %3, %4 offset:3072\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
+            : "v"(db ? a1 : a0)
+            : "memory");
+        const bf16x8 vf0 = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+        const bf16x8 vf1 = __builtin_shufflevector(v2, v3, 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          o[q][db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf0, pf[q][0], o[q][db], 0, 0, 0);
+          o[q][db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf1, pf[q][1], o[q][db], 0, 0, 0);
+        }
+        continue;
+      }
       asm volatile(
           "ds_read_b64_tr_b16 %0, %8\n\t"
           "ds_read_b64_tr_b16 %1, %8 offset:1024\n\t"
@@ -169,7 +195,8 @@ __shared__ __attribute__((aligned(16))) char g_attn_smem[3 * 2 * AT_KV * 128];
 // the kernel body for workgroup index `blk_` of a launch over query rows [q_lo, q_hi)
 // MX (fp8 mode, round 4): the context leaves as block-scaled e4m3 -- ctx is then a BYTE buffer [B*N, D], bs its e8m0 bytes [B*N][2][D / 64] --
 // the out-proj GEMM's operand, written here instead of by a quantisation pass over bf16 rows (a head's 64 columns are two blocks of 32)
-template <int AT_NQ, bool MX = false>
+// DIET = false (test option "attn_diet" = 0): the full-width tail tile and the per-lane global pointers of the staging, as before
+template <int AT_NQ, bool MX, bool DIET>
 __device__ __forceinline__ void attn_bf16_body(const int blk_, const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
                                                int N, int heads, int npairs, float scale_log2e, int q_lo, int q_hi, unsigned char* __restrict__ bs = nullptr) {
   char* const smem = g_attn_smem;
@@ -222,7 +249,30 @@ __device__ __forceinline__ void attn_bf16_body(const int blk_, const bf16_t* __r
   const int kc0 = ((lane & 7) ^ ((prow0 >> 1) & 7)) * 8, kc1 = ((lane & 7) ^ ((prow1 >> 1) & 7)) * 8;
   const int vc0 = ((lane & 7) ^ (((prow0 >> 1) & 1) << 2)) * 8, vc1 = ((lane & 7) ^ (((prow1 >> 1) & 1) << 2)) * 8;
   const bf16_t* kbase = base + D + h * 64;
-#define AT_STAGE(slot_, kt_)                                                                                   \
+  // DIET: staging through a buffer descriptor (as gemm_pp.hip): the base is the (image, head) K column block advanced to the tile's first
+  // key row -- wave-uniform, in SGPRs --, a lane keeps one 32-bit byte offset per piece, computed here once, and V lies 2 D bytes behind K
+  // in the scalar offset.  num_records ends with the V columns of the tile's last key < N, so a key row >= N starts past it and reads
+  // as zeros instead of being clamped to row N - 1: a zero K row is masked like any other, a zero V row meets p = 0.  (The bound is
+  // met by the lane offset alone, however the hardware counts the scalar one: a valid K chunk ends 2 D bytes before it, the next row
+  // starts 4 D - 128 past it.)  Four live offsets cost registers -- hipcc recomputed the pointers of AT_STAGE_PTR from the lane id every
+  // tile: 227 -> 235 in the 64-row body, 126 -> 152 in the 32-row one --; what this form removes is per-tile VALU work.
+  const unsigned ldb = (unsigned)ld * 2;
+  const unsigned ok0 = prow0 * ldb + kc0 * 2, ok1 = prow1 * ldb + kc1 * 2, ov0 = prow0 * ldb + vc0 * 2, ov1 = prow1 * ldb + vc1 * 2;
+  const unsigned row_end = 2 * D + 128;                               // from a key row's K columns to the end of its V columns
+#define AT_STAGE_BUF(slot_, kt_)                                                                               \
+  {                                                                                                            \
+    const int left_ = N - (kt_) * AT_KV;                               /* key rows from this tile on */        \
+    const __amdgpu_buffer_rsrc_t r_ = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)kbase + (size_t)(kt_) * AT_KV * ldb), 0, \
+                                                                        (int)((unsigned)((left_ < AT_KV ? left_ : AT_KV) - 1) * ldb + row_end), 0x00020000); \
+    char* sK_ = smem + (slot_) * (2 * AT_KV * 128) + wu * 2048;                                                \
+    char* sV_ = sK_ + AT_KV * 128;                                                                             \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r_, (lptr_t)(sK_), 16, ok0, 0, 0, 0);                             \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r_, (lptr_t)(sK_ + 1024), 16, ok1, 0, 0, 0);                      \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r_, (lptr_t)(sV_), 16, ov0, 2 * D, 0, 0);                         \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r_, (lptr_t)(sV_ + 1024), 16, ov1, 2 * D, 0, 0);                  \
+  }
+#define AT_STAGE(slot_, kt_) { if (DIET) AT_STAGE_BUF(slot_, kt_) else AT_STAGE_PTR(slot_, kt_) }
+#define AT_STAGE_PTR(slot_, kt_)                                                                               \
   {                                                                                                            \
     int key0 = (kt_) * AT_KV + prow0, key1 = (kt_) * AT_KV + prow1;                                            \
     key0 = key0 < N ? key0 : N - 1; key1 = key1 < N ? key1 : N - 1;                                            \
@@ -257,7 +307,9 @@ __device__ __forceinline__ void attn_bf16_body(const int blk_, const bf16_t* __r
   unsigned long long* stamps = ATTN_STAMPS;
   unsigned long long t_begin = 0, t_wait = 0;
   if (stamps) t_begin = __builtin_amdgcn_s_memtime();
-  for (int kt = 0; kt < nkt; ++kt) {
+  // full tiles in the loop, the masked last tile (if any) behind it: the loop body holds ONE form of the tile -- with the tail forms as
+  // branches of the body the register allocation of all of them met in one region (64-row body: 256 registers and spills; here 235)
+  for (int kt = 0; kt < nfull; ++kt) {
     unsigned long long tw0 = 0;
     if (stamps) tw0 = __builtin_amdgcn_s_memtime();
     if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");     // tile kt landed, tile kt+1 may fly
@@ -270,12 +322,21 @@ __device__ __forceinline__ void attn_bf16_body(const int blk_, const bf16_t* __r
       AT_STAGE(ns, kt + 2)
     }
     const char* sK = smem + slot * (2 * AT_KV * 128);
-    const char* sV = sK + AT_KV * 128;
-    if (active) {
-      if (kt < nfull) attn_tile<false, AT_NQ>(sK, sV, qf, o, m_run, l_run, scale_log2e, kt * AT_KV, N, lr, lh, g16, tq, tp);
-      else attn_tile<true, AT_NQ>(sK, sV, qf, o, m_run, l_run, scale_log2e, kt * AT_KV, N, lr, lh, g16, tq, tp);
-    }
+    if (active) attn_tile<0, AT_NQ>(sK, sK + AT_KV * 128, qf, o, m_run, l_run, scale_log2e, kt * AT_KV, N, lr, lh, g16, tq, tp);
     slot = slot == 2 ? 0 : slot + 1;
+  }
+  if (nfull < nkt) {      // the last tile, 1..63 keys: nothing left to stage
+    unsigned long long tw0 = 0;
+    if (stamps) tw0 = __builtin_amdgcn_s_memtime();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (stamps) t_wait += __builtin_amdgcn_s_memtime() - tw0;
+    const char* sK = smem + slot * (2 * AT_KV * 128);
+    if (active) {
+      if (DIET && N - nfull * AT_KV <= 32) attn_tile<2, AT_NQ>(sK, sK + AT_KV * 128, qf, o, m_run, l_run, scale_log2e, nfull * AT_KV, N, lr, lh, g16, tq, tp);
+      else attn_tile<1, AT_NQ>(sK, sK + AT_KV * 128, qf, o, m_run, l_run, scale_log2e, nfull * AT_KV, N, lr, lh, g16, tq, tp);
+    }
   }
 
   if (stamps && tid == 0) {
@@ -322,20 +383,20 @@ __device__ __forceinline__ void attn_bf16_body(const int blk_, const bf16_t* __r
   }
 }
 
-template <int AT_NQ, bool MX>
+template <int AT_NQ, bool MX, bool DIET>
 __global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
                                                         int N, int heads, int npairs, float scale_log2e, int q_lo, int q_hi, unsigned char* __restrict__ bs) {
-  attn_bf16_body<AT_NQ, MX>(blockIdx.x, qkv, ctx, N, heads, npairs, scale_log2e, q_lo, q_hi, bs);
+  attn_bf16_body<AT_NQ, MX, DIET>(blockIdx.x, qkv, ctx, N, heads, npairs, scale_log2e, q_lo, q_hi, bs);
 }
 // ONE launch for a sequence whose last 256-row block is short (N = 1370: 5 blocks + 90 rows): workgroups [0, main_blocks) run the
 // 64-rows-per-wave body over rows [0, q_main), the workgroups behind them the 32-rows-per-wave body over the remainder -- dispatched
 // last, they fill the main part's end-of-kernel bubble instead of costing a launch of their own (round 3: the separate tail launch
 // took 62.6 us per layer for 6.6 % of the rows, profiles/r03_bench_bf16_kernel_stats.csv).  main_blocks % 8 == 0 keeps both XCD maps.
-template <bool MX>
+template <bool MX, bool DIET>
 __global__ __launch_bounds__(256, 2) void attn_bf16_fused_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
                                                               int N, int heads, int npairs, float scale_log2e, int main_blocks, int q_main, unsigned char* __restrict__ bs) {
-  if ((int)blockIdx.x < main_blocks) attn_bf16_body<2, MX>(blockIdx.x, qkv, ctx, N, heads, npairs, scale_log2e, 0, q_main, bs);
-  else attn_bf16_body<1, MX>((int)blockIdx.x - main_blocks, qkv, ctx, N, heads, npairs, scale_log2e, q_main, N, bs);
+  if ((int)blockIdx.x < main_blocks) attn_bf16_body<2, MX, DIET>(blockIdx.x, qkv, ctx, N, heads, npairs, scale_log2e, 0, q_main, bs);
+  else attn_bf16_body<1, MX, DIET>((int)blockIdx.x - main_blocks, qkv, ctx, N, heads, npairs, scale_log2e, q_main, N, bs);
 }
 
 // (Round 4 built a 512-thread PING-PONG form of this kernel -- both waves of every SIMD in one workgroup, phased against each other with the
@@ -351,12 +412,26 @@ extern "C" int dod_debug_attn_stamps(void* dev_buf) {
 }
 #endif
 
+// the kernel of a launch: NQ = 1 / 2 query blocks per wave, 0 = the fused kernel; every form has the same parameters
+typedef void (*attn_kern_t)(const bf16_t*, bf16_t*, int, int, int, float, int, int, unsigned char*);
+template <int NQ>
+static attn_kern_t attn_pick(bool mx, bool diet) {
+  if constexpr (NQ == 0) return mx ? (diet ? attn_bf16_fused_kernel<true, true> : attn_bf16_fused_kernel<true, false>)
+                                   : (diet ? attn_bf16_fused_kernel<false, true> : attn_bf16_fused_kernel<false, false>);
+  else return mx ? (diet ? attn_bf16_kernel<NQ, true, true> : attn_bf16_kernel<NQ, true, false>)
+                 : (diet ? attn_bf16_kernel<NQ, false, true> : attn_bf16_kernel<NQ, false, false>);
+}
+static std::atomic<long> g_attn_half_tiles{0};
+long attn_half_tile_count() { return g_attn_half_tiles.load(); }
+
 int launch_attn_bf16(const bf16_t* qkv, bf16_t* ctx, int B, int N, int heads, float scale, hipStream_t s, unsigned char* ctx_bs) {
   if (B <= 0 || N <= 0 || heads <= 0) return 1;
   if (ctx_bs && (heads * 64) % 64 != 0) return 2;
   const bool mx = ctx_bs != nullptr;
   const int npairs = B * heads, pairs8 = (npairs + 7) / 8 * 8;
   const float c = scale * 1.44269504088896340736f;
+  const bool diet = dod_option(DOD_OPT_ATTN_DIET) != 0;                  // 0: the full-width tail tile and pointer staging (bit-identical)
+  if (diet && (N - 1) % AT_KV < 32) ++g_attn_half_tiles;                 // the last key tile holds 1..32 keys
   // 64 query rows per wave once the grid still fills the chip several times over (measured: +5 % at B*heads = 768,
   // -12 % at 96), else 32
   static const char* nqe = DOD_TUNE_ENV("DINODET_ATTN_NQ");   // tuning override
@@ -375,26 +450,19 @@ int launch_attn_bf16(const bf16_t* qkv, bf16_t* ctx, int B, int N, int heads, fl
       // tuning builds: DINODET_ATTN_LDS_PAD = bytes of unused dynamic LDS per workgroup (64 KiB leaves ONE workgroup per CU: one wave per SIMD)
       static const int pad = [] { const char* v = getenv("DINODET_ATTN_LDS_PAD"); return v ? atoi(v) : 0; }();
       if (pad > 0 && !mx) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bf16_fused_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, pad);
-        hipLaunchKernelGGL(attn_bf16_fused_kernel<false>, dim3(pairs8 * nqb + pairs8), dim3(256), pad, s, qkv, ctx, N, heads, npairs, c, pairs8 * nqb, q_main, ctx_bs);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bf16_fused_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, pad);
+        hipLaunchKernelGGL((attn_bf16_fused_kernel<false, true>), dim3(pairs8 * nqb + pairs8), dim3(256), pad, s, qkv, ctx, N, heads, npairs, c, pairs8 * nqb, q_main, ctx_bs);
         return hipGetLastError() == hipSuccess ? 0 : 3;
       }
 #endif
-      if (mx) hipLaunchKernelGGL(attn_bf16_fused_kernel<true>, dim3(pairs8 * nqb + pairs8), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, pairs8 * nqb, q_main, ctx_bs);
-      else hipLaunchKernelGGL(attn_bf16_fused_kernel<false>, dim3(pairs8 * nqb + pairs8), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, pairs8 * nqb, q_main, ctx_bs);
+      hipLaunchKernelGGL(attn_pick<0>(mx, diet), dim3(pairs8 * nqb + pairs8), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, pairs8 * nqb, q_main, ctx_bs);
     } else {
-      if (mx) {
-        hipLaunchKernelGGL((attn_bf16_kernel<2, true>), dim3(pairs8 * nqb), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, 0, q_main, ctx_bs);
-        if (split) hipLaunchKernelGGL((attn_bf16_kernel<1, true>), dim3(pairs8), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, q_main, N, ctx_bs);
-      } else {
-        hipLaunchKernelGGL((attn_bf16_kernel<2, false>), dim3(pairs8 * nqb), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, 0, q_main, ctx_bs);
-        if (split) hipLaunchKernelGGL((attn_bf16_kernel<1, false>), dim3(pairs8), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, q_main, N, ctx_bs);
-      }
+      hipLaunchKernelGGL(attn_pick<2>(mx, diet), dim3(pairs8 * nqb), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, 0, q_main, ctx_bs);
+      if (split) hipLaunchKernelGGL(attn_pick<1>(mx, diet), dim3(pairs8), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, q_main, N, ctx_bs);
     }
   } else {
     const int nqb = (N + AT_WAVES * 32 - 1) / (AT_WAVES * 32);
-    if (mx) hipLaunchKernelGGL((attn_bf16_kernel<1, true>), dim3(pairs8 * nqb), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, 0, N, ctx_bs);
-    else hipLaunchKernelGGL((attn_bf16_kernel<1, false>), dim3(pairs8 * nqb), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, 0, N, ctx_bs);
+    hipLaunchKernelGGL(attn_pick<1>(mx, diet), dim3(pairs8 * nqb), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, 0, N, ctx_bs);
   }
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }

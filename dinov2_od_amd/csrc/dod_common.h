@@ -29,12 +29,14 @@ enum { DOD_OPT_TAILSPLIT = 0,         // GEMM wave-quantisation tail split: 0 of
        DOD_OPT_ATTN_BWD_FLASH,        // backbone-tail attention adjoint (tail_train.hip tail_flash_bwd): 0 = never the flash form, 1 = whenever head_dim is 64
        DOD_OPT_EPI_REGMATH,           // 16-wave bf16 GEMM, plain bf16 rows (gemm_x3.hip): 0 = the LDS-staged epilogue, 1 = epilogue math on the accumulators (shipped)
        DOD_OPT_F32X3_TILE,            // fp32-in bf16 split GEMM (gemm_f32x3.hip): 64 / 128 = that tile for every product (0 = the shipped rule)
+       DOD_OPT_ATTN_DIET,             // bf16 flash attention (attn_bf16.hip): 0 = the full-width tail key tile and per-lane pointer staging, 1 = half tail tile + descriptor staging (shipped)
        DOD_OPT_COUNT };
 int dod_option(int which);            // dod_api.hip; -1 when unset
 long gemm_tail_split_count();         // gemm_pp.hip: GEMM calls that took the tail-split path so far
 long optim_launch_count();            // optim.hip: launches of the optimizer entries so far
 long optim_constant(int which);       // optim.hip: 0 elements per workgroup, 1 / 2 tensors per update / norm launch
 long gemm_rem_cut_count();            // gemm_bf16.hip: GEMM calls whose short last round ran as a launch of its own
+long attn_half_tile_count();          // attn_bf16.hip: attention launches whose last key tile ran at half width
 long gemm_epi_regmath_count();        // gemm_x3.hip: launches of the 16-wave bf16 GEMM that took the register epilogue
 
 #ifdef DINODET_TUNING

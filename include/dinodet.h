@@ -661,10 +661,12 @@ int dod_reserve_gemm_scratch(size_t bytes);
  *                      1 = the epilogue math on the accumulators (shipped; bit-identical).  Read once per launch
  *   "f32x3_tile"       fp32-in bf16 split GEMM (gemm_f32x3.hip): 64 / 128 = that tile for every product; 0 = the shipped rule (128x128 from 256 such
  *                      tiles up, one per CU)
+ *   "attn_diet"        bf16 flash attention (attn_bf16.hip): 0 = the last key tile at full width and per-lane global pointers for the K/V staging,
+ *                      1 = a last tile of at most 32 keys computes one 32-key block, staging through a buffer descriptor (shipped; bit-identical)
  * dod_test_counter("tail_splits"): GEMM calls that took the tail-split path so far; "rem_cuts": GEMM calls whose short last round ran as a
  * launch of its own (gemm_bf16.hip); "f32_ksplits": fp32 GEMM launches that split K across workgroups (gemm_f32.hip); "epi_regmath": launches
  * of the 16-wave bf16 GEMM that took the register epilogue; "f32x3_launches": launches of the fp32-in bf16 split GEMM, "f32x3_wide_launches": those
- * that took its 128x128 tile; -1 for an unknown name.
+ * that took its 128x128 tile; "attn_diet": bf16 attention launches whose last key tile ran at half width; -1 for an unknown name.
  * The in-kernel time stamps, the register-only MFMA probes and every tile / schedule override of the tuning rounds exist only in
  * -DDINODET_TUNING builds (include/dinodet_tuning.h); the release library exports none of them. */
 int dod_test_set_option(const char* name, int value);
