@@ -42,6 +42,11 @@ int dod_option(int which) { return which >= 0 && which < DOD_OPT_COUNT ? g_optio
 static const char* const k_option_names[DOD_OPT_COUNT] = {"tailsplit", "dec_fused_split", "mha_chunk_images", "no_fused_patch", "ln_fold", "deterministic", "f32_ksplit",
                                                        "attn_bwd_flash", "epi_regmath", "f32x3_tile", "attn_diet"};
 
+static std::atomic<long> g_form_launches[FORM_COUNT];
+static const char* const k_form_names[FORM_COUNT] = {"bf16_128_r2", "bf16_128_r3", "bf16_m16", "k64", "ppm", "x3_16w", "x3_pp", "h2", "fp8_rows", "fp8mx_256x128",
+                                                     "fp8mx2_256x128", "fp8mx2_256x256", "f32", "patch_fused"};
+void gemm_form_launched(int form) { if (form >= 0 && form < FORM_COUNT) ++g_form_launches[form]; }
+
 extern "C" {
 
 int dod_test_set_option(const char* name, int value) {
@@ -62,6 +67,9 @@ long dod_test_counter(const char* name) {
   if (name && !strcmp(name, "optim_chunk_elems")) return optim_constant(0);
   if (name && !strcmp(name, "optim_table_tensors")) return optim_constant(1);
   if (name && !strcmp(name, "optim_norm_table_tensors")) return optim_constant(2);
+  if (name && !strncmp(name, "form_", 5))
+    for (int i = 0; i < FORM_COUNT; ++i)
+      if (!strcmp(name + 5, k_form_names[i])) return g_form_launches[i].load();
   return -1;
 }
 

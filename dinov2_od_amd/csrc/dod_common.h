@@ -38,6 +38,10 @@ long optim_constant(int which);       // optim.hip: 0 elements per workgroup, 1 
 long gemm_rem_cut_count();            // gemm_bf16.hip: GEMM calls whose short last round ran as a launch of its own
 long attn_half_tile_count();          // attn_bf16.hip: attention launches whose last key tile ran at half width
 long gemm_epi_regmath_count();        // gemm_x3.hip: launches of the 16-wave bf16 GEMM that took the register epilogue
+// kernel launches per inference GEMM form so far (dod_api.hip; dod_test_counter("form_<name>"), names in include/dinodet.h): counted by the launchers
+enum { FORM_BF16_128_R2 = 0, FORM_BF16_128_R3, FORM_BF16_M16, FORM_K64, FORM_PPM, FORM_X3_16W, FORM_X3_PP, FORM_H2, FORM_FP8_ROWS, FORM_FP8MX_256X128,
+       FORM_FP8MX2_256X128, FORM_FP8MX2_256X256, FORM_F32, FORM_PATCH_FUSED, FORM_COUNT };
+void gemm_form_launched(int form);
 
 #ifdef DINODET_TUNING
 #define DOD_TUNE_ENV(name) getenv(name)

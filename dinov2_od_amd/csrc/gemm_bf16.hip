@@ -370,6 +370,7 @@ int launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, 
       return launch_gemm_bf16_k64(A, lda, W, ldw, M, N, K, e, s);
     }
     LN_DISPATCH(e, GO_M16)
+    gemm_form_launched(FORM_BF16_M16);
     return hipGetLastError() == hipSuccess ? 0 : 3;
   }
   // Below that: 256x128x32 on v_mfma_f32_16x16x32_bf16 (two workgroups per CU) from 1 024 rows up, 128x128 for small M (decoder memory at small
@@ -381,6 +382,7 @@ int launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, 
   const bool m16 = force ? (force[0] == '8') : (M >= 1024 && N >= 128 && !few);
   if (m16) {
     LN_DISPATCH(e, GO_M16)
+    gemm_form_launched(FORM_BF16_M16);
   } else {
     const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
     // a grid of at most one workgroup per CU has nothing beside it to hide its DMA latency: the 3-slot ring (two K-tiles in flight)
@@ -389,8 +391,8 @@ int launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, 
     { static int cus[16] = {}; if (dev >= 0 && dev < 16) { if (!cus[dev]) { int c = 0; (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev); cus[dev] = c > 0 ? c : 256; } cu128 = cus[dev]; } }
 #define GO_128(LN_) hipLaunchKernelGGL((gemm_bf16_kernel<LN_, 2>), dim3(tiles), dim3(256), LDS128, s, A, lda, W, ldw, M, N, K, e);
 #define GO_128R(LN_) hipLaunchKernelGGL((gemm_bf16_kernel<LN_, 3>), dim3(tiles), dim3(256), LDS128R, s, A, lda, W, ldw, M, N, K, e);
-    if (ring && tiles <= cu128 && K >= 3 * BK) { LN_DISPATCH(e, GO_128R) }
-    else { LN_DISPATCH(e, GO_128) }
+    if (ring && tiles <= cu128 && K >= 3 * BK) { LN_DISPATCH(e, GO_128R) gemm_form_launched(FORM_BF16_128_R3); }
+    else { LN_DISPATCH(e, GO_128) gemm_form_launched(FORM_BF16_128_R2); }
 #undef GO_128
 #undef GO_128R
   }

@@ -282,6 +282,7 @@ int launch_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int
   }
   if (vec_ok(A, lda) && vec_ok(W, ldw)) hipLaunchKernelGGL(gemm_f32_kernel<true>, dim3(tiles, S), dim3(256), 0, s, A, lda, W, ldw, M, N, K, e, part, counters);
   else hipLaunchKernelGGL(gemm_f32_kernel<false>, dim3(tiles, S), dim3(256), 0, s, A, lda, W, ldw, M, N, K, e, part, counters);
+  gemm_form_launched(FORM_F32);
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 

@@ -531,16 +531,19 @@ int launch_gemm_fp8(const unsigned char* A, int lda, const unsigned char* W, int
     if (e.w_bs && big && !(big == 2 && e.out_bs) && M >= 4096 && N >= 512) {      // (tuning value 2: not for the gated weights_in)
       const int tiles_b = ((M + F8M - 1) / F8M) * ((N + F8BN - 1) / F8BN);
       hipLaunchKernelGGL(gemm_fp8mx_256x256x128_kernel, dim3(tiles_b), dim3(1024), LDS8C, s, A, lda, W, ldw, M, N, K, e, gm);
+      gemm_form_launched(FORM_FP8MX2_256X256);
       return hipGetLastError() == hipSuccess ? 0 : 3;
     }
     if (e.w_bs) hipLaunchKernelGGL(gemm_fp8mx_256x128_kernel<true>, dim3(tiles), dim3(512), LDS8MX, s, A, lda, W, ldw, M, N, K, e, gm);
     else hipLaunchKernelGGL(gemm_fp8mx_256x128_kernel<false>, dim3(tiles), dim3(512), LDS8MX, s, A, lda, W, ldw, M, N, K, e, gm);
+    gemm_form_launched(e.w_bs ? FORM_FP8MX2_256X128 : FORM_FP8MX_256X128);
     return hipGetLastError() == hipSuccess ? 0 : 3;
   }
   fp8_attr();
   const int gm = N >= 3072 ? 8 : (N >= 2048 ? 4 : 2);
   const int tiles = ((M + F8M - 1) / F8M) * ((N + F8N - 1) / F8N);
   hipLaunchKernelGGL(gemm_fp8_256x128_kernel, dim3(tiles), dim3(512), LDS8, s, A, lda, W, ldw, M, N, K, e, gm);
+  gemm_form_launched(FORM_FP8_ROWS);
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 

@@ -512,6 +512,7 @@ int launch_gemm_bf16_ppm(const bf16_t* A, int lda, const bf16_t* W, int ldw, int
   ppm_attr();
   int gm = gemm_tile_mode();
   const int tiles = wres_grid(M, N, &gm);
+  gemm_form_launched(FORM_PPM);
 #define GO_(LN_) hipLaunchKernelGGL((gemm_ppm_256x256_kernel<false, false, LN_>), dim3(tiles), dim3(512), LDSPP, s, A, lda, W, ldw, M, N, K, e, gm);
   LN_DISPATCH(e, GO_)
 #undef GO_
@@ -528,6 +529,7 @@ int launch_gemm_x3_pp(const bf16_t* A2, int lda, const bf16_t* W2, int ldw, int 
   ppm_attr();
   int gm = gemm_tile_mode();
   const int tiles = wres_grid(M, N, &gm);
+  gemm_form_launched(FORM_X3_PP);
 #define GO_(LN_) hipLaunchKernelGGL((gemm_ppm_256x256_kernel<true, false, LN_>), dim3(tiles), dim3(512), LDSPP, s, A2, lda, W2, ldw, M, N, K, e, gm);
   LN_DISPATCH(e, GO_)
 #undef GO_
@@ -560,6 +562,7 @@ int launch_gemm_h2(const void* A, int lda, const void* W, int ldw, int M, int N,
   h2_attr();
   const int gm = gemm_tile_mode();
   const int tiles = ((M + PPM - 1) / PPM) * ((N + PPN - 1) / PPN);
+  gemm_form_launched(FORM_H2);
 #define GO_(LN_) hipLaunchKernelGGL(gemm_h2_256x256_kernel<LN_>, dim3(tiles), dim3(512), LDSH2, s, (const char*)A, lda, (const char*)W, ldw, M, N, K, e, gm);
   LN_DISPATCH(e, GO_)
 #undef GO_
@@ -727,6 +730,7 @@ int gemm_tail_split(int kind, const void* A, int lda, const void* W, int ldw, in
   es.out_f32 = scratch; es.ldc = N; es.h2_wexp = e.h2_wexp;
   es.ksplit = S; es.kslice_len = K / S; es.kslice_stride = (long long)slab;
   const int gm = gemm_tile_mode() & 0xfff;          // no start stagger
+  gemm_form_launched(kind == 2 ? FORM_H2 : (kind == 1 ? FORM_X3_PP : FORM_PPM));      // the K-split launch runs the family's ping-pong kernel
   if (kind == 2) {
     h2_attr();
     const char* Ar = (const char*)A + (size_t)Mmain * lda;

@@ -323,6 +323,7 @@ int launch_gemm_x3(const bf16_t* A2, int lda, const bf16_t* W2, int ldw, int M, 
 #define GO_(LN_) hipLaunchKernelGGL((gemm_x3_256x256_kernel<false, LN_>), dim3(tiles), dim3(1024), LDSX3, s, A2, lda, W2, ldw, M, N, K, e, gm);
   LN_DISPATCH(e, GO_)
 #undef GO_
+  gemm_form_launched(FORM_X3_16W);
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
@@ -335,6 +336,7 @@ int launch_gemm_bf16_k64(const bf16_t* A, int lda, const bf16_t* W, int ldw, int
   x3_attr();
   const int gm = gemm_tile_mode();
   const int tiles = ((M + X3M - 1) / X3M) * ((N + X3N - 1) / X3N);
+  gemm_form_launched(FORM_K64);
   // plain bf16 rows (QKV, fc1 of the bf16 mode): the register epilogue.  Test option DOD_OPT_EPI_REGMATH, read once per launch: 0 = the
   // LDS-staged epilogue.  A template parameter, so that neither form carries the other's registers
   if (dod_option(DOD_OPT_EPI_REGMATH) != 0 && epi_regmath_ok(e, N)) {

@@ -244,5 +244,6 @@ int launch_patch_embed(const void* img, int u8, int B, int H, int W, int p, cons
     else { if (u8) PE_LAUNCH(false, true, 16); else PE_LAUNCH(false, false, 16); }
   }
 #undef PE_LAUNCH
+  gemm_form_launched(FORM_PATCH_FUSED);
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }

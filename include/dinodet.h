@@ -667,6 +667,13 @@ int dod_reserve_gemm_scratch(size_t bytes);
  * launch of its own (gemm_bf16.hip); "f32_ksplits": fp32 GEMM launches that split K across workgroups (gemm_f32.hip); "epi_regmath": launches
  * of the 16-wave bf16 GEMM that took the register epilogue; "f32x3_launches": launches of the fp32-in bf16 split GEMM, "f32x3_wide_launches": those
  * that took its 128x128 tile; "attn_diet": bf16 attention launches whose last key tile ran at half width; -1 for an unknown name.
+ * Kernel launches per inference GEMM form, counted by the launchers (a call the heuristics cut in two counts each part under its own form; a
+ * tail split's K-split launch counts under its family's ping-pong form, its reduce launch under none):
+ *   "form_bf16_128_r2" / "form_bf16_128_r3"  gemm_bf16.hip 128x128 tile on a 2- / 3-slot ring;  "form_bf16_m16"  its 256x128 tile
+ *   "form_k64"  16-wave 256x256 plain bf16 (gemm_x3.hip, either epilogue);  "form_ppm"  ping-pong 256x256 plain bf16 (gemm_pp.hip)
+ *   "form_x3_16w" / "form_x3_pp"  split product on the 16-wave / the ping-pong kernel;  "form_h2"  the H2 kernel
+ *   "form_fp8_rows"  per-row scaled e4m3;  "form_fp8mx_256x128"  block-scaled A;  "form_fp8mx2_256x128" / "form_fp8mx2_256x256"  both operands
+ *   block-scaled on the 256x128 / the 256x256 tile;  "form_f32"  gemm_f32.hip;  "form_patch_fused"  the fused patch embedding (patch_embed.hip)
  * The in-kernel time stamps, the register-only MFMA probes and every tile / schedule override of the tuning rounds exist only in
  * -DDINODET_TUNING builds (include/dinodet_tuning.h); the release library exports none of them. */
 int dod_test_set_option(const char* name, int value);

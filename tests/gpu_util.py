@@ -7,6 +7,44 @@ import torch
 from dinov2_od_amd import _native as nat
 from dinov2_od_amd import synth
 from dinov2_od_amd.models import DINOv2ObjectDetector, DINOv2Backbone, DETRDecoder
+from tests.attention_cases import GUARD
+
+# dtype -> (integer view, guard pattern, pattern of a not yet written element): both float patterns are NaNs, 0x7f is e4m3's NaN
+PATTERN = {torch.bfloat16: (torch.int16, 0x7FA5, 0x7FC1), torch.float32: (torch.int32, 0x7FC0A5A5, 0x7FC00001), torch.uint8: (torch.uint8, 0xA5, 0x7F)}
+
+
+class Out:
+    """[GUARD + rows + GUARD, ld] of `dtype`: the guard pattern around the rows and in their pad columns width..ld-1, the unwritten pattern
+    inside.  `view` is the [rows, ld] block a kernel is handed (ld == width: the contiguous output), `data` its first `width` columns."""
+
+    def __init__(self, rows, width, dtype, unwritten=None, ld=None, device="cuda"):
+        it, self.guard, fill = PATTERN[dtype]
+        self.fill = fill if unwritten is None else unwritten
+        self.rows, self.width, self.ld = rows, width, width if ld is None else ld
+        assert self.ld >= width
+        self.raw = torch.full((rows + 2 * GUARD, self.ld), self.guard, dtype=it, device=device)
+        self.raw[GUARD:GUARD + rows, :width] = self.fill
+        self.view = self.raw[GUARD:GUARD + rows].view(dtype)
+        self.data = self.view[:, :width]
+
+    def guards_intact(self):
+        """guard rows and pad columns"""
+        return (bool((self.raw[:GUARD] == self.guard).all()) and bool((self.raw[GUARD + self.rows:] == self.guard).all())
+                and bool((self.raw[GUARD:GUARD + self.rows, self.width:] == self.guard).all()))
+
+    def unwritten(self):
+        """number of elements that still hold the unwritten pattern"""
+        return int((self.raw[GUARD:GUARD + self.rows, :self.width] == self.fill).sum())
+
+
+def guarded_input(t, ld=None, pad=float("nan")):
+    """[rows, W] -> the same rows, at pitch ld >= W, inside ONE buffer whose other rows and pad columns hold `pad` (NaN; 0x7f for e4m3 bytes):
+    the [rows, ld] view; its first W columns are the operand"""
+    rows, W = t.shape
+    ld = W if ld is None else ld
+    full = torch.full((rows + 2 * GUARD, ld), pad, dtype=t.dtype, device=t.device)
+    full[GUARD:GUARD + rows, :W] = t
+    return full[GUARD:GUARD + rows]
 
 
 def dev():

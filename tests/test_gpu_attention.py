@@ -27,6 +27,7 @@ import torch
 
 from dinov2_od_amd import _native as nat
 from tests import attention_cases as ac
+from tests.gpu_util import PATTERN, Out, guarded_input as _guarded_input
 from tests.test_gpu_fp8 import ACC_TOL, quant_ref
 from tests.test_gpu_h2 import decode as h2_decode, pack as h2_pack
 
@@ -35,8 +36,6 @@ pytestmark = pytest.mark.gpu
 GUARD = ac.GUARD
 DEV = "cuda"
 BF16, F32, U8 = torch.bfloat16, torch.float32, torch.uint8
-# dtype -> (integer view, guard pattern, pattern of a not yet written element): both float patterns are NaNs, 0x7f is e4m3's NaN
-PATTERN = {BF16: (torch.int16, 0x7FA5, 0x7FC1), F32: (torch.int32, 0x7FC0A5A5, 0x7FC00001), U8: (torch.uint8, 0xA5, 0x7F)}
 FLASH = ["bf16", "mx", "x3", "h2"]
 WORST = {}      # kernel -> (error / bound, where); X3_DIST: kernel -> (largest emulation distance, where)
 DIST = {}
@@ -52,28 +51,6 @@ def G():
         print(f"attention worst  {k:<6s} {WORST[k][0]:.3f} of its per-element bound at {WORST[k][1]}")
     for k in sorted(DIST):
         print(f"attention reference distance  {k:<6s} {DIST[k][0]:.3e} T at {DIST[k][1]}")
-
-
-class Out:
-    """[GUARD + rows + GUARD, width] of `dtype`: the guard pattern around, the unwritten pattern inside"""
-
-    def __init__(self, rows, width, dtype, unwritten=None):
-        it, self.guard, fill = PATTERN[dtype]
-        self.rows = rows
-        self.raw = torch.full((rows + 2 * GUARD, width), self.guard, dtype=it, device=DEV)
-        self.raw[GUARD:GUARD + rows] = fill if unwritten is None else unwritten
-        self.view = self.raw[GUARD:GUARD + rows].view(dtype)
-
-    def guards_intact(self):
-        return bool((self.raw[:GUARD] == self.guard).all()) and bool((self.raw[GUARD + self.rows:] == self.guard).all())
-
-
-def _guarded_input(t):
-    """CUDA [rows, W] -> the same rows inside a buffer whose other rows are NaN"""
-    rows, W = t.shape
-    full = torch.full((rows + 2 * GUARD, W), float("nan"), dtype=t.dtype, device=DEV)
-    full[GUARD:GUARD + rows] = t
-    return full[GUARD:GUARD + rows]
 
 
 def _hold(kernel, where, got, want, bound):
