@@ -25,12 +25,8 @@ def _staging(nbytes):
     return _STAGE
 
 
-def preprocess_batch(images, size=(224, 224), device="cuda", as_uint8=False):
-    """images: sequence of uint8 RGB images [H_i, W_i, 3] (numpy arrays, torch tensors or PIL images); size: (height, width)
-    as torchvision's Resize takes it.  Returns float32 [B, 3, height, width] on `device` -- or, with as_uint8, the resampled
-    bytes uint8 [B, height, width, 3] (before ToTensor) for `model.forward_packed_u8`, whose patch-embedding kernel divides by 255
-    in its load stage: the fp32 batch then never goes through HBM."""
-    out_h, out_w = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+def _as_arrays(images):
+    """the batch as contiguous uint8 [H, W, 3] numpy arrays"""
     arrs = []
     for im in images:
         a = im.cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
@@ -39,15 +35,16 @@ def preprocess_batch(images, size=(224, 224), device="cuda", as_uint8=False):
         arrs.append(np.ascontiguousarray(a))
     if not arrs:
         raise ValueError("empty batch")
-    B = len(arrs)
+    return arrs
+
+
+def _stage(arrs, dev):
+    """the raw bytes gathered straight into a (cached) pinned staging buffer: one host copy, one DMA to the device.
+    Returns (src on the device, src_offs, heights, widths) -- the last three on the host."""
     hs = np.array([a.shape[0] for a in arrs], dtype=np.int32)
     ws = np.array([a.shape[1] for a in arrs], dtype=np.int32)
     sizes = hs.astype(np.int64) * ws * 3
     src_offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
-    tsz = hs.astype(np.int64) * out_w * 3
-    tmp_offs = np.concatenate([[0], np.cumsum(tsz)[:-1]]).astype(np.int64)
-    dev = torch.device(device)
-    # the raw bytes are gathered straight into a (cached) pinned staging buffer: one host copy, one DMA to the device
     total = int(sizes.sum())
     stage = _staging(total)
     sv = stage.numpy()
@@ -57,6 +54,25 @@ def preprocess_batch(images, size=(224, 224), device="cuda", as_uint8=False):
     global _STAGE_BUSY
     _STAGE_BUSY = torch.cuda.Event()
     _STAGE_BUSY.record()
+    return src, src_offs, hs, ws
+
+
+def _out_size(size):
+    return (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+
+
+def preprocess_batch(images, size=(224, 224), device="cuda", as_uint8=False):
+    """images: sequence of uint8 RGB images [H_i, W_i, 3] (numpy arrays, torch tensors or PIL images); size: (height, width)
+    as torchvision's Resize takes it.  Returns float32 [B, 3, height, width] on `device` -- or, with as_uint8, the resampled
+    bytes uint8 [B, height, width, 3] (before ToTensor) for `model.forward_packed_u8`, whose patch-embedding kernel divides by 255
+    in its load stage: the fp32 batch then never goes through HBM."""
+    out_h, out_w = _out_size(size)
+    arrs = _as_arrays(images)
+    B = len(arrs)
+    dev = torch.device(device)
+    src, src_offs, hs, ws = _stage(arrs, dev)
+    tsz = hs.astype(np.int64) * out_w * 3
+    tmp_offs = np.concatenate([[0], np.cumsum(tsz)[:-1]]).astype(np.int64)
     meta = [torch.from_numpy(x).to(dev) for x in (src_offs, hs, ws, tmp_offs)]
     tmp = torch.empty(int(tsz.sum()), dtype=torch.uint8, device=dev)
     if as_uint8:

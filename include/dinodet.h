@@ -311,6 +311,34 @@ int dod_preprocess_u8(const uint8_t* src, const int64_t* src_offs, const int32_t
                       int max_h, int max_w, int out_h, int out_w, uint8_t* tmp, const int64_t* tmp_offs, uint8_t* out_hwc,
                       void* stream);
 
+/* Train-time augmentation in the same two passes (Python mirror: dinov2_od_amd/augment.py), Pillow-exact and in this order per
+ * image b:  img.crop(box) -> ImageEnhance.Brightness / .Contrast / .Color (in that order) -> resize((out_w, out_h), BILINEAR) ->
+ * transpose(FLIP_LEFT_RIGHT) -> ToTensor.
+ *   crops   int32 [B, 4]: (left, top, width, height), a box inside image b (0 <= left, left + width <= widths[b], width >= 1,
+ *           likewise vertically).  The kernels skip an image whose box is not, leaving its output unwritten; the caller validates.
+ *           Pixels outside the box never enter a filter window (crop-then-resize).
+ *   flips   uint8 [B]: non-zero mirrors the resized image left-right.
+ *   jitter  float [B, 3]: the brightness, contrast and saturation factors, each finite and >= 0, 1.0 = identity; NULL = no jitter
+ *           (the geometric-only call: no more bytes read than dod_preprocess on the same boxes).
+ *   lsum    uint64 [B] caller-owned workspace of the contrast step: the call zeroes it on `stream` and sums every crop's luma into
+ *           it before the horizontal pass.  It may be NULL when every contrast factor is 1.0 (host-known to the caller): the
+ *           reduction is then not launched and the contrast step is skipped.
+ *   max_crop_h / max_crop_w (host): the largest crop height / width; they bound the grid and the filter width
+ *           (ceil(crop / out) * 2 + 1 <= 32 taps, else DOD_ERR_INVALID).
+ * tmp: image b at tmp + tmp_offs[b]: (crop height of b) * out_w * 3 bytes when jitter is NULL, (crop height) * (out_w + crop
+ * width) * 3 bytes otherwise -- the jittered crop is written once behind the horizontal pass's rows, so that every source pixel is
+ * jittered once and not once per filter tap.  All pointers are device pointers; heights / widths are those of the source images, as
+ * in dod_preprocess. */
+int dod_preprocess_aug(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
+                       const int32_t* crops, const uint8_t* flips, const float* jitter, uint64_t* lsum, int max_crop_h,
+                       int max_crop_w, int out_h, int out_w, uint8_t* tmp, const int64_t* tmp_offs, float* out, void* stream);
+
+/* as dod_preprocess_aug, stopping before ToTensor: out_hwc = uint8 [B, out_h, out_w, 3], the input of dod_forward_u8 */
+int dod_preprocess_aug_u8(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
+                          const int32_t* crops, const uint8_t* flips, const float* jitter, uint64_t* lsum, int max_crop_h,
+                          int max_crop_w, int out_h, int out_w, uint8_t* tmp, const int64_t* tmp_offs, uint8_t* out_hwc,
+                          void* stream);
+
 /* ---- Hungarian-matcher cost matrices on device -------------------------------------
  * Replaces the per-image cost computation of HungarianMatcher.forward, dino_detector/matching.py:79-98 (focal class
  * cost :80-86, L1 box cost :89, GIoU cost :92-95 with utils.py:124-164, weighted sum :98) for the whole batch.
@@ -687,7 +715,8 @@ const char* dod_version(void);
  * needs them resolves them by name (the Python binding fails at load when one is missing).  The training-step operators
  * (dod_op_layernorm_bwd ... dod_op_colsum_add) joined revision 6 the same way.  So did the optimizer step (dod_optim_*), the deep-supervision
  * step (dod_decoder_train_aux_*), the layered criterion (dod_set_criterion_layers_*) and the split-product operators (dod_op_gemm_f32x3,
- * dod_op_linear_f32x3; the training entry points reading cfg->precision changes no signature either).
+ * dod_op_linear_f32x3; the training entry points reading cfg->precision changes no signature either) and the train-time augmentation
+ * (dod_preprocess_aug, dod_preprocess_aug_u8).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);
