@@ -197,6 +197,7 @@ SYMBOLS = {
     "dod_reserve_gemm_scratch": (_I, [C.c_size_t]),
     "dod_test_set_option": (_I, [C.c_char_p, _I]),
     "dod_test_counter": (C.c_long, [C.c_char_p]),
+    "dod_test_gemm_plan": (_I, [_I, _I, _I, _I, C.c_uint, _I, C.c_size_t, _P, _I]),
     "dod_version": (C.c_char_p, []),
     "dod_abi_version": (_I, []),
     "dod_device_count": (_I, []),
@@ -243,6 +244,20 @@ def lib():
             pass
         _lib = L
     return _lib
+
+
+class DodGemmStep(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("form", "row0", "rows", "kslices", "regmath", "gm")]
+
+
+def gemm_plan(family, M, N, K, epi_flags, cus, scratch_bytes):
+    """dod_test_gemm_plan (include/dinodet.h): the launches the inference GEMM launchers would make, as (form, row0, rows, kslices, regmath, gm)
+    tuples in launch order.  Host only: no device is touched"""
+    steps = (DodGemmStep * 4)()
+    n = lib().dod_test_gemm_plan(family, M, N, K, epi_flags, cus, scratch_bytes, steps, 4)
+    if n < 0:
+        raise ValueError(f"dod_test_gemm_plan rejected family={family} M={M} N={N} K={K} cus={cus}")
+    return [(s.form, s.row0, s.rows, s.kslices, s.regmath, s.gm) for s in steps[:n]]
 
 
 def set_option(name, value):

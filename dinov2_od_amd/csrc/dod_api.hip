@@ -1,6 +1,7 @@
 // C ABI of libdinodet.so: handle life cycle, the forward entry points and the stateless dod_op_* operators.
 // See include/dinodet.h for the contract; dod_pack.hip packs the weights, dod_forward.hip holds the forward schedules.
 #include "dod_internal.h"
+#include "gemm_plan.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -71,6 +72,17 @@ long dod_test_counter(const char* name) {
     for (int i = 0; i < FORM_COUNT; ++i)
       if (!strcmp(name + 5, k_form_names[i])) return g_form_launches[i].load();
   return -1;
+}
+
+int dod_test_gemm_plan(int family, int M, int N, int K, unsigned epi_flags, int cus, size_t scratch_bytes, dod_gemm_step* steps, int max_steps) {
+  if (family < GEMM_BF16 || family > GEMM_F32 || M <= 0 || N <= 0 || K <= 0 || cus <= 0 || !steps) return -1;
+  const GemmPlan pl = gemm_plan(family, M, N, K, epi_flags, gemm_policy(cus, scratch_bytes, scratch_bytes > 0));
+  if (pl.n > 4 || pl.n > max_steps) return -1;
+  for (int i = 0; i < pl.n; ++i) {
+    const GemmStep& st = pl.step[i];
+    steps[i].form = st.form; steps[i].row0 = st.row0; steps[i].rows = st.rows; steps[i].kslices = st.kslices; steps[i].regmath = st.regmath; steps[i].gm = st.gm;
+  }
+  return pl.n;
 }
 
 const char* dod_version(void) { return "dinodet 0.3 (gfx950)"; }

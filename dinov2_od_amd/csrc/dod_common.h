@@ -32,16 +32,17 @@ enum { DOD_OPT_TAILSPLIT = 0,         // GEMM wave-quantisation tail split: 0 of
        DOD_OPT_ATTN_DIET,             // bf16 flash attention (attn_bf16.hip): 0 = the full-width tail key tile and per-lane pointer staging, 1 = half tail tile + descriptor staging (shipped)
        DOD_OPT_COUNT };
 int dod_option(int which);            // dod_api.hip; -1 when unset
-long gemm_tail_split_count();         // gemm_pp.hip: GEMM calls that took the tail-split path so far
+long gemm_tail_split_count();         // gemm_dispatch.hip: GEMM calls that took the tail-split path so far
 long optim_launch_count();            // optim.hip: launches of the optimizer entries so far
 long optim_constant(int which);       // optim.hip: 0 elements per workgroup, 1 / 2 tensors per update / norm launch
-long gemm_rem_cut_count();            // gemm_bf16.hip: GEMM calls whose short last round ran as a launch of its own
+long gemm_rem_cut_count();            // gemm_dispatch.hip: GEMM calls whose short last round ran as a launch of its own
 long attn_half_tile_count();          // attn_bf16.hip: attention launches whose last key tile ran at half width
-long gemm_epi_regmath_count();        // gemm_x3.hip: launches of the 16-wave bf16 GEMM that took the register epilogue
-// kernel launches per inference GEMM form so far (dod_api.hip; dod_test_counter("form_<name>"), names in include/dinodet.h): counted by the launchers
+long gemm_epi_regmath_count();        // gemm_dispatch.hip: launches of the 16-wave bf16 GEMM that took the register epilogue
+// kernel launches per inference GEMM form so far (dod_api.hip; dod_test_counter("form_<name>"), names in include/dinodet.h): counted by gemm_dispatch
 enum { FORM_BF16_128_R2 = 0, FORM_BF16_128_R3, FORM_BF16_M16, FORM_K64, FORM_PPM, FORM_X3_16W, FORM_X3_PP, FORM_H2, FORM_FP8_ROWS, FORM_FP8MX_256X128,
        FORM_FP8MX2_256X128, FORM_FP8MX2_256X256, FORM_F32, FORM_PATCH_FUSED, FORM_COUNT };
 void gemm_form_launched(int form);
+enum { GEMM_BF16 = 0, GEMM_X3, GEMM_H2, GEMM_FP8, GEMM_F32 };      // inference GEMM family = operand format = the public launcher called
 
 #ifdef DINODET_TUNING
 #define DOD_TUNE_ENV(name) getenv(name)
@@ -349,22 +350,35 @@ int launch_split2(const float* in, int ld_in, bf16_t* out, int rows, int K, hipS
 int launch_split_h2(const float* in, int ld_in, void* out, int rows, int K, unsigned char* wexp, hipStream_t s);
 // H2 GEMM (gemm_pp.hip): A [M, K] activation rows (pitch lda BYTES >= 4K), W [N, K] weight rows (pitch ldw BYTES >= 3K), e.h2_wexp set
 int launch_gemm_h2(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s);
-// Wave-quantisation tail of the 256x256-tile GEMMs (gemm_pp.hip): when tiles % CUs leaves a short last round (1029 tiles on 256
-// CUs: a fifth round for five tiles, +24 %), the rows of that round are cut off the main launch and computed by a K-SPLIT launch
-// (every tile of the remainder as S slices on S CUs, fp32 partials to a scratch buffer) plus a reduce + epilogue launch.
-// kind: 0 plain bf16 (ppm kernel), 1 split product, 2 H2.  Returns 0 when done, -1 when the shape does not qualify (caller
-// launches normally), > 0 on error.  gemm_tail_reserve(bytes): allocate the scratch outside any stream capture.  The scratch is one
-// slab per launching stream (four per device, least-recently-used first: a forward may run as two concurrent micro-batches on two
-// streams, engine.py).  The slices are summed in a fixed order, so results do not depend on scheduling.
-int gemm_tail_split(int kind, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s);
-int gemm_tail_reserve(size_t bytes);
 // split-product GEMM on pair-layout operands A2 [M, 2K], W2 [N, 2K] (gemm_x3.hip)
-int launch_gemm_bf16_k64(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s);
-int gemm_tile_mode();   // tile-order mode word of the 256-row kernels (gemm_x3.hip; gemm_epi.h tile_map)
-// 256x256x64 ping-pong kernel (gemm_pp.hip): K % 64 == 0
-int launch_gemm_bf16_ppm(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s);
-int launch_gemm_x3_pp(const bf16_t* A2, int lda, const bf16_t* W2, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s);
 int launch_gemm_x3(const bf16_t* A2, int lda, const bf16_t* W2, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s);
+// ---- Dispatch of the five inference launchers above (launch_gemm_bf16 / _x3 / _h2 / _fp8 / _f32): each checks its arguments and calls
+// gemm_dispatch (gemm_dispatch.hip), which gathers the policy inputs, asks gemm_plan (gemm_plan.h: the ONE statement of which form runs which
+// rows with how many K slices) and runs every step through the form's own run_* function below.  A run_* function decides nothing: it
+// launches its form on the rows it is given (A and e already moved to the step's first row) and returns 0, or 3 when the launch failed (2: a
+// step its kernel cannot run).  family: GEMM_*; allow_ksplit: launch_gemm_f32's.
+int gemm_dispatch(int family, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s, bool allow_ksplit = false);
+int device_cus();       // CU count of the current device, looked up once per device (256 when it cannot be read)
+struct KernelLds { const void* fn; int bytes; };
+// kernels that need more than 64 KiB of dynamic LDS: hipFuncSetAttribute once per device; done = the caller's static bool[16]
+void gemm_lds_attr_once(bool* done, const KernelLds* k, int n);
+int gemm_tile_mode();   // tile-order mode word of the 256-row kernels (gemm_x3.hip; gemm_epi.h tile_map)
+int run_gemm_bf16_128(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, int slots, hipStream_t s);      // gemm_bf16.hip
+int run_gemm_bf16_m16(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, int gm, hipStream_t s);
+int run_gemm_x3_16w(const bf16_t* A2, int lda, const bf16_t* W2, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s);                 // gemm_x3.hip
+int run_gemm_k64(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, bool regmath, hipStream_t s);
+int run_gemm_pp(bool x3, const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s);            // gemm_pp.hip
+int run_gemm_h2(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s);
+int run_gemm_ksplit_reduce(const float* part, int S, int R, int N, const GemmEpi& e, int m_base, int M, int K, hipStream_t s);
+int run_gemm_fp8(int form, const unsigned char* A, int lda, const unsigned char* W, int ldw, int M, int N, int K, const GemmEpi& e, int gm, hipStream_t s);      // gemm_fp8.hip
+int run_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int N, int K, const GemmEpi& e, int S, hipStream_t s);               // gemm_f32.hip
+// Scratch of the tail split's K-split launch (gemm_pp.hip): gemm_tail_reserve(bytes) allocates it outside any stream capture.  One slab of
+// `bytes` per launching stream (four per device, least-recently-used first: a forward may run as two concurrent micro-batches on two
+// streams, engine.py).  The slices are summed in a fixed order, so results do not depend on scheduling.
+int gemm_tail_reserve(size_t bytes);
+size_t gemm_tail_reserved();              // bytes per slab on the current device (0: none)
+float* gemm_tail_slab(hipStream_t s);     // the launching stream's slab
+bool gemm_f32_ksplit_reserved();          // gemm_f32.hip: the current device has the fp32 K split's slabs
 // tgt[b][q][:] = query_embed[q][:]
 int launch_bcast_rows(const float* src, float* dst, int B, int rows, int D, hipStream_t s);
 

@@ -18,7 +18,6 @@
 // contiguous run, so the ~64 tiles resident on an XCD share 8 A panels and 8 W panels (3 MiB < 4 MiB L2).
 #include "dod_common.h"
 #include "gemm_epi.h"
-#include <atomic>
 #include <cstdlib>
 
 #define BM 128
@@ -294,8 +293,38 @@ static constexpr int LDS128 = (BM * (BN * 4 + 16)) > 2 * STAGE_BYTES ? (BM * (BN
 static constexpr int LDS128R = 3 * STAGE_BYTES;
 static constexpr int LDS5 = (128 * (B5N * 4 + 16)) > B5_SLOTS * B5_STAGE ? (128 * (B5N * 4 + 16)) : B5_SLOTS * B5_STAGE;
 
-static std::atomic<long> g_rem_cuts{0};
-long gemm_rem_cut_count() { return g_rem_cuts.load(); }
+static void bf16_attr() {      // > 64 KiB of dynamic LDS: once per device
+  static bool done[16] = {};
+#define ATTR_(LN_) {reinterpret_cast<const void*>(gemm_bf16_kernel<LN_, 2>), LDS128}, {reinterpret_cast<const void*>(gemm_bf16_kernel<LN_, 3>), LDS128R}, \
+                   {reinterpret_cast<const void*>(gemm_bf16_256x128_m16_kernel<LN_>), LDS5},
+  static const KernelLds k[] = {ATTR_(LN_NONE) ATTR_(LN_CONS) ATTR_(LN_PROD)};
+#undef ATTR_
+  gemm_lds_attr_once(done, k, sizeof k / sizeof k[0]);
+}
+
+// FORM_BF16_128_R2 / FORM_BF16_128_R3: the 128x128 tile on a ring of `slots` K-tiles
+int run_gemm_bf16_128(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, int slots, hipStream_t s) {
+  bf16_attr();
+  const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+#define GO_128(LN_) hipLaunchKernelGGL((gemm_bf16_kernel<LN_, 2>), dim3(tiles), dim3(256), LDS128, s, A, lda, W, ldw, M, N, K, e);
+#define GO_128R(LN_) hipLaunchKernelGGL((gemm_bf16_kernel<LN_, 3>), dim3(tiles), dim3(256), LDS128R, s, A, lda, W, ldw, M, N, K, e);
+  if (slots == 3) { LN_DISPATCH(e, GO_128R) }
+  else { LN_DISPATCH(e, GO_128) }
+#undef GO_128
+#undef GO_128R
+  return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+// FORM_BF16_M16: the 256x128 tile; gm = grouped-order depth (m-tiles per group inside an XCD's run)
+int run_gemm_bf16_m16(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, int gm, hipStream_t s) {
+  bf16_attr();
+  const int gm5 = gm | (gemm_tile_mode() & 0x300);
+  const int tiles5 = ((M + B5M - 1) / B5M) * ((N + B5N - 1) / B5N);
+#define GO_M16(LN_) hipLaunchKernelGGL(gemm_bf16_256x128_m16_kernel<LN_>, dim3(tiles5), dim3(512), LDS5, s, A, lda, W, ldw, M, N, K, e, gm5);
+  LN_DISPATCH(e, GO_M16)
+#undef GO_M16
+  return hipGetLastError() == hipSuccess ? 0 : 3;
+}
 
 int launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K,
                      const GemmEpi& e, hipStream_t s) {
@@ -303,102 +332,8 @@ int launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, 
   if (K % BK != 0 || N % 4 != 0 || lda % 8 != 0 || ldw % 8 != 0 || e.ldc % 4 != 0) return 2;
   if (e.resid && e.ldr % 4 != 0) return 2;
   if (!e.out_f32 && !e.out_bf16) return 2;
-  static bool attr_set[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-#define ATTR_(LN_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_kernel<LN_, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS128); \
-                   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_kernel<LN_, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS128R); \
-                   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_256x128_m16_kernel<LN_>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS5);
-    ATTR_(LN_NONE) ATTR_(LN_CONS) ATTR_(LN_PROD)
-#undef ATTR_
-    attr_set[dev] = true;
-  }
-  const char* force = DOD_TUNE_ENV("DINODET_GEMM_TILE");     // tuning builds: "q" ping-pong, "x" 16-wave k64, "8" 256x128, "1" 128x128
-  if (!force && M >= 2048 && N >= 512 && e.act != ACT_GELU && e.act != ACT_SIGMOID && e.rows_per_img == 0 && K % 64 == 0) {   // the 256x256-tile shapes
-    const int t = gemm_tail_split(0, A, lda, W, ldw, M, N, K, e, s);      // short last round (M >= 8192), or a grid of a few dozen tiles (M >= 2048)
-    if (t >= 0) return t;
-  }
-  if (force && force[0] == 'q' && K % 64 == 0) return launch_gemm_bf16_ppm(A, lda, W, ldw, M, N, K, e, s);
-  if (force && force[0] == 'x') return launch_gemm_bf16_k64(A, lda, W, ldw, M, N, K, e, s);
-  // grouped-order depth of the 256x128 kernel (m-tiles per group inside an XCD's run), measured: 8 for N = 3072, 4 for 2304, 2 for 768
-  const int gm5 = (N >= 3072 ? 8 : (N >= 2048 ? 4 : 2)) | (gemm_tile_mode() & 0x300);
-  const int tiles5 = ((M + B5M - 1) / B5M) * ((N + B5N - 1) / B5N);
-#define GO_M16(LN_) hipLaunchKernelGGL(gemm_bf16_256x128_m16_kernel<LN_>, dim3(tiles5), dim3(512), LDS5, s, A, lda, W, ldw, M, N, K, e, gm5);
-  if (!force && M >= 4096 && N >= 512 && K % 64 == 0 && e.act != ACT_SIGMOID && e.rows_per_img == 0) {
-    // Round-aware choice between the 256x256 tiles (one workgroup per CU: the 16-wave `k64` kernel of gemm_x3.hip -- 256x256x64, two 64-KiB
-    // slots: QKV 760 / out-proj 460 / fc2 765 TFLOP/s at M = 87 680 -- or the 8-wave ping-pong kernel of gemm_pp.hip, 3-7 % faster on
-    // N >= 1536 at every M measured) and the 256x128 tile (`m16`, two co-resident workgroups per CU that run at about half speed each, so
-    // one of its tiles costs ~0.55 of a 256x256 tile only while a CU holds a single one).  Cost in units of a 256x256 tile time = rounds
-    // of CUs x tile cost; a GELU epilogue costs the one-workgroup-per-CU kernels ~8 % (nothing overlaps it).
-    // tools/bench_pp.py --rows {4112, 8224, 16448, 21920, 43840, 87680}: the rule reproduces the faster kernel in 27 of 28 cases
-    // (M = 8224, batch 32 at 224x224: QKV 46 vs 53 us, out-proj 27 vs 32, fc1 66 vs 78, fc2 59 vs 75).
-    static int cus[16] = {};
-    if (dev >= 0 && dev < 16 && !cus[dev]) { int c = 0; (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev); cus[dev] = c > 0 ? c : 256; }
-    const int cu = (dev >= 0 && dev < 16) ? cus[dev] : 256;
-    const long tm = (M + 255) / 256, t_big = tm * ((N + 255) / 256), t_small = tm * ((N + 127) / 128);
-    const double c_big = (double)((t_big + cu - 1) / cu) * (e.act == ACT_GELU ? 1.08 : 1.0);
-    const double c_small = (double)((t_small + cu - 1) / cu) * (K >= 2048 ? 0.62 : 0.55);      // long K: the smaller tile's lower FLOP per staged byte shows
-    // Round 4: with its epilogue passes written out the 16-wave kernel holds its accumulators in registers (it had spilled 34 of them since
-    // round 1) and is the fastest choice for EVERY wide GEMM (N >= 1536: QKV, fc1 incl. its GELU epilogue) at every M measured
-    // (tools/bench_pp.py, rows 8 224 / 10 960 / 43 840 / 87 680: QKV 46.9 / 53.2 / 173.0 / 338.2 us against 51.8 / 56.8 / 186.6 / 345.5 for the
-    // round-3 choice, fc1 59.9 / 87.7 / 264.2 / 518.9 against 63.8 / 104.7 / 297.9 / 548.4); the narrow ones (N = 768) keep the round rule
-    // below, and the long-K narrow one (fc2) the ping-pong kernel behind its tail split.
-    if (N >= 1536 && K < 2048) {
-      // A last round of a few tiles costs these short-K GEMMs a whole tile time when the grid is only one or two rounds deep (8 images of
-      // 518^2: fc1 = 43 x 12 = 516 tiles = two rounds + 4; 32 images of 224^2: QKV = 33 x 9 = 297 = one round + 41).  The m-tiles of that
-      // round are cut off and run as a launch of their own, which the small-M rules below spread over the chip as 128-row tiles.
-      const long rounds = t_big / cu, rem = t_big % cu;
-      static const int rem_div = [] { const char* v = DOD_TUNE_ENV("DINODET_GEMM_REMCUT"); return v ? atoi(v) : 6; }();      // 0: off
-      // (rem >= CUs / 16: a handful of lone tiles finish at well under a tile time -- and a second stream's kernels fill the idle CUs -- so cutting
-      // them costs more than it saves: 2 x 4 images of 518^2, fc1 = 264 tiles, 1 737 against 1 794 images/s with the cut)
-      if (rounds >= 1 && rounds <= 2 && rem * 16 >= cu && rem_div > 0 && rem * rem_div <= cu && gemm_epi_rows_ok(e)) {
-        const int tn = (N + 255) / 256;
-        const int Mmain = (int)((rounds * cu) / tn) * 256, R = M - Mmain;
-        if (Mmain >= 2048 && R > 0 && R < 2048) {
-          const int rc = launch_gemm_bf16_k64(A, lda, W, ldw, Mmain, N, K, e, s);
-          if (rc) return rc;
-          ++g_rem_cuts;
-          return launch_gemm_bf16(A + (size_t)Mmain * lda, lda, W, ldw, R, N, K, gemm_epi_rows(e, Mmain), s);
-        }
-      }
-      return launch_gemm_bf16_k64(A, lda, W, ldw, M, N, K, e, s);
-    }
-    static const double m16_bias = [] { const char* v = DOD_TUNE_ENV("DINODET_GEMM_M16_BIAS"); return v ? atof(v) : 1.02; }();      // tuning builds: > 1 favours the 256x256 tiles
-    if (c_big <= c_small * m16_bias) {
-      if (K >= 2048) return launch_gemm_bf16_ppm(A, lda, W, ldw, M, N, K, e, s);
-      return launch_gemm_bf16_k64(A, lda, W, ldw, M, N, K, e, s);
-    }
-    LN_DISPATCH(e, GO_M16)
-    gemm_form_launched(FORM_BF16_M16);
-    return hipGetLastError() == hipSuccess ? 0 : 3;
-  }
-  // Below that: 256x128x32 on v_mfma_f32_16x16x32_bf16 (two workgroups per CU) from 1 024 rows up, 128x128 for small M (decoder memory at small
-  // batch, tests) -- and for a grid of a few dozen 256x128 tiles (the decoder's query-side linears: B*Q = 3 200 rows at batch 32 -> 78 workgroups
-  // walking K' = 3K = 2 304), which leaves most CUs idle while one workgroup per CU pulls its operands at the per-CU staging rate whatever its
-  // tile: the 128x128 kernel puts the same bytes on twice as many CUs (tools/bench_small_m.py, M = 3200: N = 768 41.5 -> 30.9 us, N = 1024
-  // 42.7 -> 31.9, K = 3072 53.9 -> 38.7; N = 2304 (234 tiles) 47.8 vs 48.4: stays).
-  const bool few = (long)tiles5 * 2 <= 256 + 64;
-  const bool m16 = force ? (force[0] == '8') : (M >= 1024 && N >= 128 && !few);
-  if (m16) {
-    LN_DISPATCH(e, GO_M16)
-    gemm_form_launched(FORM_BF16_M16);
-  } else {
-    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    // a grid of at most one workgroup per CU has nothing beside it to hide its DMA latency: the 3-slot ring (two K-tiles in flight)
-    static const int ring = [] { const char* v = DOD_TUNE_ENV("DINODET_GEMM_RING"); return v ? atoi(v) : 1; }();
-    int cu128 = 256;
-    { static int cus[16] = {}; if (dev >= 0 && dev < 16) { if (!cus[dev]) { int c = 0; (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev); cus[dev] = c > 0 ? c : 256; } cu128 = cus[dev]; } }
-#define GO_128(LN_) hipLaunchKernelGGL((gemm_bf16_kernel<LN_, 2>), dim3(tiles), dim3(256), LDS128, s, A, lda, W, ldw, M, N, K, e);
-#define GO_128R(LN_) hipLaunchKernelGGL((gemm_bf16_kernel<LN_, 3>), dim3(tiles), dim3(256), LDS128R, s, A, lda, W, ldw, M, N, K, e);
-    if (ring && tiles <= cu128 && K >= 3 * BK) { LN_DISPATCH(e, GO_128R) gemm_form_launched(FORM_BF16_128_R3); }
-    else { LN_DISPATCH(e, GO_128) gemm_form_launched(FORM_BF16_128_R2); }
-#undef GO_128
-#undef GO_128R
-  }
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return gemm_dispatch(GEMM_BF16, A, lda, W, ldw, M, N, K, e, s);
 }
-#undef GO_M16
 
 #ifdef DINODET_TUNING
 extern "C" int dod_debug_gemm_stamps(void* dev_buf) {

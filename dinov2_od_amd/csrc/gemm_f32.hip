@@ -16,7 +16,7 @@
 // workgroups are what overlap it.
 #include "dod_common.h"
 #include "gemm_f32x_epi.h"
-#include <atomic>
+#include "gemm_plan.h"
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -134,7 +134,8 @@ inline bool vec_ok(const void* p, long long ld, long long s1 = 0, long long s2 =
 // B*Q = 400 .. 3 200 rows) put 2-156 such tiles on 256 CUs.  grid.y = S slices of the k-tiles; every slice stores its 64x64 partial
 // ([slice][tile][16 registers][256 threads]: coalesced), the LAST workgroup to arrive at a tile (one atomic counter per tile, reset by that
 // workgroup) sums the S partials IN SLICE ORDER -- so the result does not depend on which one was last -- and runs the epilogue.
-// S is a function of (N, K) alone (launch_gemm_f32): a row's bits do not depend on the batch it is computed in.
+// S is chosen from (N, K) alone, and the split is dropped when tiles x S exceeds the slab (gemm_plan.h): while it runs, a row's bits do not depend on
+// the batch it is computed in.
 template <bool VEC>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__ A, int lda,
                                                        const float* __restrict__ W, int ldw,
@@ -216,9 +217,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 // ---- scratch of the K split: F32K_SLOTS slabs per device, one per launching stream (least recently used first, as gemm_pp.hip's tail scratch:
 // a forward may run as concurrent micro-batches on separate streams); a slab = F32K_TILES counters (zero between launches) + partials of at most
 // F32K_PARTS (tile, slice) pairs.  Allocated by gemm_f32_ksplit_reserve() outside any stream capture, never freed (captured graphs keep the addresses).
-#define F32K_SLOTS 4
-#define F32K_TILES 4096
-#define F32K_PARTS 1536
+#define F32K_SLOTS 4      // (F32K_TILES, F32K_PARTS: gemm_plan.h -- the planner drops the split beyond them)
 static std::mutex g_f32k_mu;
 static char* g_f32k[16] = {};
 static hipStream_t g_f32k_owner[16][F32K_SLOTS] = {};
@@ -251,38 +250,33 @@ static char* f32k_slab(int dev, hipStream_t s) {
   g_f32k_used[dev][pick] = ++g_f32k_clock;
   return g_f32k[dev] + (size_t)pick * F32K_SLAB;
 }
-static std::atomic<long> g_f32k_count{0};
-long gemm_f32_ksplit_count() { return g_f32k_count.load(); }
+bool gemm_f32_ksplit_reserved() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
+  std::lock_guard<std::mutex> lk(g_f32k_mu);
+  return g_f32k[dev] != nullptr;
+}
 
 int launch_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int N, int K,
                     const GemmEpi& e, hipStream_t s, bool allow_ksplit) {
   if (M <= 0 || N <= 0 || K <= 0) return 1;
   if (!e.out_f32 && !e.out_bf16) return 2;
-  const int tiles_n = (N + FBN - 1) / FBN;
-  const int tiles = ((M + FBM - 1) / FBM) * tiles_n;
-  // Slices: from (N, K) alone -- the row count must not change a row's bits (micro-batches, single-image launches).  The callers that allow the
-  // split send at most ~16 m-tiles of N >= 128 here (larger row counts take the bf16 split-3 form, dod_forward.hip qlinear) and any number for the
-  // narrow heads (N < 128): aim at two workgroups per CU for 16 m-tiles, at least 8 k-tiles per slice, at most 8 slices.
-  int S = 1;
+  return gemm_dispatch(GEMM_F32, A, lda, W, ldw, M, N, K, e, s, allow_ksplit);
+}
+
+// FORM_F32; S > 1: the K split across workgroups on this stream's slab
+int run_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int N, int K, const GemmEpi& e, int S, hipStream_t s) {
+  const int tiles = ((M + FBM - 1) / FBM) * ((N + FBN - 1) / FBN);
   float* part = nullptr; unsigned* counters = nullptr;
-  static const int mode = [] { const char* v = DOD_TUNE_ENV("DINODET_F32_KSPLIT"); return v ? atoi(v) : 1; }();      // tuning builds: 0 = off
-  { const int opt = dod_option(DOD_OPT_F32_KSPLIT); if (opt == 0) allow_ksplit = false; else if (opt == 1) allow_ksplit = true; }      // test hook
-  if (allow_ksplit && mode && e.rows_per_img == 0) {
-    const int nk = (K + FBK - 1) / FBK;
-    const int target = mode > 1 ? mode : 512;      // workgroups aimed at for 16 m-tiles (tuning builds: DINODET_F32_KSPLIT = that number)
-    int want = (target + 8 * tiles_n) / (16 * tiles_n);      // rounded: N = 768 (12 n-tiles) -> 3
-    want = want > 8 ? 8 : want;
-    want = want > nk / 8 ? nk / 8 : want;
-    if (want >= 2 && tiles <= F32K_TILES && (long)tiles * want <= F32K_PARTS) {
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      char* slab = f32k_slab(dev, s);
-      if (slab) { S = want; counters = reinterpret_cast<unsigned*>(slab); part = reinterpret_cast<float*>(slab + (size_t)F32K_TILES * 4); ++g_f32k_count; }
-    }
+  if (S > 1) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    char* slab = f32k_slab(dev, s);
+    if (!slab || tiles > F32K_TILES || (long)tiles * S > F32K_PARTS) return 2;
+    counters = reinterpret_cast<unsigned*>(slab); part = reinterpret_cast<float*>(slab + (size_t)F32K_TILES * 4);
   }
   if (vec_ok(A, lda) && vec_ok(W, ldw)) hipLaunchKernelGGL(gemm_f32_kernel<true>, dim3(tiles, S), dim3(256), 0, s, A, lda, W, ldw, M, N, K, e, part, counters);
   else hipLaunchKernelGGL(gemm_f32_kernel<false>, dim3(tiles, S), dim3(256), 0, s, A, lda, W, ldw, M, N, K, e, part, counters);
-  gemm_form_launched(FORM_F32);
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 

@@ -498,19 +498,6 @@ static constexpr int LDS8C = 2 * F8C_STAGE + 4 * F8_SC_BYTES;      // 136 KiB (>
 static constexpr int LDS8MX = F8_SLOTS * F8_STAGE + 2 * F8_SC_BYTES + 2 * F8_SCW_BYTES;
 static constexpr int LDS8 = (128 * (F8N * 4 + 16)) > F8_SLOTS * F8_STAGE ? (128 * (F8N * 4 + 16)) : F8_SLOTS * F8_STAGE;
 
-static void fp8_attr() {      // > 64 KiB of dynamic LDS: once per DEVICE (a process may drive several)
-  static bool attr_set[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fp8_256x128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS8);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fp8mx_256x128_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS8MX);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fp8mx_256x128_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS8MX);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fp8mx_256x256x128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS8C);
-    attr_set[dev] = true;
-  }
-}
-
 int launch_gemm_fp8(const unsigned char* A, int lda, const unsigned char* W, int ldw, int M, int N, int K,
                     const GemmEpi& e, hipStream_t s) {
   if (M <= 0 || N <= 0 || K <= 0) return 1;
@@ -523,27 +510,24 @@ int launch_gemm_fp8(const unsigned char* A, int lda, const unsigned char* W, int
   if (e.a_bs) {          // block-scaled activations
     if (K % 256 != 0) return 2;
     if ((reinterpret_cast<uintptr_t>(e.a_bs) | reinterpret_cast<uintptr_t>(e.w_bs)) & 3) return 2;      // the scale bytes arrive by 4-byte LDS-DMA
-    fp8_attr();
-    const int gm = N >= 3072 ? 8 : (N >= 2048 ? 4 : 2);
-    const int tiles = ((M + F8M - 1) / F8M) * ((N + F8N - 1) / F8N);
-    // both operands block-scaled, a grid of several rounds of 256x256 tiles: the one-workgroup-per-CU tile (fewer staged bytes per MAC)
-    static const int big = [] { const char* v = DOD_TUNE_ENV("DINODET_FP8_TILE"); return v ? atoi(v) : 1; }();      // tuning builds: 0 = 256x128 everywhere
-    if (e.w_bs && big && !(big == 2 && e.out_bs) && M >= 4096 && N >= 512) {      // (tuning value 2: not for the gated weights_in)
-      const int tiles_b = ((M + F8M - 1) / F8M) * ((N + F8BN - 1) / F8BN);
-      hipLaunchKernelGGL(gemm_fp8mx_256x256x128_kernel, dim3(tiles_b), dim3(1024), LDS8C, s, A, lda, W, ldw, M, N, K, e, gm);
-      gemm_form_launched(FORM_FP8MX2_256X256);
-      return hipGetLastError() == hipSuccess ? 0 : 3;
-    }
-    if (e.w_bs) hipLaunchKernelGGL(gemm_fp8mx_256x128_kernel<true>, dim3(tiles), dim3(512), LDS8MX, s, A, lda, W, ldw, M, N, K, e, gm);
-    else hipLaunchKernelGGL(gemm_fp8mx_256x128_kernel<false>, dim3(tiles), dim3(512), LDS8MX, s, A, lda, W, ldw, M, N, K, e, gm);
-    gemm_form_launched(e.w_bs ? FORM_FP8MX2_256X128 : FORM_FP8MX_256X128);
-    return hipGetLastError() == hipSuccess ? 0 : 3;
   }
-  fp8_attr();
-  const int gm = N >= 3072 ? 8 : (N >= 2048 ? 4 : 2);
+  return gemm_dispatch(GEMM_FP8, A, lda, W, ldw, M, N, K, e, s);
+}
+
+// FORM_FP8_ROWS / FORM_FP8MX_256X128 / FORM_FP8MX2_256X128 / FORM_FP8MX2_256X256; gm = grouped-order depth
+int run_gemm_fp8(int form, const unsigned char* A, int lda, const unsigned char* W, int ldw, int M, int N, int K, const GemmEpi& e, int gm, hipStream_t s) {
+  static bool done[16] = {};      // > 64 KiB of dynamic LDS: once per DEVICE (a process may drive several)
+  static const KernelLds k[] = {{reinterpret_cast<const void*>(gemm_fp8_256x128_kernel), LDS8}, {reinterpret_cast<const void*>(gemm_fp8mx_256x128_kernel<false>), LDS8MX},
+                                {reinterpret_cast<const void*>(gemm_fp8mx_256x128_kernel<true>), LDS8MX}, {reinterpret_cast<const void*>(gemm_fp8mx_256x256x128_kernel), LDS8C}};
+  gemm_lds_attr_once(done, k, 4);
   const int tiles = ((M + F8M - 1) / F8M) * ((N + F8N - 1) / F8N);
-  hipLaunchKernelGGL(gemm_fp8_256x128_kernel, dim3(tiles), dim3(512), LDS8, s, A, lda, W, ldw, M, N, K, e, gm);
-  gemm_form_launched(FORM_FP8_ROWS);
+  if (form == FORM_FP8MX2_256X256) {
+    const int tiles_b = ((M + F8M - 1) / F8M) * ((N + F8BN - 1) / F8BN);
+    hipLaunchKernelGGL(gemm_fp8mx_256x256x128_kernel, dim3(tiles_b), dim3(1024), LDS8C, s, A, lda, W, ldw, M, N, K, e, gm);
+  } else if (form == FORM_FP8MX2_256X128) hipLaunchKernelGGL(gemm_fp8mx_256x128_kernel<true>, dim3(tiles), dim3(512), LDS8MX, s, A, lda, W, ldw, M, N, K, e, gm);
+  else if (form == FORM_FP8MX_256X128) hipLaunchKernelGGL(gemm_fp8mx_256x128_kernel<false>, dim3(tiles), dim3(512), LDS8MX, s, A, lda, W, ldw, M, N, K, e, gm);
+  else if (form == FORM_FP8_ROWS) hipLaunchKernelGGL(gemm_fp8_256x128_kernel, dim3(tiles), dim3(512), LDS8, s, A, lda, W, ldw, M, N, K, e, gm);
+  else return 2;
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 

@@ -19,7 +19,6 @@
 //   * WAR: the LDS reads of a phase are retired (lgkmcnt(0)) BEFORE the barrier that ends the LOAD segment; a plane is
 //     re-staged only after the barrier following group 1's last read of it.  RAW: a plane is read one barrier (at least)
 //     after the barrier that follows every wave's vmcnt wait for it.
-#include <atomic>
 #include <mutex>
 #include "dod_common.h"
 #include "gemm_epi.h"
@@ -60,10 +59,7 @@ extern "C" int dod_debug_pp_stamps(void* dev_buf) {
 #define PP_STAMPS_DECL unsigned long long* const stamps = nullptr;      // release build: the stamp code folds away
 #endif
 
-// DC = true: the two LDS-DMA instructions of a phase are issued from inside the COMPUTE segment (between its MFMAs, whose issue slots
-// have slack: an MFMA holds the issue port for half its 16 cycles) instead of the LOAD segment, whose length -- not the MFMAs' --
-// paces the ping-pong once it exceeds the partner's COMPUTE; the counted wait of LOAD 3 then leaves vmcnt(2) (one plane) in flight.
-template <bool X3, bool DC, int LN>
+template <bool X3, int LN>
 __global__ __launch_bounds__(512) void gemm_ppm_256x256_kernel(const bf16_t* __restrict__ A, int lda,
                                                                const bf16_t* __restrict__ W, int ldw, int M, int N,
                                                                int K, GemmEpi e_, int GM) {
@@ -145,8 +141,8 @@ __global__ __launch_bounds__(512) void gemm_ppm_256x256_kernel(const bf16_t* __r
       a0[ii] = *reinterpret_cast<const bf16x8*>((st) + offA[2 * (q) + ii]);                                    \
       a1[ii] = *reinterpret_cast<const bf16x8*>((st) + offA[2 * (q) + ii] + PP_PLANE);                         \
     }                                                                                                          \
-    if (!DC && (PF_ON)) PPM_STAGE(PF_T, PF_PL)                                                                 \
-    if ((VW) == 4) { if (DC) asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); } \
+    if (PF_ON) PPM_STAGE(PF_T, PF_PL)                                                                          \
+    if ((VW) == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                                            \
     else if ((VW) == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                       \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                         \
     __builtin_amdgcn_sched_barrier(0);                                                                         \
@@ -155,11 +151,6 @@ __global__ __launch_bounds__(512) void gemm_ppm_256x256_kernel(const bf16_t* __r
     __builtin_amdgcn_s_setprio(1);                                                                             \
     _Pragma("unroll") for (int ii = 0; ii < 2; ++ii)                                                           \
       _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                          \
-        if (DC && (PF_ON) && j == 1) {                                                                         \
-          __builtin_amdgcn_sched_barrier(0);                                                                   \
-          PPM_STAGE_H(PF_T, PF_PL, ii)                                                                         \
-          __builtin_amdgcn_sched_barrier(0);                                                                   \
-        }                                                                                                      \
         f32x4 c_ = acc[2 * (q) + ii][j];                                                                       \
         if (X3) {                                                                                              \
           c_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[j], a0[ii], c_, 0, 0, 0);   /* Wl Ah: small terms first */ \
@@ -491,46 +482,23 @@ static int wres_grid(int M, int N, int*) { return ((M + PPM - 1) / PPM) * ((N + 
 #endif
 
 static void ppm_attr() {      // > 64 KiB of dynamic LDS: once per device
-  static bool attr_set[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-#define ATTR_(LN_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ppm_256x256_kernel<false, false, LN_>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSPP); \
-                   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ppm_256x256_kernel<true, false, LN_>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSPP);
-    ATTR_(LN_NONE) ATTR_(LN_CONS) ATTR_(LN_PROD)
+  static bool done[16] = {};
+#define ATTR_(LN_) {reinterpret_cast<const void*>(gemm_ppm_256x256_kernel<false, LN_>), LDSPP}, {reinterpret_cast<const void*>(gemm_ppm_256x256_kernel<true, LN_>), LDSPP},
+  static const KernelLds k[] = {ATTR_(LN_NONE) ATTR_(LN_CONS) ATTR_(LN_PROD)};
 #undef ATTR_
-    attr_set[dev] = true;
-  }
+  gemm_lds_attr_once(done, k, sizeof k / sizeof k[0]);
 }
 
-// plain bf16 on the m-phased ping-pong kernel: K % 64 == 0
-int launch_gemm_bf16_ppm(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s) {
-  if (M <= 0 || N <= 0 || K <= 0 || K % PPK != 0) return 2;
-  if (N % 4 != 0 || lda % 8 != 0 || ldw % 8 != 0 || e.ldc % 4 != 0) return 2;
-  if (e.resid && e.ldr % 4 != 0) return 2;
-  if (!e.out_f32 && !e.out_bf16) return 2;
+// FORM_PPM (x3 = false: plain bf16, K % 64 == 0) / FORM_X3_PP (x3 = true: the split product on pair-layout operands, K % 32 == 0) on the m-phased
+// ping-pong kernel.  e.ksplit > 1 (the tail split's K-split launch, gemm_dispatch.hip): grid.y = slice, no start stagger
+int run_gemm_pp(bool x3, const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s) {
+  if (K % (x3 ? 32 : PPK) != 0) return 2;
   ppm_attr();
-  int gm = gemm_tile_mode();
-  const int tiles = wres_grid(M, N, &gm);
-  gemm_form_launched(FORM_PPM);
-#define GO_(LN_) hipLaunchKernelGGL((gemm_ppm_256x256_kernel<false, false, LN_>), dim3(tiles), dim3(512), LDSPP, s, A, lda, W, ldw, M, N, K, e, gm);
-  LN_DISPATCH(e, GO_)
-#undef GO_
-  return hipGetLastError() == hipSuccess ? 0 : 3;
-}
-
-// split product on pair-layout operands (same contract as launch_gemm_x3): K % 32 == 0
-int launch_gemm_x3_pp(const bf16_t* A2, int lda, const bf16_t* W2, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s) {
-  if (M <= 0 || N <= 0 || K <= 0) return 1;
-  if (K % 32 != 0 || N % 4 != 0 || lda % 8 != 0 || ldw % 8 != 0 || lda < 2 * K || ldw < 2 * K) return 2;
-  if (e.out_f32 && e.ldc % 4 != 0) return 2;
-  if (e.resid && e.ldr % 4 != 0) return 2;
-  if (!e.out_f32 && !e.out_bf16) return 2;
-  ppm_attr();
-  int gm = gemm_tile_mode();
-  const int tiles = wres_grid(M, N, &gm);
-  gemm_form_launched(FORM_X3_PP);
-#define GO_(LN_) hipLaunchKernelGGL((gemm_ppm_256x256_kernel<true, false, LN_>), dim3(tiles), dim3(512), LDSPP, s, A2, lda, W2, ldw, M, N, K, e, gm);
+  const int S = e.ksplit > 1 ? e.ksplit : 1;
+  int gm = S > 1 ? gemm_tile_mode() & 0xfff : gemm_tile_mode();
+  const int tiles = S > 1 ? ((M + PPM - 1) / PPM) * ((N + PPN - 1) / PPN) : wres_grid(M, N, &gm);
+#define GO_(LN_) { if (x3) hipLaunchKernelGGL((gemm_ppm_256x256_kernel<true, LN_>), dim3(tiles, S), dim3(512), LDSPP, s, A, lda, W, ldw, M, N, K, e, gm); \
+                   else hipLaunchKernelGGL((gemm_ppm_256x256_kernel<false, LN_>), dim3(tiles, S), dim3(512), LDSPP, s, A, lda, W, ldw, M, N, K, e, gm); }
   LN_DISPATCH(e, GO_)
 #undef GO_
   return hipGetLastError() == hipSuccess ? 0 : 3;
@@ -538,17 +506,6 @@ int launch_gemm_x3_pp(const bf16_t* A2, int lda, const bf16_t* W2, int ldw, int 
 
 // H2 operands (dod_common.h): A [M, K] activation rows at pitch lda bytes (>= 4K), W [N, K] weight rows at pitch ldw bytes (>= 3K)
 static constexpr int LDSH2 = (128 * (PPN * 4 + 16)) > H2_LDS ? (128 * (PPN * 4 + 16)) : H2_LDS;
-static void h2_attr() {
-  static bool attr_set[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2_256x256_kernel<LN_NONE>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSH2);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2_256x256_kernel<LN_CONS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSH2);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2_256x256_kernel<LN_PROD>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSH2);
-    attr_set[dev] = true;
-  }
-}
 int launch_gemm_h2(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s) {
   if (M <= 0 || N <= 0 || K <= 0) return 1;
   if (K % 32 != 0 || N % 4 != 0 || lda % 16 != 0 || ldw % 16 != 0 || lda < 4 * K || ldw < 3 * K || !e.h2_wexp) return 2;
@@ -558,19 +515,25 @@ int launch_gemm_h2(const void* A, int lda, const void* W, int ldw, int M, int N,
   { const int No = e.glu ? N / 2 : N;     // columns of the output row (GemmEpi::glu: the gate halves them)
     if (e.out_h2 && (No % 32 != 0 || e.ldc < 2 * No || e.ldc % 8 != 0 || e.out_split != 0)) return 2;
     if (e.glu && e.out_h2 && (N % 8 != 0)) return 2; }
-  { const int t = gemm_tail_split(2, A, lda, W, ldw, M, N, K, e, s); if (t >= 0) return t; }
-  h2_attr();
-  const int gm = gemm_tile_mode();
+  return gemm_dispatch(GEMM_H2, A, lda, W, ldw, M, N, K, e, s);
+}
+// FORM_H2; e.ksplit > 1 as in run_gemm_pp
+int run_gemm_h2(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s) {
+  static bool done[16] = {};
+  static const KernelLds k[] = {{reinterpret_cast<const void*>(gemm_h2_256x256_kernel<LN_NONE>), LDSH2}, {reinterpret_cast<const void*>(gemm_h2_256x256_kernel<LN_CONS>), LDSH2},
+                                {reinterpret_cast<const void*>(gemm_h2_256x256_kernel<LN_PROD>), LDSH2}};
+  gemm_lds_attr_once(done, k, 3);
+  const int S = e.ksplit > 1 ? e.ksplit : 1;
+  const int gm = S > 1 ? gemm_tile_mode() & 0xfff : gemm_tile_mode();
   const int tiles = ((M + PPM - 1) / PPM) * ((N + PPN - 1) / PPN);
-  gemm_form_launched(FORM_H2);
-#define GO_(LN_) hipLaunchKernelGGL(gemm_h2_256x256_kernel<LN_>, dim3(tiles), dim3(512), LDSH2, s, (const char*)A, lda, (const char*)W, ldw, M, N, K, e, gm);
+#define GO_(LN_) hipLaunchKernelGGL(gemm_h2_256x256_kernel<LN_>, dim3(tiles, S), dim3(512), LDSH2, s, (const char*)A, lda, (const char*)W, ldw, M, N, K, e, gm);
   LN_DISPATCH(e, GO_)
 #undef GO_
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Wave-quantisation tail (dod_common.h gemm_tail_split).  One 256x256 tile per CU and round: 343 x 3 = 1029 tiles of an N = 768 GEMM at
+// Wave-quantisation tail (the rule: gemm_plan.h tail_split; the launches: gemm_dispatch.hip).  One 256x256 tile per CU and round: 343 x 3 = 1029 tiles of an N = 768 GEMM at
 // M = 87680 take FIVE rounds on 256 CUs for 4.02 rounds of work (tools/pp_timeline.py: kernel span = 5 tile times).  The rows of the
 // short last round are cut off, their tiles K-split S ways in ONE launch (grid.y = slice: S CUs per tile, fp32 partial slabs), and
 // a reduce + epilogue launch sums the slabs into an LDS tile and drains it with the GEMMs' own epilogue code.
@@ -645,106 +608,22 @@ static float* tail_slab(int dev, hipStream_t s) {
   return (float*)((char*)g_tail_scratch[dev][g_tail_gen[dev] - 1] + (size_t)pick * g_tail_bytes[dev]);
 }
 
-// mode of the split (test option DOD_OPT_TAILSPLIT): -1 / 1 = the shipped heuristic, 0 = off, 2 = every qualifying shape
-static int tail_mode() {
-  const int m = dod_option(DOD_OPT_TAILSPLIT);
-  if (m >= 0) return m;
-  static const char* env = DOD_TUNE_ENV("DINODET_GEMM_TAILSPLIT");
-  return env ? (env[0] == '0' ? 0 : (env[0] == '2' ? 2 : 1)) : 1;
+size_t gemm_tail_reserved() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
+  std::lock_guard<std::mutex> lk(g_tail_mu);
+  return g_tail_bytes[dev];
+}
+float* gemm_tail_slab(hipStream_t s) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+  return tail_slab(dev, s);
 }
 
-static thread_local bool t_in_tail_split = false;
-static std::atomic<long> g_tail_splits{0};
-long gemm_tail_split_count() { return g_tail_splits.load(); }
-int gemm_tail_split(int kind, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s) {
-  if (t_in_tail_split || e.ksplit > 1 || e.rows_per_img != 0 || e.a_scale || e.out_split > 0) return -1;
-  const int mode = tail_mode();
-  if (mode == 0) return -1;
-  const int ktile = kind == 0 ? 64 : 32;
-  if (N % 4 != 0 || K % ktile != 0) return -1;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -1;
-  static int cus[16] = {};
-  if (!cus[dev]) { int c = 0; (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev); cus[dev] = c > 0 ? c : 256; }
-  const int CU = cus[dev];
-  const int tiles_n = (N + PPN - 1) / PPN, tiles_m = (M + PPM - 1) / PPM, tiles = tiles_m * tiles_n;
-  const int nk = K / ktile;
-  const bool force = mode == 2;
-  int Mmain, R, tiles_r, S = 0;
-  // plain bf16 (kind 0) has a 256x128 tile for underfilled grids and does NOT take this K-split by default.  Round 3 tried it on the
-  // decoder's query-side linears (M = B*Q = 3 200 rows at batch 32: 39 tiles of 256x256 walking K' = 3K = 2 304, 48.5 us on 78 CUs as
-  // 256x128 tiles): six slices per tile (234 workgroups) + the reduce launch write and re-read 59 MB of fp32 partials, and the forward
-  // gains nothing (`bench.py --workload vitb224`: 7 539 vs 7 571 images/s, vitb518 2 241.7 both ways).  Tuning builds: DINODET_GEMM_KSPLIT0 = n
-  // enables it for grids of at most CUs * n / 12 tiles.
-  static const int k0frac = [] { const char* v = DOD_TUNE_ENV("DINODET_GEMM_KSPLIT0"); return v ? atoi(v) : 0; }();
-  if (M >= 2048 && (kind >= 1 ? tiles * 2 <= CU + CU / 8 : tiles * 12 <= CU * k0frac)) {
-    // (a) an UNDERFILLED single round (the compensated kernels have no smaller tile): 99 tiles of an N = 768 GEMM at M = 8224 leave 157
-    // CUs idle -- every tile is K-split so that tiles x S fills the chip (no main launch)
-    Mmain = 0; R = M; tiles_r = tiles;
-    for (int c : {8, 6, 4, 3, 2})
-      if (nk % c == 0 && nk / c >= 3 && tiles_r * c <= CU) { S = c; break; }
-  } else {
-    // (b) a short LAST round.  Measured at M = 87680 (343 x 3 tiles, 4.02 rounds; tools/bench_h2.py, tools/bench_pp.py with
-    // DINODET_GEMM_TAILSPLIT=0 / 2): the unsplit kernels last ~4.3 tile times, not 5 -- the five tiles of the last round run alone on
-    // the chip -- so the split pays where a tile is long: fc2 (K = 3072) 976 vs 1047 us (split product), 866 vs 944 (H2), 474 vs 491
-    // (plain bf16); out-proj (K = 768) 367 vs 373, 346 vs 350, 218 vs 217: not worth a second and third launch.  Enabled at K >= 2048
-    // (DINODET_GEMM_TAILSPLIT=2 forces every qualifying shape).
-    // (with the engine's two concurrent micro-batches the other stream's kernels fill the last-round bubble anyway: fp16x2 at 2 x 32
-    // images 1 198 images/s with the split, 1 208 without; so case (b) is kept for the launches that only a single-stream forward of a
-    // large batch makes, M >= 65536 rows)
-    const int rounds = tiles / CU, rem = tiles % CU;
-    // (round 4) a grid one or two rounds deep whose last round is 6-16 % full -- the compensated QKV at 32 images of 224^2: 33 x 9 = 297 tiles --
-    // loses most of a tile time to it at any K (bench.py --workload vitb224: bf16x3 4 953 -> 5 015 images/s, fp16x2 5 258 -> 5 318; a fuller or
-    // emptier last round, e.g. 2 x 4 images of 518^2, gains nothing).  The plain bf16 kernels cut those rows off instead (gemm_bf16.hip).
-    const bool shallow = kind >= 1 && M >= 4096 && rounds >= 1 && rounds <= 2 && rem * 16 >= CU && rem * 6 <= CU;
-    if (M < 8192 && !shallow) return -1;
-    if (!force && !shallow && (K < 2048 || M < 65536)) return -1;
-    if (rounds < 1 || rounds > 6 || rem == 0) return -1;
-    const int m_main = (rounds * CU) / tiles_n;
-    Mmain = m_main * PPM; R = M - Mmain;
-    if (R <= 0) return -1;
-    tiles_r = ((R + PPM - 1) / PPM) * tiles_n;
-    for (int c : {8, 6, 4, 3, 2})
-      if (nk % c == 0 && nk / c >= 3 && tiles_r * c <= CU) { S = c; break; }
-    // worth it when the last round shrinks from one tile time to 1/S of one (+ ~1/4 for the slab round trip and the two extra
-    // launches) and that is >= 4 % of the kernel: 1029 tiles (4 rounds + 5: S = 8) and 344 tiles (1 round + 88: S = 2) both qualify
-    if (S >= 2 && (1.0 - 1.0 / S - 0.25) < 0.04 * (rounds + 1)) S = 0;
-  }
-  if (S < 2) return -1;
-  const size_t slab = (size_t)R * N;
-  if (g_tail_bytes[dev] < slab * S * 4) return -1;           // reserved outside stream capture (gemm_tail_reserve)
-  float* scratch = tail_slab(dev, s);
-  if (!scratch) return -1;
-  // ---- main rows: the caller's own dispatch
-  if (Mmain > 0) {
-    t_in_tail_split = true;
-    int rc;
-    if (kind == 0) rc = launch_gemm_bf16((const bf16_t*)A, lda, (const bf16_t*)W, ldw, Mmain, N, K, e, s);
-    else if (kind == 1) rc = launch_gemm_x3((const bf16_t*)A, lda, (const bf16_t*)W, ldw, Mmain, N, K, e, s);
-    else rc = launch_gemm_h2(A, lda, W, ldw, Mmain, N, K, e, s);
-    t_in_tail_split = false;
-    if (rc) return rc;
-  }
-  // ---- remainder rows, K-split: fp32 partial slabs
-  GemmEpi es; memset(&es, 0, sizeof es);
-  es.out_f32 = scratch; es.ldc = N; es.h2_wexp = e.h2_wexp;
-  es.ksplit = S; es.kslice_len = K / S; es.kslice_stride = (long long)slab;
-  const int gm = gemm_tile_mode() & 0xfff;          // no start stagger
-  gemm_form_launched(kind == 2 ? FORM_H2 : (kind == 1 ? FORM_X3_PP : FORM_PPM));      // the K-split launch runs the family's ping-pong kernel
-  if (kind == 2) {
-    h2_attr();
-    const char* Ar = (const char*)A + (size_t)Mmain * lda;
-    hipLaunchKernelGGL(gemm_h2_256x256_kernel<LN_NONE>, dim3(tiles_r, S), dim3(512), LDSH2, s, Ar, lda, (const char*)W, ldw, R, N, K, es, gm);
-  } else {
-    ppm_attr();
-    const bf16_t* Ar = (const bf16_t*)A + (size_t)Mmain * lda;
-    if (kind == 1) hipLaunchKernelGGL((gemm_ppm_256x256_kernel<true, false, LN_NONE>), dim3(tiles_r, S), dim3(512), LDSPP, s, Ar, lda, (const bf16_t*)W, ldw, R, N, K, es, gm);
-    else hipLaunchKernelGGL((gemm_ppm_256x256_kernel<false, false, LN_NONE>), dim3(tiles_r, S), dim3(512), LDSPP, s, Ar, lda, (const bf16_t*)W, ldw, R, N, K, es, gm);
-  }
-  if (hipGetLastError() != hipSuccess) return 3;
-  // ---- reduce + the caller's epilogue on global rows Mmain..M-1
-  ++g_tail_splits;
-#define GO_(LN_) hipLaunchKernelGGL(gemm_ksplit_reduce_kernel<LN_>, dim3((R + KSR_ROWS - 1) / KSR_ROWS, tiles_n), dim3(512), 0, s, scratch, (long long)slab, S, R, N, e, Mmain, M, K);
+// FORM_KSPLIT_REDUCE: sums the S partial slabs of rows m_base .. m_base + R - 1 in slice order and runs the call's epilogue `e` on them
+int run_gemm_ksplit_reduce(const float* part, int S, int R, int N, const GemmEpi& e, int m_base, int M, int K, hipStream_t s) {
+  const int tiles_n = (N + PPN - 1) / PPN;
+#define GO_(LN_) hipLaunchKernelGGL(gemm_ksplit_reduce_kernel<LN_>, dim3((R + KSR_ROWS - 1) / KSR_ROWS, tiles_n), dim3(512), 0, s, part, (long long)R * N, S, R, N, e, m_base, M, K);
   LN_DISPATCH(e, GO_)
 #undef GO_
   return hipGetLastError() == hipSuccess ? 0 : 3;

@@ -283,19 +283,13 @@ static constexpr int LDSX3 = (128 * (X3N * 4 + 16)) > X3_SLOTS * X3_STAGE ? (128
 static constexpr int LDSX3E = X3_PAR + 4096;      // REGM: the ring (then the bf16 tile) + the tile's parameters
 
 static void x3_attr() {      // > 64 KiB of dynamic LDS: once per device
-  static bool attr_set[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-#define ATTR_(LN_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3_256x256_kernel<false, LN_>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSX3); \
-                   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3_256x256_kernel<true, LN_>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSX3);
-    ATTR_(LN_NONE) ATTR_(LN_CONS) ATTR_(LN_PROD)
+  static bool done[16] = {};
+#define ATTR_(LN_) {reinterpret_cast<const void*>(gemm_x3_256x256_kernel<false, LN_>), LDSX3}, {reinterpret_cast<const void*>(gemm_x3_256x256_kernel<true, LN_>), LDSX3},
+#define ATTRE_(LN_) {reinterpret_cast<const void*>(gemm_x3_256x256_kernel<true, LN_, true>), LDSX3E},
+  static const KernelLds k[] = {ATTR_(LN_NONE) ATTR_(LN_CONS) ATTR_(LN_PROD) ATTRE_(LN_NONE) ATTRE_(LN_CONS)};
 #undef ATTR_
-#define ATTR_(LN_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3_256x256_kernel<true, LN_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSX3E);
-    ATTR_(LN_NONE) ATTR_(LN_CONS)
-#undef ATTR_
-    attr_set[dev] = true;
-  }
+#undef ATTRE_
+  gemm_lds_attr_once(done, k, sizeof k / sizeof k[0]);
 }
 
 // A2 [M, lda >= 2K], W2 [N, ldw >= 2K]: pair layout; K % 32 == 0
@@ -306,44 +300,31 @@ int launch_gemm_x3(const bf16_t* A2, int lda, const bf16_t* W2, int ldw, int M, 
   if (e.out_f32 && e.ldc % 4 != 0) return 2;
   if (e.resid && e.ldr % 4 != 0) return 2;
   if (!e.out_f32 && !e.out_bf16) return 2;
-  { const int t = gemm_tail_split(1, A2, lda, W2, ldw, M, N, K, e, s); if (t >= 0) return t; }
-  {
-    // the 8-wave ping-pong kernel (gemm_pp.hip) wherever a workgroup's K loop or column count is long enough to pay for its
-    // 512-thread epilogue: measured at M = 87680 against the 16-wave kernel below -- QKV 400 vs 378, fc1 376 vs 363, fc2 406 vs 371
-    // TFLOP/s algorithmic; out-proj (N = K = 768) 276 vs 293, so that one stays.  (tuning builds: DINODET_X3_TILE = p / w forces either)
-    const char* v = DOD_TUNE_ENV("DINODET_X3_TILE");
-    // (round 4, after both kernels' epilogues were rewritten: the ping-pong kernel wins out-proj too -- 337.6 vs 345.1 us at M = 87 680,
-    // 183.0 vs 185.8 at 43 840, 58.0 vs 59.6 at 10 960 -- so every large-M split product takes it)
-    const bool pp = v ? v[0] == 'p' : (M >= 4096);
-    if (pp) return launch_gemm_x3_pp(A2, lda, W2, ldw, M, N, K, e, s);
-  }
+  return gemm_dispatch(GEMM_X3, A2, lda, W2, ldw, M, N, K, e, s);
+}
+
+// FORM_X3_16W: the split product on the 16-wave kernel
+int run_gemm_x3_16w(const bf16_t* A2, int lda, const bf16_t* W2, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s) {
   x3_attr();
   const int gm = gemm_tile_mode();
   const int tiles = ((M + X3M - 1) / X3M) * ((N + X3N - 1) / X3N);
 #define GO_(LN_) hipLaunchKernelGGL((gemm_x3_256x256_kernel<false, LN_>), dim3(tiles), dim3(1024), LDSX3, s, A2, lda, W2, ldw, M, N, K, e, gm);
   LN_DISPATCH(e, GO_)
 #undef GO_
-  gemm_form_launched(FORM_X3_16W);
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
-static std::atomic<long> g_epi_regmath{0};
-long gemm_epi_regmath_count() { return g_epi_regmath.load(); }
-
-// plain bf16 GEMM on the same structure (256x256x64, 16 waves, two 64-KiB slots): K % 64 == 0
-int launch_gemm_bf16_k64(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, hipStream_t s) {
-  if (M <= 0 || N <= 0 || K <= 0 || K % 64 != 0) return 2;
+// FORM_K64: plain bf16 GEMM on the same structure (256x256x64, 16 waves, two 64-KiB slots): K % 64 == 0.  regmath (plain bf16 rows: QKV, fc1 of
+// the bf16 mode; epi_regmath_ok): the register epilogue -- a template parameter, so that neither form carries the other's registers
+int run_gemm_k64(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, int N, int K, const GemmEpi& e, bool regmath, hipStream_t s) {
+  if (K % 64 != 0 || (regmath && !epi_regmath_ok(e, N))) return 2;
   x3_attr();
   const int gm = gemm_tile_mode();
   const int tiles = ((M + X3M - 1) / X3M) * ((N + X3N - 1) / X3N);
-  gemm_form_launched(FORM_K64);
-  // plain bf16 rows (QKV, fc1 of the bf16 mode): the register epilogue.  Test option DOD_OPT_EPI_REGMATH, read once per launch: 0 = the
-  // LDS-staged epilogue.  A template parameter, so that neither form carries the other's registers
-  if (dod_option(DOD_OPT_EPI_REGMATH) != 0 && epi_regmath_ok(e, N)) {
+  if (regmath) {
 #define GO_(LN_) hipLaunchKernelGGL((gemm_x3_256x256_kernel<true, LN_, true>), dim3(tiles), dim3(1024), LDSX3E, s, A, lda, W, ldw, M, N, K, e, gm);
     if (ln_mode_of(e) == LN_CONS) { GO_(LN_CONS) } else { GO_(LN_NONE) }
 #undef GO_
-    ++g_epi_regmath;
     return hipGetLastError() == hipSuccess ? 0 : 3;
   }
 #define GO_(LN_) hipLaunchKernelGGL((gemm_x3_256x256_kernel<true, LN_>), dim3(tiles), dim3(1024), LDSX3, s, A, lda, W, ldw, M, N, K, e, gm);

@@ -706,6 +706,23 @@ int dod_reserve_gemm_scratch(size_t bytes);
  * -DDINODET_TUNING builds (include/dinodet_tuning.h); the release library exports none of them. */
 int dod_test_set_option(const char* name, int value);
 long dod_test_counter(const char* name);
+/* What the inference GEMM launchers WOULD do, without a device (the planner of csrc/gemm_plan.h, which the launchers execute): the launches of one
+ * linear in order -- at most main rows cut in two by the remainder cut, then a tail split's K-split launch and its reduce launch.  Returns the number
+ * of steps written (1..4), -1 for a bad argument or max_steps too small.  The caller chooses the CU count and the scratch bytes reserved
+ * (dod_reserve_gemm_scratch; > 0 also means the fp32 K split's slab exists); the "tailsplit" / "f32_ksplit" / "epi_regmath" test options are read
+ * as the launchers read them.
+ *   family     0 plain bf16 operands (dod_op_linear), 1 split product (dod_op_linear_x3), 2 H2 (dod_op_linear_h2), 3 fp8, 4 fp32
+ *   epi_flags  what the policy reads of the epilogue, nothing else of it matters:  1 GELU, 2 sigmoid, 4 patch-embed row map, 8 fp8 per-row A scales,
+ *              16 [hi | hi | lo] output, 32 K-sliced epilogue, 64 the epilogue of a row range can run as a launch of its own (no row map, K slices or fp8
+ *              scales), 128 plain bf16 rows the register epilogue can write (bf16 out, N and pitch multiples of 8, no residual / pair / H2 / gated form, act
+ *              none / relu / gelu), 256 / 512 / 1024 fp8 block scales of A / W / the gated output, 2048 the fp32 caller allows the K split
+ *   step.form  index of the form in the dod_test_counter("form_*") list below, in that order (0 = bf16_128_r2 ... 12 = f32), or 14 = the tail
+ *              split's reduce launch;  row0, rows: the rows it computes;  kslices: K slices of a K-split launch and its reduce (1 otherwise);
+ *              regmath: the k64 form takes the register epilogue;  gm: grouped-order depth of the bf16_m16 and fp8 forms (0 otherwise)
+ * Executing the steps moves the counters so: one per form; "tail_splits" per reduce step; "rem_cuts" per step with row0 > 0 and kslices == 1;
+ * "f32_ksplits" per f32 step with kslices > 1; "epi_regmath" per step with regmath. */
+typedef struct dod_gemm_step { int form, row0, rows, kslices, regmath, gm; } dod_gemm_step;
+int dod_test_gemm_plan(int family, int M, int N, int K, unsigned epi_flags, int cus, size_t scratch_bytes, dod_gemm_step* steps, int max_steps);
 
 const char* dod_version(void);
 /* ABI revision of this header: bumped whenever an exported signature or struct layout changes (round 2's dod_set_weight gained its
@@ -716,7 +733,7 @@ const char* dod_version(void);
  * (dod_op_layernorm_bwd ... dod_op_colsum_add) joined revision 6 the same way.  So did the optimizer step (dod_optim_*), the deep-supervision
  * step (dod_decoder_train_aux_*), the layered criterion (dod_set_criterion_layers_*) and the split-product operators (dod_op_gemm_f32x3,
  * dod_op_linear_f32x3; the training entry points reading cfg->precision changes no signature either) and the train-time augmentation
- * (dod_preprocess_aug, dod_preprocess_aug_u8).
+ * (dod_preprocess_aug, dod_preprocess_aug_u8) and the host-side dispatch query (dod_test_gemm_plan).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);
