@@ -73,6 +73,23 @@ class DINOv2ObjectDetector(_EngineMixin, nn.Module):   # state-dict keys already
             raise RuntimeError("forward_packed_u8 is an eval-mode entry (train() takes the fp32 batch)")
         return self._get_engine().forward_u8(pixels_hwc, self._engine_named())
 
+    def detect(self, pixel_values, sizes=None, **kw):
+        """[B,3,H,W] -> postprocess.Detections: the top_k detections of every image as pixel xyxy boxes with score and label
+        (postprocess.detect_packed takes **kw: top_k, threshold, nms_iou, class_agnostic, clamp, skip_background).  sizes: the
+        (height, width) the boxes are scaled to -- None = the input's own (H, W).  Runs the eval-mode forward under no_grad and
+        puts the model back into the mode it was in; no host sync."""
+        from ..postprocess import detect_packed
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                det = self.forward_packed(pixel_values)
+                if sizes is None:
+                    sizes = (pixel_values.shape[-2], pixel_values.shape[-1])
+                return detect_packed(det, self._dc_cfg.num_classes, sizes, **kw)
+        finally:
+            self.train(was_training)
+
     def forward(self, pixel_values):
         """pixel_values [batch, 3, H, W] -> {"pred_logits", "pred_boxes"} (detector.py:58-69)."""
         if self._use_autograd(pixel_values):            # train(): autograd composite of the same math (detector.py:58-69)

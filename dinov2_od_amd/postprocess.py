@@ -4,8 +4,11 @@ Mirrors the reference's `evaluate_coco(model, dataloader, device, output_file=No
 signature, same list of `{'image_id', 'category_id', 'bbox', 'score'}` dicts in the same order, same JSON dump -- but the
 sigmoid / threshold / box conversion / compaction of utils.py:195-233 (a triple Python loop with a `.cpu().numpy()` per
 class) runs as three small HIP kernels over the packed detections, and only the kept records cross PCIe.
+`detect_packed` is the other consumer of the packed buffer (`dod_detect`): per image the `top_k` best (query, class) pairs as
+pixel xyxy boxes with score and label, optionally after greedy NMS, in fixed-shape tensors and without a host sync.
 No CPU fallback: without the HIP library this module raises.
 """
+import collections
 import ctypes as C
 import json
 
@@ -48,6 +51,71 @@ def postprocess_packed(det, num_classes, image_ids=None, threshold=0.05, max_out
                                 nat.ptr(ws), ws.numel(), nat.stream_ptr()))
     n = min(int(count.item()), cap)                       # the one host sync: how many records to fetch
     return out[: n * RECORD_DTYPE.itemsize].cpu().numpy().view(RECORD_DTYPE).copy()
+
+
+Detections = collections.namedtuple("Detections", ["scores", "labels", "boxes", "queries", "counts"])
+MAX_TOP_K, MAX_TOP_K_NMS = 1024, 512      # include/dinodet.h dod_detect
+
+
+def _sizes_rows(sizes, B):
+    """None / one (h, w) / a sequence of B pairs / a [B, 2] tensor -> a [B, 2] tensor of (height, width) on its own device, or None"""
+    if sizes is None:
+        return None
+    t = sizes if isinstance(sizes, torch.Tensor) else torch.from_numpy(np.asarray(sizes, dtype=np.float32))
+    if t.dim() == 1 and t.numel() == 2:
+        t = t.reshape(1, 2).expand(B, 2)
+    if t.dim() != 2 or tuple(t.shape) != (B, 2):
+        raise ValueError(f"sizes must be None, one (height, width) or one pair per image ({B}), got shape {tuple(t.shape)}")
+    return t
+
+
+def detect_packed(det, num_classes, sizes=None, top_k=100, threshold=-1.0, nms_iou=None, class_agnostic=False, clamp=True,
+                  skip_background=True):
+    """det: packed detections [B, Q, C+4] fp32 on the GPU.  Per image the `top_k` highest-logit (query, class) pairs -- of those with
+    sigmoid(logit) > threshold when threshold >= 0, class 0 left out when skip_background -- in (logit descending, q*C + c ascending)
+    order, as xyxy boxes scaled by sizes (height, width; None keeps them normalised) and clamped to the image when clamp; with
+    nms_iou (>= 0) greedy NMS, per class unless class_agnostic, removes later boxes whose IoU with a survivor exceeds it.
+    Returns Detections(scores [B,K] f32, labels [B,K] i32, boxes [B,K,4] f32, queries [B,K] i32, counts [B] i32) of CUDA tensors; rows
+    at and beyond counts[b] are padding (score 0, label -1, query -1, box 0).  One launch on the current stream, no host sync."""
+    if not (isinstance(det, torch.Tensor) and det.dtype == torch.float32 and det.dim() == 3):
+        raise ValueError("det must be a CUDA fp32 tensor [B, Q, C+4]")
+    B, Q, W = det.shape
+    Cn, K = int(num_classes), int(top_k)
+    if W != Cn + 4 or Cn < 1:
+        raise ValueError(f"det has {W} columns, expected num_classes + 4 = {Cn + 4}")
+    if B < 1 or Q < 1 or Q * Cn > (1 << 20):
+        raise ValueError(f"need at least one image and one query and at most 2^20 (query, class) pairs per image, got B={B} Q={Q} C={Cn}")
+    first = 1 if skip_background else 0
+    if first >= Cn:
+        raise ValueError("skip_background leaves no class (num_classes == 1)")
+    nms = nms_iou is not None
+    if nms and not float(nms_iou) >= 0.0:
+        raise ValueError(f"nms_iou must be None or >= 0, got {nms_iou}")
+    kmax = MAX_TOP_K_NMS if nms else MAX_TOP_K
+    if not 1 <= K <= kmax:
+        raise ValueError(f"top_k must be in 1..{kmax}{' with NMS' if nms else ''}, got {K}")
+    st = _sizes_rows(sizes, B)
+    if not det.is_cuda:                                       # last: every argument is checked whether or not a GPU is present
+        raise ValueError("det must be a CUDA fp32 tensor [B, Q, C+4] (there is no CPU fallback)")
+    det = det.contiguous()
+    L = nat.lib()
+    dev = det.device
+    if st is not None:
+        st = st.to(device=dev, dtype=torch.float32).contiguous()
+    ws = torch.empty(L.dod_detect_workspace_bytes(B, Q, Cn, K), dtype=torch.uint8, device=dev)
+    out = Detections(torch.empty(B, K, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
+                     torch.empty(B, K, 4, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
+                     torch.empty(B, dtype=torch.int32, device=dev))
+    nat.check(L.dod_detect(nat.ptr(det), B, Q, Cn, first, nat.ptr(st), float(threshold), K, float(nms_iou) if nms else -1.0,
+                           int(bool(class_agnostic)), int(bool(clamp)), nat.ptr(out.scores), nat.ptr(out.labels), nat.ptr(out.queries),
+                           nat.ptr(out.boxes), nat.ptr(out.counts), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+    return out
+
+
+def detections_to_list(result):
+    """Detections -> per image {"boxes" [n,4], "scores" [n], "labels" [n]} trimmed to counts (the one host sync: it reads counts)"""
+    counts = result.counts.tolist()
+    return [{"boxes": result.boxes[b, :n], "scores": result.scores[b, :n], "labels": result.labels[b, :n]} for b, n in enumerate(counts)]
 
 
 def records_to_coco(rec):

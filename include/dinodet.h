@@ -295,6 +295,36 @@ int dod_postprocess(const float* det, int B, int Q, int C, const int64_t* image_
                     dod_detection* out, int64_t max_out, int64_t* count, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* ---- detection output on device: top-k, pixel boxes, optional NMS -----------------------------------
+ * What a caller that is not running COCO eval wants from the packed detections: per image the K best (query, class) pairs as xyxy
+ * boxes in pixels with score and label, duplicates optionally removed.  Fixed-shape outputs, one launch on `stream`, no host
+ * synchronisation, no atomics on global memory: the results are a function of the input bits and bit-identical from run to run.
+ *   candidates of image b   all (q, c) with c >= first_class (1 skips the background class as dod_postprocess does; 0 keeps it) whose
+ *                           logit is not NaN and for which threshold < 0 or sigmoid(logit) > threshold, sigmoid = 1 / (1 + expf(-x)).
+ *   order                   logit descending, ties by flat index q*C + c ascending.  Ranking is on the logit's bits (sign-flipped
+ *                           to an order-preserving integer: +0.0 ranks before -0.0, +inf first, -inf last), never on the fp32 score, so
+ *                           it is a total order where the sigmoid saturates.  The first K candidates in that order are selected.
+ *   box                     x1 = cx - 0.5 w, y1 = cy - 0.5 h, x2 = cx + 0.5 w, y2 = cy + 0.5 h (as dod_postprocess), then x *= width_b,
+ *                           y *= height_b with sizes[b] = (height, width) fp32 (device [B, 2]; NULL = 1 x 1: boxes stay normalised),
+ *                           then with clamp != 0 every coordinate v becomes v < 0 ? 0 : (v > limit ? limit : v), limit = width_b or
+ *                           height_b.  One fp32 rounding per operation.
+ *   NMS (iou_threshold >= 0)  greedy over the selected candidates in their order, on the output boxes: j is suppressed by an earlier
+ *                           survivor i when (class_agnostic or label_i == label_j) and inter > iou_threshold * union, in fp32 and in
+ *                           this order: iw = max(0, min(x2i, x2j) - max(x1i, x1j)), ih likewise, inter = iw * ih,
+ *                           area = max(0, x2 - x1) * max(0, y2 - y1), union = (area_i + area_j) - inter; min(a, b) = a < b ? a : b,
+ *                           max(a, b) = a > b ? a : b.  No division: the decision can be reproduced bit for bit on the host.
+ *                           Survivors are compacted to the front in order.  NMS needs K <= 512 (its K x K bit matrix lives in LDS).
+ *   outputs                 scores [B, K] f32 (the sigmoid), labels [B, K] i32 (c), queries [B, K] i32 (q), boxes [B, K, 4] f32 xyxy
+ *                           (16-byte aligned), counts [B] i32.  Rows at and beyond counts[b] are padding: score 0, label -1, query -1,
+ *                           box 0.
+ * Limits: 1 <= K <= 1024, Q*C <= 2^20, C >= 1, 0 <= first_class < C, B, Q >= 1; outside them, for a NULL det / output pointer or a
+ * workspace below dod_detect_workspace_bytes(B, Q, C, K) (which is 0 outside the limits) the call returns DOD_ERR_INVALID before
+ * any launch.  All pointers are device pointers. */
+size_t dod_detect_workspace_bytes(int B, int Q, int C, int K);
+int dod_detect(const float* det, int B, int Q, int C, int first_class, const float* sizes, float threshold, int K,
+               float iou_threshold, int class_agnostic, int clamp, float* scores, int32_t* labels, int32_t* queries, float* boxes,
+               int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- input pipeline on device -------------------------------------------------------
  * Replaces the per-image host transform of dino_detector/train.py:584-587 -- torchvision Resize((R,R)) + ToTensor() on a
  * PIL image, i.e. Pillow's Image.resize(BILINEAR) (two-pass 8-bit fixed-point resample, antialiased when downscaling)
@@ -733,7 +763,7 @@ const char* dod_version(void);
  * (dod_op_layernorm_bwd ... dod_op_colsum_add) joined revision 6 the same way.  So did the optimizer step (dod_optim_*), the deep-supervision
  * step (dod_decoder_train_aux_*), the layered criterion (dod_set_criterion_layers_*) and the split-product operators (dod_op_gemm_f32x3,
  * dod_op_linear_f32x3; the training entry points reading cfg->precision changes no signature either) and the train-time augmentation
- * (dod_preprocess_aug, dod_preprocess_aug_u8) and the host-side dispatch query (dod_test_gemm_plan).
+ * (dod_preprocess_aug, dod_preprocess_aug_u8), the host-side dispatch query (dod_test_gemm_plan) and the detection output (dod_detect*).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);
