@@ -14,4 +14,7 @@ def __getattr__(name):
     if name == "optim":      # dinov2_od_amd.optim.Adam / clip_grad_norm_: the optimizer step on the HIP kernels
         import importlib
         return importlib.import_module(".optim", __name__)
+    if name in ("draw_detections", "log_images", "save_images"):      # dinov2_od_amd.visualize: boxes drawn into the batch on the GPU
+        import importlib
+        return getattr(importlib.import_module(".visualize", __name__), name)
     raise AttributeError(name)

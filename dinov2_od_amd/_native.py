@@ -85,6 +85,18 @@ class DodLnFold(C.Structure):
                 ("part_in", C.c_void_p), ("stats_out", C.c_void_p), ("eps", C.c_float)]
 
 
+class DodDrawLayer(C.Structure):
+    """struct dod_draw_layer (include/dinodet.h): one layer of boxes of dod_draw_detections"""
+    _fields_ = [("boxes", C.c_void_p), ("counts", C.c_void_p), ("labels", C.c_void_p), ("scores", C.c_void_p), ("K", C.c_int32),
+                ("format", C.c_int32), ("score_threshold", C.c_float), ("use_palette", C.c_int32), ("color", C.c_uint8 * 4)]
+
+
+class DodDrawStyle(C.Structure):
+    """struct dod_draw_style (include/dinodet.h)"""
+    _fields_ = [("thickness", C.c_int32), ("fill_alpha", C.c_int32), ("font_scale", C.c_int32), ("palette_size", C.c_int32),
+                ("palette", C.c_void_p), ("names", C.c_void_p), ("n_names", C.c_int32), ("name_len", C.c_int32), ("font", C.c_void_p)]
+
+
 # include/dinodet_tuning.h: exported by -DDINODET_TUNING builds only (tools/ load one through DINODET_LIB); bound when present
 TUNING_SYMBOLS = {
     "dod_debug_gemm_stamps": (_I, [_P]),
@@ -145,6 +157,7 @@ SYMBOLS = {
     "dod_postprocess": (_I, [_P, _I, _I, _I, _P, _F, _P, C.c_int64, _P, _P, _SZ, _P]),
     "dod_detect_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "dod_detect": (_I, [_P, _I, _I, _I, _I, _P, _F, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "dod_draw_detections": (_I, [_P, _I, _I, _I, _I, C.POINTER(DodDrawLayer), C.POINTER(DodDrawLayer), C.POINTER(DodDrawStyle), _P, _P]),
     "dod_preprocess": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dod_preprocess_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dod_preprocess_aug": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),

@@ -325,6 +325,76 @@ int dod_detect(const float* det, int B, int Q, int C, int first_class, const flo
                float iou_threshold, int class_agnostic, int clamp, float* scores, int32_t* labels, int32_t* queries, float* boxes,
                int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- detections and ground truth drawn into the image batch on device ---------------------------------
+ * The counterpart of the reference's log_images (dino_detector/utils.py:360-384, whose box drawing is a TODO) and of
+ * visualize_predictions (analyze_results.py:81-203, matplotlib on the host): up to two LAYERS of boxes -- `below` (ground truth) first,
+ * `above` (predictions) over it -- are rendered into a fresh uint8 batch as outlined, optionally filled and captioned rectangles.  One
+ * launch on `stream`, no host synchronisation, no atomics, no data-dependent shape: every output byte is a function of the input bits,
+ * identical from run to run and on any stream.  All integer arithmetic below is exact; every fp32 operation rounds once.
+ *   images      images_fp32 == 0: uint8 [B, H, W, 3] (the buffer dod_forward_u8 takes); 1: fp32 [B, 3, H, W] in [0, 1], each value x
+ *               becoming the byte  v = x * 255.0f; v = v + 0.5f; NaN -> 0; v < 0 -> 0; v > 255 -> 255; truncate.
+ *   out         uint8 [B, H, W, 3], never the input buffer.  Any byte alignment; nothing outside its B*H*W*3 bytes is written.
+ *   a layer     struct dod_draw_layer, or NULL / boxes == NULL / K == 0 for "absent".  boxes fp32 [B, K, 4] (16-byte aligned), counts
+ *               int32 [B] (NULL = K rows everywhere), labels int32 [B, K], scores fp32 [B, K] or NULL: the tensors dod_detect writes.
+ *               Rows at and beyond min(max(counts[b], 0), K) are ignored.  format 0: x1, y1, x2, y2 in pixels of this image.  format 1:
+ *               normalised cx, cy, w, h converted as dod_detect does with sizes = (H, W) and no clamp:  x1 = cx - 0.5f * w, then
+ *               x1 = x1 * (float)W  (y with h and H, x2 / y2 with +).  A row with scores != NULL is skipped when score_threshold is
+ *               not below 0 and score <= score_threshold.
+ *   rectangle   a row with a NaN coordinate is skipped.  xa = I(floorf(x1)), ya = I(floorf(y1)), xb = I(ceilf(x2)) - 1,
+ *               yb = I(ceilf(y2)) - 1 with I(v) = (int) of v saturated to [-32768, 32767] first (infinities saturate).  The row is
+ *               skipped when xb < xa or yb < ya, or when the rectangle [xa, xb] x [ya, yb] (bounds included) has no pixel in the
+ *               image [0, W) x [0, H).  Only pixels inside the image are ever touched.
+ *   colour      use_palette != 0: palette[m] with m = label mod palette_size taken non-negative (uint8 [palette_size, 3] device table);
+ *               otherwise the layer's own color[0..2] (r, g, b).
+ *   outline     thickness t: a pixel (x, y) of the rectangle with min(x - xa, xb - x, y - ya, yb - y) < t takes the colour, opaque.
+ *               (For sides >= 2 t this is Pillow's ImageDraw.rectangle([xa, ya, xb, yb], outline = c, width = t).)
+ *   fill        fill_alpha a > 0: every other pixel of the rectangle becomes, per channel,  div255(dst * (255 - a) + c * a)  with
+ *               div255(u) = ((u + 128) + ((u + 128) >> 8)) >> 8   (Pillow's RGBA-mode rectangle(fill = (r, g, b, a))).  a == 0: untouched.
+ *   caption     font_scale s > 0.  Text: the row's class name -- the bytes of names[label] (uint8 [n_names, name_len] device table,
+ *               zero padded) up to the first zero byte -- when names != NULL, 0 <= label < n_names and that name is not empty;
+ *               otherwise the decimal label ('-' first when negative).  With scores != NULL a space, the decimal of
+ *               p = floorf(score * 100.0f + 0.5f) (NaN -> 0, then clamped to [0, 999]) and '%' follow.  n = number of characters.
+ *               Rectangle: cw = min(6 s n + s, W), ch = min(9 s, H); cy0 = ya - ch when that is >= 0 (above the box), else ya
+ *               (inside it); then cy0 = min(max(cy0, 0), H - ch), cx0 = min(max(xa, 0), W - cw): the caption never leaves the image,
+ *               and one wider or higher than the image is cut at its right / bottom edge.  Pixel (x, y) of [cx0, cx0 + cw) x
+ *               [cy0, cy0 + ch): u = x - cx0 - s, v = y - cy0 - s (a margin of s pixels); for u, v >= 0: character i = u / (6 s), glyph
+ *               column gx = (u mod 6 s) / s, glyph row gy = v / s; the pixel is TEXT when i < n, gx < 5, gy < 7 and bit (4 - gx) of
+ *               font[g][gy] is set, g = byte - 0x20 for a byte in 0x20..0x7F, else 95.  font: uint8 [96, 7] device table, 5 low bits per
+ *               row, bit 4 the leftmost column (dinov2_od_amd/visualize.py FONT_5X7 is the one copy; glyph 95 and every glyph the
+ *               font does not design are solid).  Text pixels are black (0) when 299 r + 587 g + 114 b >= 128000 for the box colour, else
+ *               white (255); every other caption pixel takes the box colour.  Both opaque.
+ *   order       painter's algorithm: layer `below`, then `above`; inside a layer rows count - 1 down to 0, so row 0 ends on top; for a
+ *               row the fill and outline, then its caption.
+ * Limits: 1 <= B <= 65535, 1 <= H, W <= 16384, 0 <= K <= 1024 per layer, thickness 1..8, fill_alpha 0..255, font_scale 0..4 (0: no
+ * captions; > 0 needs font), format 0 or 1, name_len 1..64 and n_names >= 1 when names is given, palette with palette_size >= 1 when a
+ * present layer asks for it, labels != NULL for a present layer.  Outside them, for a NULL images / out / style pointer, out == images or
+ * images_fp32 not 0 / 1 the call returns DOD_ERR_INVALID before any launch.  All data pointers are device pointers; the structs are
+ * host memory read during the call. */
+typedef struct dod_draw_layer {
+  const float* boxes;
+  const int32_t* counts;
+  const int32_t* labels;
+  const float* scores;
+  int32_t K;
+  int32_t format;
+  float score_threshold;
+  int32_t use_palette;
+  uint8_t color[4];           /* r, g, b, unused */
+} dod_draw_layer;
+typedef struct dod_draw_style {
+  int32_t thickness;
+  int32_t fill_alpha;
+  int32_t font_scale;
+  int32_t palette_size;
+  const uint8_t* palette;
+  const uint8_t* names;
+  int32_t n_names;
+  int32_t name_len;
+  const uint8_t* font;
+} dod_draw_style;
+int dod_draw_detections(const void* images, int images_fp32, int B, int H, int W, const dod_draw_layer* below,
+                        const dod_draw_layer* above, const dod_draw_style* style, uint8_t* out, void* stream);
+
 /* ---- input pipeline on device -------------------------------------------------------
  * Replaces the per-image host transform of dino_detector/train.py:584-587 -- torchvision Resize((R,R)) + ToTensor() on a
  * PIL image, i.e. Pillow's Image.resize(BILINEAR) (two-pass 8-bit fixed-point resample, antialiased when downscaling)
@@ -763,7 +833,8 @@ const char* dod_version(void);
  * (dod_op_layernorm_bwd ... dod_op_colsum_add) joined revision 6 the same way.  So did the optimizer step (dod_optim_*), the deep-supervision
  * step (dod_decoder_train_aux_*), the layered criterion (dod_set_criterion_layers_*) and the split-product operators (dod_op_gemm_f32x3,
  * dod_op_linear_f32x3; the training entry points reading cfg->precision changes no signature either) and the train-time augmentation
- * (dod_preprocess_aug, dod_preprocess_aug_u8), the host-side dispatch query (dod_test_gemm_plan) and the detection output (dod_detect*).
+ * (dod_preprocess_aug, dod_preprocess_aug_u8), the host-side dispatch query (dod_test_gemm_plan), the detection output (dod_detect*)
+ * and the drawing entry (dod_draw_detections with its two new structs, which no earlier entry reads).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);
