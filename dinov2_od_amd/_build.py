@@ -22,8 +22,8 @@ LIB = os.path.join(LIBDIR, "libdinodet.so")
 OBJ = os.path.join(ROOT, "build", "obj")
 SOURCES = ["dod_api.hip", "dod_pack.hip", "dod_forward.hip", "gemm_bf16.hip", "gemm_f32.hip", "gemm_f32x3.hip", "attn_bf16.hip", "attn_f32.hip", "rowops.hip", "deform.hip",
            "postproc.hip", "matchcost.hip", "gemm_fp8.hip", "attn_x3.hip", "gemm_x3.hip", "gemm_dispatch.hip", "preproc.hip", "attn_f32m.hip", "gemm_pp.hip", "train_ops.hip", "dec_train.hip", "tail_train.hip", "patch_embed.hip",
-           "criterion.hip", "assign.hip", "cocoeval.hip", "optim.hip", "detect.hip", "draw.hip"]
-HEADERS = [os.path.join(CSRC, "dod_common.h"), os.path.join(CSRC, "dod_internal.h"), os.path.join(CSRC, "train_internal.h"), os.path.join(CSRC, "gemm_epi.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(CSRC, "gemm_f32x_epi.h"), os.path.join(ROOT, "include", "dinodet.h"),
+           "criterion.hip", "assign.hip", "cocoeval.hip", "optim.hip", "detect.hip", "draw.hip", "detect_views.hip"]
+HEADERS = [os.path.join(CSRC, "dod_common.h"), os.path.join(CSRC, "dod_internal.h"), os.path.join(CSRC, "train_internal.h"), os.path.join(CSRC, "gemm_epi.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(CSRC, "gemm_f32x_epi.h"), os.path.join(CSRC, "detect_select.h"), os.path.join(ROOT, "include", "dinodet.h"),
            os.path.join(ROOT, "include", "dinodet_tuning.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-I" + os.path.join(ROOT, "include")]
@@ -34,9 +34,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # tools/probes/mfma_valu_overlap.hip, profiles/r04_mfma_valu_overlap_probe.txt) while plain VALU does.
 # cocoeval.hip restates pycocotools' double arithmetic: `da + ga - i` must round twice, so no FMA contraction there.
 # detect.hip: every box / IoU operation of dod_detect is one fp32 rounding (`cx - 0.5 w` then `* width`, `iou * union`), likewise.
+# detect_views.hip: dod_detect's arithmetic again, plus the view mapping (`x * vw` then `+ vl`) and the edge test (`vl + m`).
 # draw.hip: the same box conversion, and `x * 255 + 0.5` of the fp32 -> byte rule, round once per operation.
 EXTRA = {"attn_bf16.hip": ["-fno-slp-vectorize"], "attn_x3.hip": ["-fno-slp-vectorize"], "cocoeval.hip": ["-ffp-contract=off"], "detect.hip": ["-ffp-contract=off"],
-         "draw.hip": ["-ffp-contract=off"]}
+         "draw.hip": ["-ffp-contract=off"], "detect_views.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -157,6 +157,8 @@ SYMBOLS = {
     "dod_postprocess": (_I, [_P, _I, _I, _I, _P, _F, _P, C.c_int64, _P, _P, _SZ, _P]),
     "dod_detect_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "dod_detect": (_I, [_P, _I, _I, _I, _I, _P, _F, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "dod_detect_views_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "dod_detect_views": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _I, _F, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "dod_draw_detections": (_I, [_P, _I, _I, _I, _I, C.POINTER(DodDrawLayer), C.POINTER(DodDrawLayer), C.POINTER(DodDrawStyle), _P, _P]),
     "dod_preprocess": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dod_preprocess_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),

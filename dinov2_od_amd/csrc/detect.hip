@@ -15,20 +15,13 @@
 //   3. the <= K selected words are gathered into LDS (slot order is arbitrary) and sorted descending by a bitonic network: the
 //      order is a function of the words alone.
 //   4. thread t turns word t into score / label / query / box; without NMS it stores row t.
-//   5. NMS: a bit-matrix of the K x K suppression relation in LDS (one ballot per 64 pairs), a serial sweep by one wave that carries
-//      the removed set as one 64-bit word per lane, and an ordered compaction by population count.
+//   5. NMS: a bit-matrix of the K x K suppression relation in LDS, upper-triangular (one ballot per 64 pairs), a serial sweep by one
+//      wave that carries the removed set as one 64-bit word per lane, and an ordered compaction by population count.
 // The box and IoU arithmetic must round once per operation: this file is compiled with -ffp-contract=off (_build.EXTRA).
-#include "dod_common.h"
+#include "detect_select.h"       // stages 1 - 3 and 5 and the key / word helpers, shared with detect_views.hip
 #include "../../include/dinodet.h"
 
-#define DET_THREADS 1024
-#define DET_WAVES (DET_THREADS / DOD_WAVE)
-#define DET_MAX_K 1024           // one thread per output row
-#define DET_NMS_MAX_K 512        // the suppression matrix: 512 x 512 bits = 32 KiB of LDS
-#define DET_MAX_PAIRS (1 << 20)  // Q*C: the index field of the select word
-#define DET_COPIES 8
-#define DET_UNROLL 8
-#define DET_HSTRIDE 257          // 256 bins + 1: the copies of one bin sit on different banks
+#define DET_NMS_MAX_K 512        // dod_detect's documented limit with NMS
 
 struct DetArgs {
   const float* det; const float* sizes; unsigned* keys;
@@ -38,16 +31,6 @@ struct DetArgs {
   int agnostic, clamp;
 };
 
-// torch.sigmoid in fp32, as pp_sigmoid (postproc.hip)
-__device__ __forceinline__ float det_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-// larger logit <=> larger key; +0.0 (0x80000000) ranks above -0.0 (0x7FFFFFFF); 0 only for the all-ones NaN
-__device__ __forceinline__ unsigned det_key(float x) {
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ unsigned long long det_word(unsigned key, int i) {
-  return ((unsigned long long)key << 24) | ((unsigned long long)(0xFFFFFu - (unsigned)i) << 4);
-}
 __device__ __forceinline__ float det_logit(const DetArgs& a, const float* dp, int i) {
   const int q = i / a.C, c = i - q * a.C;
   return dp[(size_t)q * (a.C + 4) + c];
@@ -57,120 +40,19 @@ __device__ __forceinline__ unsigned det_make_key(const DetArgs& a, int i, float 
   const bool cand = c >= a.first_class && x == x && (a.threshold < 0.0f || det_sigmoid(x) > a.threshold);
   return cand ? det_key(x) : 0u;
 }
-// use(i, load(i)) for every i < N of this thread (i = tid, tid + 1024, ...), DET_UNROLL loads in flight before the first use: a pass is
-// a few dozen elements per thread, and one L2 round trip per element would be most of its time
-template <class Load, class Use>
-__device__ __forceinline__ void det_for_each(int N, int tid, Load load, Use use) {
-  for (int base = tid; base < N; base += DET_UNROLL * DET_THREADS) {
-    decltype(load(0)) v[DET_UNROLL];
-#pragma unroll
-    for (int u = 0; u < DET_UNROLL; ++u) {
-      const int i = base + u * DET_THREADS;
-      v[u] = i < N ? load(i) : decltype(load(0))();
-    }
-#pragma unroll
-    for (int u = 0; u < DET_UNROLL; ++u) {
-      const int i = base + u * DET_THREADS;
-      if (i < N) use(i, v[u]);
-    }
-  }
-}
-__device__ __forceinline__ float det_clamp(float v, float hi) { return v < 0.0f ? 0.0f : (v > hi ? hi : v); }
-__device__ __forceinline__ float det_min(float a, float b) { return a < b ? a : b; }
-__device__ __forceinline__ float det_max(float a, float b) { return a > b ? a : b; }
 
 template <bool NMS>
 __global__ __launch_bounds__(DET_THREADS) void det_kernel(const DetArgs a) {
-  __shared__ unsigned hist[DET_COPIES * DET_HSTRIDE];
-  __shared__ unsigned long long sel[DET_MAX_K];
-  __shared__ unsigned long long s_prefix;
-  __shared__ unsigned s_kk, s_done, s_cnt;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ DetSelectLds L;
+  const int tid = threadIdx.x;
   const int b = blockIdx.x, C = a.C, K = a.K;
   const int N = a.Q * C;
   const float* dp = a.det + (size_t)b * a.Q * (C + 4);
   unsigned* kp = a.keys + (size_t)b * N;
-  if (tid == 0) s_cnt = 0;
 
-  // ---- 1 + 2: keys, and the threshold word Tc: selected <=> key != 0 && word >= Tc
-  unsigned long long Tc = 0;
-  if (N < K) {                                   // everything that is a candidate is selected
-    det_for_each(N, tid, [&](int i) { return det_logit(a, dp, i); }, [&](int i, float x) { kp[i] = det_make_key(a, i, x); });
-    __syncthreads();
-  } else {
-    unsigned long long prefix = 0;
-    unsigned kk = (unsigned)K;                   // rank still wanted among the words that share `prefix` above the current digit
-    for (int shift = 48; shift >= 0; shift -= 8) {
-      for (int j = tid; j < DET_COPIES * DET_HSTRIDE; j += DET_THREADS) hist[j] = 0;
-      __syncthreads();
-      unsigned* const hcopy = hist + (lane & (DET_COPIES - 1)) * DET_HSTRIDE;
-      if (shift == 48)
-        det_for_each(N, tid, [&](int i) { return det_logit(a, dp, i); }, [&](int i, float x) {
-          const unsigned key = det_make_key(a, i, x);
-          kp[i] = key;
-          atomicAdd(&hcopy[key >> 24], 1u);
-        });
-      else
-        det_for_each(N, tid, [&](int i) { return kp[i]; }, [&](int i, unsigned key) {
-          const unsigned long long w = det_word(key, i);
-          if ((w >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hcopy[(unsigned)((w >> shift) & 255u)], 1u);
-        });
-      __syncthreads();
-      if (wave == 0) {                           // lane l owns digits 255-4l .. 252-4l: a prefix sum over lanes walks the digits downwards
-        unsigned c4[4], s = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int d = 255 - (4 * lane + j);
-          unsigned n = 0;
-#pragma unroll
-          for (int cp = 0; cp < DET_COPIES; ++cp) n += hist[cp * DET_HSTRIDE + d];
-          c4[j] = n; s += n;
-        }
-        unsigned incl = s;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
-        unsigned above = incl - s;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (above < kk && kk <= above + c4[j]) {
-            s_prefix = prefix | ((unsigned long long)(255 - (4 * lane + j)) << shift);
-            s_kk = kk - above;
-            s_done = c4[j] == kk - above ? 1u : 0u;     // the whole bin is wanted: lower digits need no pass
-          }
-          above += c4[j];
-        }
-      }
-      __syncthreads();
-      prefix = s_prefix; kk = s_kk;
-      if (s_done) break;
-    }
-    Tc = prefix;
-  }
-
-  // ---- 3: gather and sort
-  det_for_each(N, tid, [&](int i) { return kp[i]; }, [&](int i, unsigned key) {
-    const unsigned long long w = det_word(key, i);
-    if (key != 0u && w >= Tc) {
-      const unsigned slot = atomicAdd(&s_cnt, 1u);
-      if (slot < DET_MAX_K) sel[slot] = w;
-    }
-  });
-  __syncthreads();
-  const int n = (int)(s_cnt < (unsigned)K ? s_cnt : (unsigned)K);
-  int P = 1;
-  while (P < n) P <<= 1;
-  if (tid >= n && tid < P) sel[tid] = 0;
-  __syncthreads();
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (tid < (P >> 1)) {
-        const int lo = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), hi = lo + j;
-        const unsigned long long x = sel[lo], y = sel[hi];
-        const bool desc = (lo & k) == 0;
-        if ((x < y) == desc) { sel[lo] = y; sel[hi] = x; }
-      }
-      __syncthreads();
-    }
+  // ---- 1 - 3: keys, radix select, gather and sort (detect_select.h)
+  const int n = det_select_sort(L, N, K, tid, kp, [&](int i) { return det_logit(a, dp, i); }, [&](int i, float x) { return det_make_key(a, i, x); });
+  const unsigned long long* const sel = L.sel;
 
   // ---- 4: thread t decodes word t
   float sc = 0.0f, x1 = 0.0f, y1 = 0.0f, x2 = 0.0f, y2 = 0.0f;
@@ -194,75 +76,16 @@ __global__ __launch_bounds__(DET_THREADS) void det_kernel(const DetArgs a) {
     }
     if (tid == 0) a.counts[b] = n;
   } else {
-    // ---- 5: greedy NMS over the n sorted candidates (n <= DET_NMS_MAX_K: the host refuses a larger K)
-    __shared__ float4 nbox[DET_NMS_MAX_K];
-    __shared__ float narea[DET_NMS_MAX_K];
-    __shared__ int nlab[DET_NMS_MAX_K];
-    __shared__ unsigned long long mat[DET_NMS_MAX_K * (DET_NMS_MAX_K / 64)];
-    __shared__ unsigned long long remw[DET_NMS_MAX_K / 64];
-    if (tid < n) {
-      nbox[tid] = make_float4(x1, y1, x2, y2);
-      narea[tid] = det_max(0.0f, x2 - x1) * det_max(0.0f, y2 - y1);
-      nlab[tid] = lab;
-    }
-    __syncthreads();
-    const int words = (n + 63) >> 6;
-    for (int w = 0; w < words; ++w) {                          // word w of every row i with i >> 6 <= w: bit j - 64w says "i suppresses j", j > i only
-      const int j = w * 64 + lane;                             // this lane's column stays in registers for all rows of the word
-      const bool jin = j < n;
-      const float4 bj = jin ? nbox[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      const float aj = jin ? narea[j] : 0.0f;
-      const int lj = jin ? nlab[j] : -2;
-      const int rows = n < w * 64 + 64 ? n : w * 64 + 64;
-      for (int i = wave; i < rows; i += DET_WAVES) {           // the row's box, area and label are wave-uniform reads that depend on nothing
-        const float4 bi = nbox[i];
-        const float ai = narea[i];
-        const int li = nlab[i];
-        bool bit = false;
-        if (j > i && jin && (a.agnostic || li == lj)) {
-          const float iw = det_max(0.0f, det_min(bi.z, bj.z) - det_max(bi.x, bj.x));
-          const float ih = det_max(0.0f, det_min(bi.w, bj.w) - det_max(bi.y, bj.y));
-          const float inter = iw * ih;
-          const float uni = (ai + aj) - inter;
-          bit = inter > a.iou * uni;
-        }
-        const unsigned long long m = __ballot(bit);
-        if (lane == 0) mat[i * words + w] = m;
-      }
-    }
-    __syncthreads();
-    if (wave == 0) {                                           // lane l carries word l of the removed set
-      unsigned long long rem = 0;
-      for (int i0 = 0; i0 < n; i0 += 8) {                      // eight rows are loaded before the first decision: they do not depend on it
-        unsigned long long row[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)                            // words below the diagonal were never written: they hold no bit
-          row[u] = (lane < words && lane >= ((i0 + u) >> 6) && i0 + u < n) ? mat[(i0 + u) * words + lane] : 0ull;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {                          // a row past n is 0: it changes nothing
-          const int i = i0 + u;
-          const unsigned lo = __builtin_amdgcn_readlane((unsigned)rem, i >> 6), hi = __builtin_amdgcn_readlane((unsigned)(rem >> 32), i >> 6);
-          const unsigned long long mine = ((unsigned long long)hi << 32) | lo;
-          if (!((mine >> (i & 63)) & 1ull)) rem |= row[u];
-        }
-      }
-      if (lane < DET_NMS_MAX_K / 64) remw[lane] = lane < words ? rem : 0ull;
-    }
-    __syncthreads();
-    int total = 0, rank = 0;
-    for (int w = 0; w < words; ++w) {
-      const int left = n - 64 * w;
-      const unsigned long long valid = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
-      const unsigned long long kept = ~remw[w] & valid;
-      total += __popcll(kept);
-      if (w < (tid >> 6)) rank += __popcll(kept);
-      else if (w == (tid >> 6)) rank += __popcll(kept & ((1ull << (tid & 63)) - 1ull));
-    }
+    // ---- 5: greedy NMS over the n sorted candidates (n <= DET_NMS_MAX_K: the host refuses a larger K), detect_select.h
+    __shared__ DetNmsLds<DET_NMS_MAX_K> S;
+    det_nms(S, n, tid, make_float4(x1, y1, x2, y2), lab, a.iou, a.agnostic != 0, false);
+    int rank;
+    const int total = det_nms_rank(S, n, tid, rank);
     if (tid >= total && tid < K) {                             // padding rows
       a.scores[o + tid] = 0.0f; a.labels[o + tid] = -1; a.queries[o + tid] = -1;
       reinterpret_cast<float4*>(a.boxes)[o + tid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
-    if (tid < n && !((remw[tid >> 6] >> (tid & 63)) & 1ull)) { // a survivor moves to row rank <= tid, rank < total
+    if (tid < n && !((S.rem[tid >> 6] >> (tid & 63)) & 1ull)) { // a survivor moves to row rank <= tid, rank < total
       a.scores[o + rank] = sc; a.labels[o + rank] = lab; a.queries[o + rank] = qi;
       reinterpret_cast<float4*>(a.boxes)[o + rank] = make_float4(x1, y1, x2, y2);
     }

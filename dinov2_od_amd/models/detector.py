@@ -90,6 +90,22 @@ class DINOv2ObjectDetector(_EngineMixin, nn.Module):   # state-dict keys already
         finally:
             self.train(was_training)
 
+    def detect_sliced(self, images, size=None, tile=None, overlap=0.2, full_view=True, flip=False, max_batch=64, **kw):
+        """raw uint8 RGB images [H_i, W_i, 3] (as `preprocess_batch` takes them) -> slicing.SlicedDetections in each image's own
+        pixels: the model runs on the whole image (full_view), on overlapping tiles of `tile` source pixels a side (slicing.plan_views;
+        None = `size`) and with `flip` on their mirrored copies, every view resized to `size` (None = 224 x 224), and the answers are
+        merged by one dod_detect_views launch (slicing.detect_views_packed takes **kw: top_k, threshold, nms_iou, nms_metric,
+        class_agnostic, clamp, edge_margin, skip_background).  The views go through forward_packed_u8 in chunks of at most max_batch.
+        Runs the eval-mode forward under no_grad and puts the model back into the mode it was in; no host sync after staging."""
+        from ..slicing import detect_sliced
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                return detect_sliced(self, images, size, tile, overlap, full_view, flip, max_batch, **kw)
+        finally:
+            self.train(was_training)
+
     def forward(self, pixel_values):
         """pixel_values [batch, 3, H, W] -> {"pred_logits", "pred_boxes"} (detector.py:58-69)."""
         if self._use_autograd(pixel_values):            # train(): autograd composite of the same math (detector.py:58-69)

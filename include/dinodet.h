@@ -325,6 +325,54 @@ int dod_detect(const float* det, int B, int Q, int C, int first_class, const flo
                float iou_threshold, int class_agnostic, int clamp, float* scores, int32_t* labels, int32_t* queries, float* boxes,
                int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sliced and flip-augmented inference: the detections of several views of an image merged on device ---------
+ * A fixed-square forward gives a small object one or two patches; the remedy is to run the model on overlapping tiles of the source
+ * image next to the whole image, optionally on mirrored copies, and to merge the answers in source-image coordinates.  dod_detect_views
+ * is that merge: dod_detect over ALL views of an image at once, every box mapped back through its view's rectangle and mirror flag.
+ * Fixed-shape outputs, one launch on `stream`, no host synchronisation, no atomics on global memory: the results are a function of
+ * the input bits, bit-identical from run to run and on any stream.
+ *   det            fp32 [V, Q, C+4]: the packed forward output of all V views of all B images, view-major.
+ *   view_offsets   int32 [B+1], non-decreasing, view_offsets[0] = 0, view_offsets[B] = V: the views of image b are rows
+ *                  view_offsets[b] .. view_offsets[b+1] - 1; v below is the index LOCAL to the image, v0 = view_offsets[b].  An image
+ *                  may have no view: it gets count 0 and padding rows.
+ *   view_rects     int32 [V, 4]: (left, top, width, height) = (vl, vt, vw, vh) of the view in source pixels;  view_flips uint8 [V]:
+ *                  non-zero = the view was mirrored left-right.  The tensors, in the format, that dod_preprocess_aug* reads as `crops`
+ *                  and `flips`.
+ *   sizes          fp32 [B, 2]: (height_b, width_b) of the source images, as dod_detect takes them; not optional here.
+ *   candidates of image b   every (v, q, c) over its views with c >= first_class whose logit is not NaN and for which threshold < 0
+ *                  or sigmoid(logit) > threshold (dod_detect's rule), and whose (v, q) passes the edge filter below.
+ *   order          logit descending on the logit's bits with dod_detect's key image (+0.0 before -0.0, +inf first, -inf last); ties by
+ *                  flat index (v*Q + q)*C + c ascending.  The first K candidates are selected.
+ *   box            fp32, one rounding per operation, in this order:  x1 = cx - 0.5f*w, x2 = cx + 0.5f*w, y1 = cy - 0.5f*h,
+ *                  y2 = cy + 0.5f*h;  with the flip set  t = 1.0f - x2; x2 = 1.0f - x1; x1 = t;  then  x = x * (float)vw, then
+ *                  x = x + (float)vl  for x1 and x2, and  y = y * (float)vh, then y = y + (float)vt  for y1 and y2;  then the edge
+ *                  filter;  then with clamp != 0 dod_detect's clamp to [0, width_b] and [0, height_b].
+ *   edge filter    edge_margin m > 0 (m <= 0 or NaN: off) drops partial objects cut by a tile border.  A (v, q) is no candidate when
+ *                  any of  vl > 0 && x1 < (float)vl + m;  (float)(vl + vw) < width_b && x2 > (float)(vl + vw) - m;
+ *                  vt > 0 && y1 < (float)vt + m;  (float)(vt + vh) < height_b && y2 > (float)(vt + vh) - m  holds, on the box before
+ *                  the clamp (vl + vw is the integer sum).  Every comparison is false on NaN.  A border of the view that is also a
+ *                  border of the source image never filters.
+ *   NMS (iou_threshold >= 0)  greedy over the selected candidates in their order, on the output boxes, with dod_detect's iw, ih,
+ *                  inter, area and union arithmetic and its class rule; pairs of one view are treated like any other.
+ *                  nms_metric 0 (IoU): j is suppressed by an earlier survivor i when inter > iou_threshold * union;
+ *                  nms_metric 1 (intersection over the smaller box, what slicing tools use across views): when
+ *                  inter > iou_threshold * min(area_i, area_j), min(a, b) = a < b ? a : b.  No division in either form.
+ *                  Survivors are compacted to the front in order.  K may be 1024 here: the relation is kept upper-triangular in LDS.
+ *   outputs        scores [B, K] f32, labels [B, K] i32, views [B, K] i32 (v, local to the image), queries [B, K] i32, boxes
+ *                  [B, K, 4] f32 xyxy in source pixels (16-byte aligned), counts [B] i32.  Rows at and beyond counts[b] are padding:
+ *                  score 0, label, view and query -1, box 0.
+ * Limits: 1 <= K <= 1024 with or without NMS, Q*C <= 2^20, C >= 1, 0 <= first_class < C, B, Q >= 1, V >= 0, nms_metric 0 or 1;
+ * outside them, for a NULL pointer (det, view_rects and view_flips may be NULL only when V == 0), a boxes pointer that is not 16-byte
+ * aligned or a workspace below dod_detect_views_workspace_bytes(V, Q, C, K) (which is 0 outside the limits and never 0 inside them)
+ * the call returns DOD_ERR_INVALID before any launch.  (views of one image) * Q * C <= 2^20 is a limit on device data, which the
+ * call does not read on the host: the caller keeps it (dinov2_od_amd.slicing.plan_views raises), and an image whose offsets break
+ * it, decrease or leave [0, V] is treated as an image without views.  All pointers are device pointers. */
+size_t dod_detect_views_workspace_bytes(int V, int Q, int C, int K);
+int dod_detect_views(const float* det, int B, int V, int Q, int C, const int32_t* view_offsets, const int32_t* view_rects,
+                     const uint8_t* view_flips, const float* sizes, int first_class, float threshold, int K, float iou_threshold,
+                     int nms_metric, int class_agnostic, int clamp, float edge_margin, float* scores, int32_t* labels, int32_t* views,
+                     int32_t* queries, float* boxes, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- detections and ground truth drawn into the image batch on device ---------------------------------
  * The counterpart of the reference's log_images (dino_detector/utils.py:360-384, whose box drawing is a TODO) and of
  * visualize_predictions (analyze_results.py:81-203, matplotlib on the host): up to two LAYERS of boxes -- `below` (ground truth) first,
@@ -834,7 +882,8 @@ const char* dod_version(void);
  * step (dod_decoder_train_aux_*), the layered criterion (dod_set_criterion_layers_*) and the split-product operators (dod_op_gemm_f32x3,
  * dod_op_linear_f32x3; the training entry points reading cfg->precision changes no signature either) and the train-time augmentation
  * (dod_preprocess_aug, dod_preprocess_aug_u8), the host-side dispatch query (dod_test_gemm_plan), the detection output (dod_detect*)
- * and the drawing entry (dod_draw_detections with its two new structs, which no earlier entry reads).
+ * and the drawing entry (dod_draw_detections with its two new structs, which no earlier entry reads) and the merge of sliced
+ * inference (dod_detect_views*).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);
