@@ -35,6 +35,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # cocoeval.hip restates pycocotools' double arithmetic: `da + ga - i` must round twice, so no FMA contraction there.
 # detect.hip: every box / IoU operation of dod_detect is one fp32 rounding (`cx - 0.5 w` then `* width`, `iou * union`), likewise.
 # detect_views.hip: dod_detect's arithmetic again, plus the view mapping (`x * vw` then `+ vl`) and the edge test (`vl + m`).
+#   dod_fuse_views in the same file: `sum + s * x` is a rounded product, then a rounded sum, and `mean * T / N` rounds twice.
 # draw.hip: the same box conversion, and `x * 255 + 0.5` of the fp32 -> byte rule, round once per operation.
 EXTRA = {"attn_bf16.hip": ["-fno-slp-vectorize"], "attn_x3.hip": ["-fno-slp-vectorize"], "cocoeval.hip": ["-ffp-contract=off"], "detect.hip": ["-ffp-contract=off"],
          "draw.hip": ["-ffp-contract=off"], "detect_views.hip": ["-ffp-contract=off"]}

@@ -159,6 +159,8 @@ SYMBOLS = {
     "dod_detect": (_I, [_P, _I, _I, _I, _I, _P, _F, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "dod_detect_views_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "dod_detect_views": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _I, _F, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "dod_fuse_views_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "dod_fuse_views": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _I, _F, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "dod_draw_detections": (_I, [_P, _I, _I, _I, _I, C.POINTER(DodDrawLayer), C.POINTER(DodDrawLayer), C.POINTER(DodDrawStyle), _P, _P]),
     "dod_preprocess": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dod_preprocess_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),

@@ -1,7 +1,8 @@
 // What dod_detect (detect.hip) and dod_detect_views (detect_views.hip) share: the order-preserving key image of a logit, the 56-bit
 // select word, stages 1 - 3 of the one-workgroup-per-image design -- key pass, radix select of the K-th largest word, gather and
-// bitonic sort in LDS -- and stage 5, greedy NMS through a bit matrix in LDS.  Both files are compiled with -ffp-contract=off
-// (_build.EXTRA): the overlap arithmetic of stage 5 rounds once per operation.
+// bitonic sort in LDS (det_sort_desc, which the fusing merge of detect_views.hip runs a second time over its fused scores) -- and
+// stage 5, greedy NMS through a bit matrix in LDS.  Both files are compiled with -ffp-contract=off (_build.EXTRA): the overlap
+// arithmetic of stage 5 rounds once per operation.
 #pragma once
 #include "dod_common.h"
 
@@ -52,6 +53,25 @@ struct DetSelectLds {
   unsigned long long prefix;
   unsigned kk, done, cnt;
 };
+
+// The n <= DET_MAX_K words sel[0 .. n) (written, not yet fenced) sorted descending, by all DET_THREADS threads: a bitonic network over
+// the next power of two, words n .. P - 1 filled with 0.  n is uniform over the workgroup; ends behind a barrier.
+__device__ __forceinline__ void det_sort_desc(unsigned long long* sel, int n, int tid) {
+  int P = 1;
+  while (P < n) P <<= 1;
+  if (tid >= n && tid < P) sel[tid] = 0;
+  __syncthreads();
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (tid < (P >> 1)) {
+        const int lo = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), hi = lo + j;
+        const unsigned long long x = sel[lo], y = sel[hi];
+        const bool desc = (lo & k) == 0;
+        if ((x < y) == desc) { sel[lo] = y; sel[hi] = x; }
+      }
+      __syncthreads();
+    }
+}
 
 // Stages 1 - 3 for the N flat indices of one image, by all DET_THREADS threads of the workgroup: kp[i] = make_key(i, load(i)) (0 = no
 // candidate), the K largest words det_word(key, i) of the candidates into L.sel[0 .. n), sorted descending; returns n <= K.
@@ -125,20 +145,7 @@ __device__ __forceinline__ int det_select_sort(DetSelectLds& L, int N, int K, in
   });
   __syncthreads();
   const int n = (int)(L.cnt < (unsigned)K ? L.cnt : (unsigned)K);
-  int P = 1;
-  while (P < n) P <<= 1;
-  if (tid >= n && tid < P) L.sel[tid] = 0;
-  __syncthreads();
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (tid < (P >> 1)) {
-        const int lo = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), hi = lo + j;
-        const unsigned long long x = L.sel[lo], y = L.sel[hi];
-        const bool desc = (lo & k) == 0;
-        if ((x < y) == desc) { L.sel[lo] = y; L.sel[hi] = x; }
-      }
-      __syncthreads();
-    }
+  det_sort_desc(L.sel, n, tid);
   return n;
 }
 

@@ -12,7 +12,8 @@
 //   5. NMS with K up to 1024 (detect_select.h, the code dod_detect runs at 512): the suppression relation is stored upper-triangular,
 //      so 1024 rows take 68 KiB instead of 128 KiB, and with boxes, areas, labels, select words and histograms the kernel declares about
 //      109 KiB of the CU's 160 KiB of LDS.  K <= 512 runs an instance with an 18 KiB triangle.
-// The box, edge and overlap arithmetic must round once per operation: this file is compiled with -ffp-contract=off (_build.EXTRA).
+//   5'. dod_fuse_views (fv_kernel, below): weighted boxes fusion in the place of NMS, on the same stages 0 - 4 (dv_candidates).
+// The box, edge, overlap and fusion arithmetic must round once per operation: this file is compiled with -ffp-contract=off (_build.EXTRA).
 #include "detect_select.h"
 #include "../../include/dinodet.h"
 
@@ -50,12 +51,13 @@ __device__ __forceinline__ bool dv_cut(const DvBox& b, const DvRect& r, float m,
   return (r.l > 0 && b.x1 < (float)r.l + m) || (right < iw && b.x2 > right - m) ||
          (r.t > 0 && b.y1 < (float)r.t + m) || (bottom < ih && b.y2 > bottom - m);
 }
-// NMSK: 0 = no NMS, else the largest K of this instance (512 or 1024)
-template <int NMSK>
-__global__ __launch_bounds__(DET_THREADS) void dv_kernel(const DvArgs a) {
-  __shared__ DetSelectLds L;
-  const int tid = threadIdx.x;
-  const int b = blockIdx.x, C = a.C, Q = a.Q, K = a.K;
+// what stages 0 - 4 leave in thread t: candidate t of the image's n sorted candidates (score 0, label / view / query -1, box 0 for t >= n)
+struct DvCand { float sc, x1, y1, x2, y2; int lab, vi, qi, n, v0, nv; float ih, iw; };
+
+// Stages 0 - 4 for image b by all DET_THREADS threads, shared by dv_kernel and fv_kernel; v0 / nv / ih / iw: the image's first view, view
+// count (0 when its offsets are out of range) and size.  Ends behind det_select_sort's last barrier: L.sel holds the sorted words.
+__device__ __forceinline__ DvCand dv_candidates(DetSelectLds& L, const DvArgs& a, int b, int tid) {
+  const int C = a.C, Q = a.Q, K = a.K;
   int v0 = a.voffs[b], nv = a.voffs[b + 1] - v0;
   if (v0 < 0 || nv < 0 || v0 > a.V - nv || (long long)nv * Q * C > DET_MAX_PAIRS) { v0 = 0; nv = 0; }   // no view of this image is read
   const int R = nv * Q, N = R * C;
@@ -91,18 +93,29 @@ __global__ __launch_bounds__(DET_THREADS) void dv_kernel(const DvArgs a) {
   const unsigned long long* const sel = L.sel;
 
   // ---- 4: thread t decodes word t
-  float sc = 0.0f, x1 = 0.0f, y1 = 0.0f, x2 = 0.0f, y2 = 0.0f;
-  int lab = -1, qi = -1, vi = -1;
+  DvCand d{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1, -1, -1, n, v0, nv, ih, iw};
   if (tid < n) {
     const int idx = (int)(0xFFFFFu - (unsigned)((sel[tid] >> 4) & 0xFFFFFu));
     const int r = idx / C;
-    lab = idx - r * C; vi = r / Q; qi = r - vi * Q;
+    d.lab = idx - r * C; d.vi = r / Q; d.qi = r - d.vi * Q;
     const float* row = dp + (size_t)r * (C + 4);
-    sc = det_sigmoid(row[lab]);
-    const DvBox bx = dv_box(row + C, dv_rect(a, v0 + vi), a.flips[v0 + vi] != 0);
-    x1 = bx.x1; y1 = bx.y1; x2 = bx.x2; y2 = bx.y2;
-    if (a.clamp) { x1 = det_clamp(x1, iw); y1 = det_clamp(y1, ih); x2 = det_clamp(x2, iw); y2 = det_clamp(y2, ih); }
+    d.sc = det_sigmoid(row[d.lab]);
+    const DvBox bx = dv_box(row + C, dv_rect(a, v0 + d.vi), a.flips[v0 + d.vi] != 0);
+    d.x1 = bx.x1; d.y1 = bx.y1; d.x2 = bx.x2; d.y2 = bx.y2;
+    if (a.clamp) { d.x1 = det_clamp(d.x1, iw); d.y1 = det_clamp(d.y1, ih); d.x2 = det_clamp(d.x2, iw); d.y2 = det_clamp(d.y2, ih); }
   }
+  return d;
+}
+
+// NMSK: 0 = no NMS, else the largest K of this instance (512 or 1024)
+template <int NMSK>
+__global__ __launch_bounds__(DET_THREADS) void dv_kernel(const DvArgs a) {
+  __shared__ DetSelectLds L;
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x, K = a.K;
+  const DvCand d = dv_candidates(L, a, b, tid);
+  const int n = d.n, lab = d.lab, vi = d.vi, qi = d.qi;
+  const float sc = d.sc, x1 = d.x1, y1 = d.y1, x2 = d.x2, y2 = d.y2;
   const size_t o = (size_t)b * K;
   if constexpr (NMSK == 0) {
     if (tid < K) {
@@ -126,6 +139,151 @@ __global__ __launch_bounds__(DET_THREADS) void dv_kernel(const DvArgs a) {
     }
     if (tid == 0) a.counts[b] = total;
   }
+}
+
+// ---- weighted boxes fusion across the views (include/dinodet.h dod_fuse_views; tests/fuse_views_cases.py restates it) --------------
+// Stages 0 - 4 as above, then in place of NMS one pass over the n sorted candidates that builds clusters: a candidate joins the
+// cluster whose CURRENT fused box it overlaps best (IoU above the threshold, equal quotients to the lowest cluster number) or founds
+// one.  The fused box a candidate meets depends on every earlier candidate, so the chain over the candidates is serial; what runs
+// side by side is the comparison with the clusters.  Thread c holds cluster c in registers (box, area, label, five sums, members,
+// founder).  Per candidate: the waves that hold clusters compute their lanes' match words (quotient bits, ~cluster), reduce them
+// with one ballot and a readlane per matching lane, and post one word per wave; one barrier; every thread takes the largest of the
+// posted words, so all agree on the winner, and the thread that owns it updates its registers.  The posted words are double
+// buffered: a wave can overwrite a buffer only two barriers later, when every wave has read it.  One wave alone running the same
+// comparison round by round over clusters in LDS took 1.2 times the whole call's time at K = 300 and 1.9 times at K = 1024: it is
+// bound by the issue of its own VALU instructions, about 45 per round of 64 clusters.  About 76 KiB of LDS: 16 KiB select, 28 KiB candidates, 32 KiB for the clusters'
+// results, which the sort of the output rows reads across threads.
+struct FvLds {
+  float4 cbox[DET_MAX_K];                 // the candidates: box, label, score, row (v * Q + q)
+  int clab[DET_MAX_K];
+  float csc[DET_MAX_K];
+  int crow[DET_MAX_K];
+  float4 kbox[DET_MAX_K];                 // the clusters after the chain: fused box, fused score, label, members, founder
+  float kscore[DET_MAX_K];
+  int klab[DET_MAX_K];
+  int kcnt[DET_MAX_K];
+  int kfirst[DET_MAX_K];
+  unsigned long long post[2][DET_WAVES];  // the waves' best match words of the candidate, by candidate parity
+};
+
+__device__ __forceinline__ float fv_area(const float4& b) { return det_max(0.0f, b.z - b.x) * det_max(0.0f, b.w - b.y); }
+
+__global__ __launch_bounds__(DET_THREADS) void fv_kernel(const DvArgs a, int* members, int conf) {
+  __shared__ DetSelectLds L;
+  __shared__ FvLds F;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, K = a.K;
+  const DvCand d = dv_candidates(L, a, b, tid);
+  const int n = d.n;                                           // uniform: det_select_sort reads it from LDS behind a barrier
+  if (tid < n) {
+    F.cbox[tid] = make_float4(d.x1, d.y1, d.x2, d.y2);
+    F.clab[tid] = d.lab; F.csc[tid] = d.sc; F.crow[tid] = d.vi * a.Q + d.qi;
+  }
+  __syncthreads();
+
+  // ---- 5: the chain.  n, nc and the winner are the same in every thread, so every barrier is met by the whole workgroup
+  const bool can = a.iou >= 0.0f, agnostic = a.agnostic != 0;
+  float4 kb = make_float4(0.0f, 0.0f, 0.0f, 0.0f);             // cluster tid
+  float ka = 0.0f, sx1 = 0.0f, sy1 = 0.0f, sx2 = 0.0f, sy2 = 0.0f, ss = 0.0f;
+  int kl = -1, kT = 0, kf = 0;
+  int nc = 0;
+  float4 cb = kb;
+  int cl = -1;
+  float s = 0.0f;
+  if (n > 0) { cb = F.cbox[0]; cl = F.clab[0]; s = F.csc[0]; }
+  for (int i = 0; i < n; ++i) {
+    const float ab = fv_area(cb);
+    const int waves = (nc + 63) >> 6;                          // the waves that hold a cluster
+    if (can && wave < waves) {
+      unsigned long long best = 0;                             // (quotient bits, ~cluster): larger quotient first, then the lower cluster
+      if (tid < nc) {
+        const float iw = det_max(0.0f, det_min(kb.z, cb.z) - det_max(kb.x, cb.x));
+        const float ih = det_max(0.0f, det_min(kb.w, cb.w) - det_max(kb.y, cb.y));
+        const float inter = iw * ih;
+        const float uni = (ka + ab) - inter;
+        if ((agnostic || kl == cl) && inter > a.iou * uni)     // then 0 < inter <= uni: the quotient is positive and its bits are ordered
+          best = ((unsigned long long)__float_as_uint(inter / uni) << 32) | (0xFFFFFFFFu - (unsigned)tid);
+      }
+      unsigned long long m = __ballot(best != 0), top = 0;
+      while (m) {                                              // wave-uniform: one round per lane that holds a match
+        const int l = __ffsll((long long)m) - 1;
+        const unsigned lo = __builtin_amdgcn_readlane((unsigned)best, l), hi = __builtin_amdgcn_readlane((unsigned)(best >> 32), l);
+        const unsigned long long k = ((unsigned long long)hi << 32) | lo;
+        if (k > top) top = k;
+        m &= m - 1;
+      }
+      if (lane == 0) F.post[i & 1][wave] = top;
+    }
+    float4 nb = cb;                                            // the next candidate, on its way while this one is decided
+    int nl = cl;
+    float ns = s;
+    if (i + 1 < n) { nb = F.cbox[i + 1]; nl = F.clab[i + 1]; ns = F.csc[i + 1]; }
+    __syncthreads();
+    unsigned long long win = 0;
+    if (can && waves > 0) {                                    // lane w reads wave w's word: the same reduction again, in every wave
+      const unsigned long long k = lane < waves ? F.post[i & 1][lane] : 0ull;
+      unsigned long long m = __ballot(k != 0);
+      while (m) {
+        const int l = __ffsll((long long)m) - 1;
+        const unsigned lo = __builtin_amdgcn_readlane((unsigned)k, l), hi = __builtin_amdgcn_readlane((unsigned)(k >> 32), l);
+        const unsigned long long kk = ((unsigned long long)hi << 32) | lo;
+        if (kk > win) win = kk;
+        m &= m - 1;
+      }
+    }
+    const int c = win ? (int)(0xFFFFFFFFu - (unsigned)win) : nc;
+    if (tid == c) {
+      if (win) {                                               // each product rounds, then each sum (-ffp-contract=off)
+        sx1 = sx1 + s * cb.x; sy1 = sy1 + s * cb.y; sx2 = sx2 + s * cb.z; sy2 = sy2 + s * cb.w; ss = ss + s;
+        kb = make_float4(sx1 / ss, sy1 / ss, sx2 / ss, sy2 / ss);
+        if (a.clamp) { kb.x = det_clamp(kb.x, d.iw); kb.y = det_clamp(kb.y, d.ih); kb.z = det_clamp(kb.z, d.iw); kb.w = det_clamp(kb.w, d.ih); }
+        ka = fv_area(kb); kT += 1;
+      } else {
+        sx1 = s * cb.x; sy1 = s * cb.y; sx2 = s * cb.z; sy2 = s * cb.w; ss = s;
+        kb = cb; ka = ab; kl = cl; kT = 1; kf = i;
+      }
+    }
+    if (!win) ++nc;
+    cb = nb; cl = nl; s = ns;
+  }                                                            // nc <= n <= K
+
+  // ---- 6: thread c scores cluster c: how many views could have seen its fused box
+  if (tid < nc) {
+    float score = F.csc[kf];
+    if (conf != 0) {
+      int N = 0;
+      for (int v = 0; v < d.nv; ++v) {
+        const DvRect r = dv_rect(a, d.v0 + v);
+        const bool inside = kb.x >= (float)r.l && kb.y >= (float)r.t && kb.z <= (float)(r.l + r.w) && kb.w <= (float)(r.t + r.h);
+        if (inside && !(a.margin > 0.0f && dv_cut(DvBox{kb.x, kb.y, kb.z, kb.w}, r, a.margin, d.iw, d.ih))) ++N;
+      }
+      if (N < 1) N = 1;
+      const float mean = ss / (float)kT;
+      score = kT >= N ? mean : mean * (float)kT / (float)N;
+    }
+    F.kbox[tid] = kb; F.kscore[tid] = score; F.klab[tid] = kl; F.kcnt[tid] = kT; F.kfirst[tid] = kf;
+    if (conf != 0) L.sel[tid] = det_word(det_key(score), tid);
+  }
+  // ---- 7: order.  "max": founding order, which is descending in the founder's logit.  "avg": by fused score, ties by cluster number
+  int c = tid;
+  if (conf != 0) {
+    det_sort_desc(L.sel, nc, tid);
+    if (tid < nc) c = (int)(0xFFFFFu - (unsigned)((L.sel[tid] >> 4) & 0xFFFFFu));
+  } else {
+    __syncthreads();
+  }
+  const size_t o = (size_t)b * K;
+  if (tid < nc) {
+    const int row = F.crow[F.kfirst[c]], vi = row / a.Q;
+    a.scores[o + tid] = F.kscore[c]; a.labels[o + tid] = F.klab[c]; a.views[o + tid] = vi; a.queries[o + tid] = row - vi * a.Q;
+    reinterpret_cast<float4*>(a.boxes)[o + tid] = F.kbox[c];
+    members[o + tid] = F.kcnt[c];
+  } else if (tid < K) {                                        // padding rows
+    a.scores[o + tid] = 0.0f; a.labels[o + tid] = -1; a.views[o + tid] = -1; a.queries[o + tid] = -1;
+    reinterpret_cast<float4*>(a.boxes)[o + tid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    members[o + tid] = 0;
+  }
+  if (tid == 0) a.counts[b] = nc;
 }
 
 static inline size_t dv_align(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -162,5 +320,29 @@ extern "C" int dod_detect_views(const float* det, int B, int V, int Q, int C, co
   if (!(iou_threshold >= 0.0f)) hipLaunchKernelGGL(dv_kernel<0>, dim3(B), dim3(DET_THREADS), 0, s, a);
   else if (K <= 512) hipLaunchKernelGGL(dv_kernel<512>, dim3(B), dim3(DET_THREADS), 0, s, a);
   else hipLaunchKernelGGL(dv_kernel<DV_NMS_MAX_K>, dim3(B), dim3(DET_THREADS), 0, s, a);
+  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+}
+
+extern "C" size_t dod_fuse_views_workspace_bytes(int V, int Q, int C, int K) { return dod_detect_views_workspace_bytes(V, Q, C, K); }
+
+extern "C" int dod_fuse_views(const float* det, int B, int V, int Q, int C, const int32_t* view_offsets, const int32_t* view_rects,
+                              const uint8_t* view_flips, const float* sizes, int first_class, float threshold, int K,
+                              float iou_threshold, int class_agnostic, int clamp, float edge_margin, int conf, float* scores,
+                              int32_t* labels, int32_t* views, int32_t* queries, float* boxes, int32_t* members, int32_t* counts,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  if (!view_offsets || !sizes || !scores || !labels || !views || !queries || !boxes || !members || !counts) return DOD_ERR_INVALID;
+  if (B < 1 || !dv_shape_ok(V, Q, C, K) || first_class < 0 || first_class >= C) return DOD_ERR_INVALID;
+  if (V > 0 && (!det || !view_rects || !view_flips)) return DOD_ERR_INVALID;
+  if (conf != 0 && conf != 1) return DOD_ERR_INVALID;
+  if (((uintptr_t)boxes & 15) != 0) return DOD_ERR_INVALID;      // rows are stored as float4
+  if (!workspace || workspace_bytes < dod_fuse_views_workspace_bytes(V, Q, C, K)) return DOD_ERR_INVALID;
+  DvArgs a;
+  a.det = det; a.voffs = view_offsets; a.rects = view_rects; a.flips = view_flips; a.sizes = sizes;
+  a.keys = (unsigned*)workspace; a.cut = (unsigned char*)workspace + dv_keys_bytes(V, Q, C);
+  a.scores = scores; a.labels = labels; a.views = views; a.queries = queries; a.boxes = boxes; a.counts = counts;
+  a.V = V; a.Q = Q; a.C = C; a.first_class = first_class; a.K = K;
+  a.threshold = threshold; a.iou = iou_threshold; a.margin = edge_margin;
+  a.metric = 0; a.agnostic = class_agnostic; a.clamp = clamp;
+  hipLaunchKernelGGL(fv_kernel, dim3(B), dim3(DET_THREADS), 0, (hipStream_t)stream, a, members, conf);
   return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
 }

@@ -95,7 +95,8 @@ class DINOv2ObjectDetector(_EngineMixin, nn.Module):   # state-dict keys already
         pixels: the model runs on the whole image (full_view), on overlapping tiles of `tile` source pixels a side (slicing.plan_views;
         None = `size`) and with `flip` on their mirrored copies, every view resized to `size` (None = 224 x 224), and the answers are
         merged by one dod_detect_views launch (slicing.detect_views_packed takes **kw: top_k, threshold, nms_iou, nms_metric,
-        class_agnostic, clamp, edge_margin, skip_background).  The views go through forward_packed_u8 in chunks of at most max_batch.
+        class_agnostic, clamp, edge_margin, skip_background, and merge="fuse" with fuse_conf for weighted boxes fusion by one
+        dod_fuse_views launch instead, which returns slicing.FusedDetections).  The views go through forward_packed_u8 in chunks of at most max_batch.
         Runs the eval-mode forward under no_grad and puts the model back into the mode it was in; no host sync after staging."""
         from ..slicing import detect_sliced
         was_training = self.training

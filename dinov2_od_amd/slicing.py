@@ -11,7 +11,8 @@ optionally on mirrored copies, and to merge all the answers in source-image coor
 
 `DINOv2ObjectDetector.detect_sliced` is the four together.  The merge is one launch (`dod_detect_views`, include/dinodet.h; restated
 in numpy in tests/detect_views_cases.py) without a host sync: top-k over all views of an image, every box mapped back through its
-view's rectangle and mirror flag, greedy NMS across the views.  No CPU fallback: without the HIP library this module raises.
+view's rectangle and mirror flag, greedy NMS across the views -- or, with merge="fuse", weighted boxes fusion (`dod_fuse_views`,
+restated in tests/fuse_views_cases.py).  No CPU fallback: without the HIP library this module raises.
 """
 import collections
 import math
@@ -26,6 +27,8 @@ from .postprocess import Detections, MAX_TOP_K, _sizes_rows
 
 MAX_CANDIDATES = 1 << 20                 # include/dinodet.h dod_detect_views: (views of one image) * Q * C
 NMS_METRICS = {"iou": 0, "ios": 1}       # intersection over union / over the smaller box
+MERGES = ("nms", "fuse")                 # dod_detect_views / dod_fuse_views
+FUSE_CONFS = {"max": 0, "avg": 1}        # dod_fuse_views' conf: the founder's score / the mean scaled by the views that agree
 
 ViewPlan = collections.namedtuple("ViewPlan", ["offsets", "rects", "flips"])
 ViewPlan.__doc__ = """offsets int32 [B+1], rects int32 [V, 4] (left, top, width, height), flips uint8 [V]: the views of image b are rows
@@ -40,6 +43,16 @@ class SlicedDetections(Detections):
     def __new__(cls, scores, labels, boxes, queries, counts, views):
         self = super().__new__(cls, scores, labels, boxes, queries, counts)
         self.views = views
+        return self
+
+
+class FusedDetections(SlicedDetections):
+    """SlicedDetections of merge="fuse": scores, labels and boxes are the clusters' fused ones, views and queries their founders', and
+    `members` [B, K] int32 is the number of candidates fused into every row (0 in padding rows)."""
+
+    def __new__(cls, scores, labels, boxes, queries, counts, views, members):
+        self = super().__new__(cls, scores, labels, boxes, queries, counts, views)
+        self.members = members
         return self
 
 
@@ -145,13 +158,18 @@ def extract_views(images, plan, size=(224, 224), device="cuda"):
 
 
 def detect_views_packed(det, num_classes, plan, sizes, top_k=100, threshold=0.05, nms_iou=0.5, nms_metric="iou", class_agnostic=False,
-                        clamp=True, edge_margin=0.0, skip_background=True):
+                        clamp=True, edge_margin=0.0, skip_background=True, merge="nms", fuse_conf="avg"):
     """det: packed detections [V, Q, C+4] fp32 on the GPU of all views of `plan` (view-major); sizes: (height, width) of the source
     images -- one pair, one per image or a [B, 2] tensor.  Per image the `top_k` highest-logit (view, query, class) triples, ranked and
     thresholded as detect_packed does, their boxes mapped into source pixels through the view's rectangle and mirror flag; with
     edge_margin > 0 a box within that many pixels of a view border that is not a border of the source image is dropped (an object cut
     by the tile); with nms_iou (>= 0; None = no NMS) greedy NMS across the views, nms_metric "iou" or "ios" (intersection over the
     smaller box).  Returns SlicedDetections: detect_packed's Detections plus views [B, K] i32.  top_k <= 1024 with or without NMS.
+    merge="fuse" replaces the NMS by weighted boxes fusion (dod_fuse_views): candidates whose IoU with a cluster's running fused box
+    exceeds nms_iou (required then; "ios" has no meaning against a growing box and raises) are averaged with their scores as weights.
+    fuse_conf="avg" scores a cluster with its members' mean score, scaled by members / (views covering the fused box) when fewer
+    agree than could have; "max" keeps the founder's score.  Fused scores are not thresholded again.  Returns FusedDetections:
+    SlicedDetections plus members [B, K] i32.
     One launch on the current stream, no host sync."""
     if not (isinstance(det, torch.Tensor) and det.dtype == torch.float32 and det.dim() == 3):
         raise ValueError("det must be a CUDA fp32 tensor [V, Q, C+4]")
@@ -178,6 +196,16 @@ def detect_views_packed(det, num_classes, plan, sizes, top_k=100, threshold=0.05
         raise ValueError(f"nms_iou must be None or >= 0, got {nms_iou}")
     if nms_metric not in NMS_METRICS:
         raise ValueError(f"nms_metric must be one of {sorted(NMS_METRICS)}, got {nms_metric!r}")
+    if merge not in MERGES:
+        raise ValueError(f"merge must be one of {list(MERGES)}, got {merge!r}")
+    fuse = merge == "fuse"
+    if fuse:
+        if fuse_conf not in FUSE_CONFS:
+            raise ValueError(f"fuse_conf must be one of {sorted(FUSE_CONFS)}, got {fuse_conf!r}")
+        if not nms:
+            raise ValueError("merge='fuse' needs nms_iou: it is the IoU above which a candidate joins a cluster")
+        if nms_metric != "iou":
+            raise ValueError(f"merge='fuse' matches by IoU only, got nms_metric={nms_metric!r}")
     if not 1 <= K <= MAX_TOP_K:
         raise ValueError(f"top_k must be in 1..{MAX_TOP_K}, got {K}")
     st = _sizes_rows(sizes, B)
@@ -190,7 +218,18 @@ def detect_views_packed(det, num_classes, plan, sizes, top_k=100, threshold=0.05
     dev = det.device
     pd = plan_to_device(plan, dev)
     st = st.to(device=dev, dtype=torch.float32).contiguous()
-    ws = torch.empty(L.dod_detect_views_workspace_bytes(V, Q, Cn, K), dtype=torch.uint8, device=dev)
+    ws = torch.empty(L.dod_detect_views_workspace_bytes(V, Q, Cn, K), dtype=torch.uint8, device=dev)     # dod_fuse_views' is the same
+    if fuse:
+        out = FusedDetections(torch.empty(B, K, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
+                              torch.empty(B, K, 4, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
+                              torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
+                              torch.empty(B, K, dtype=torch.int32, device=dev))
+        nat.check(L.dod_fuse_views(nat.ptr(det) if V else None, B, V, Q, Cn, nat.ptr(pd.offsets), nat.ptr(pd.rects) if V else None,
+                                   nat.ptr(pd.flips) if V else None, nat.ptr(st), first, float(threshold), K, float(nms_iou),
+                                   int(bool(class_agnostic)), int(bool(clamp)), float(edge_margin), FUSE_CONFS[fuse_conf], nat.ptr(out.scores),
+                                   nat.ptr(out.labels), nat.ptr(out.views), nat.ptr(out.queries), nat.ptr(out.boxes), nat.ptr(out.members),
+                                   nat.ptr(out.counts), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+        return out
     out = SlicedDetections(torch.empty(B, K, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
                            torch.empty(B, K, 4, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
                            torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev))
@@ -203,7 +242,8 @@ def detect_views_packed(det, num_classes, plan, sizes, top_k=100, threshold=0.05
 
 
 def detect_sliced(model, images, size=None, tile=None, overlap=0.2, full_view=True, flip=False, max_batch=64, **kw):
-    """DINOv2ObjectDetector.detect_sliced (models/detector.py); `model` is in eval mode and grad is off"""
+    """DINOv2ObjectDetector.detect_sliced (models/detector.py); `model` is in eval mode and grad is off.  **kw goes to
+    detect_views_packed: merge="fuse" (with nms_iou and fuse_conf) fuses the views' boxes instead of suppressing them."""
     arrs = _pre._as_arrays(images)
     shapes = [a.shape[:2] for a in arrs]
     size = _pre._out_size((224, 224) if size is None else size)

@@ -373,6 +373,40 @@ int dod_detect_views(const float* det, int B, int V, int Q, int C, const int32_t
                      int nms_metric, int class_agnostic, int clamp, float edge_margin, float* scores, int32_t* labels, int32_t* views,
                      int32_t* queries, float* boxes, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the same merge by weighted boxes fusion instead of NMS ---------------------------------------------
+ * NMS keeps the best of the views' answers for an object and discards the rest.  dod_fuse_views averages the boxes that agree, with
+ * their scores as weights, and lowers the fused score when fewer views agree than could have seen the box.  Arguments, candidates,
+ * order, box, edge filter, limits and error codes are dod_detect_views' (there is no nms_metric: the match measure is IoU); the n <= K
+ * selected candidates 0 .. n-1, in their order, then pass ONCE through the following, in fp32 with one rounding per operation.
+ *   cluster        label, member count T, five running sums  S_x1 = sum s*x1, S_y1, S_x2, S_y2, S_s = sum s  over its members (score s,
+ *                  box x1 y1 x2 y2), its fused box, and its founder = first member.  Clusters are numbered in founding order.
+ *   match          candidate i (score s, box b, label l) matches cluster c when (class_agnostic or label_c == l) and
+ *                  inter > iou_threshold * union, with dod_detect's iw, ih, inter, area and union arithmetic between the cluster's
+ *                  CURRENT fused box (in the place of the earlier survivor i of NMS) and b.  Among several matching clusters the one
+ *                  with the largest quotient inter / union (one fp32 division) takes the candidate; equal quotients go to the lowest
+ *                  cluster number.  Every comparison is false on NaN: a NaN box founds a cluster nothing joins.  iou_threshold < 0 or
+ *                  NaN, like iou_threshold >= 1 (inter <= union), matches nothing: the result is dod_detect_views' without NMS.
+ *   update         on a match  S_k = S_k + s * coord_k  (the product rounds, then the sum),  S_s = S_s + s,  T = T + 1,  fused box
+ *                  = S_k / S_s (four divisions), then with clamp != 0 dod_detect's clamp again.  Without a match the candidate founds
+ *                  a cluster: S_k = s * coord_k, S_s = s, fused box = b itself, T = 1.
+ *   coverage       view v of the image covers a fused box f when  f.x1 >= (float)vl, f.y1 >= (float)vt, f.x2 <= (float)(vl + vw),
+ *                  f.y2 <= (float)(vt + vh)  and, with edge_margin > 0, the edge filter's predicate is false for f against v.
+ *                  Mirrored views count like plain ones.  N = max(1, number of covering views of the image).
+ *   score          conf 0 ("max"): the founder's score.  conf 1 ("avg"):  mean = S_s / (float)T;  mean if T >= N, else
+ *                  mean * (float)T / (float)N  evaluated left to right.  Scores are NOT thresholded again after fusion: `threshold`
+ *                  acts on the candidates only, and an "avg" score may lie below it.
+ *   output order   conf 0: founding order (descending in the founder's logit).  conf 1: fused score descending, ties by cluster number.
+ *   outputs        scores (fused score), labels (the cluster's), views and queries (the founder's), boxes (the fused box),
+ *                  members [B, K] i32 (T), counts [B] (the number of clusters).  Padding rows as dod_detect_views', members 0.
+ * The fused box a candidate meets depends on all earlier candidates: the pass is serial over the candidates (about half a
+ * microsecond each on an MI355X) and parallel over the clusters.  conf outside {0, 1} or a NULL members returns DOD_ERR_INVALID like the other argument errors, before any launch. */
+size_t dod_fuse_views_workspace_bytes(int V, int Q, int C, int K);
+int dod_fuse_views(const float* det, int B, int V, int Q, int C, const int32_t* view_offsets, const int32_t* view_rects,
+                   const uint8_t* view_flips, const float* sizes, int first_class, float threshold, int K, float iou_threshold,
+                   int class_agnostic, int clamp, float edge_margin, int conf, float* scores, int32_t* labels, int32_t* views,
+                   int32_t* queries, float* boxes, int32_t* members, int32_t* counts, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
 /* ---- detections and ground truth drawn into the image batch on device ---------------------------------
  * The counterpart of the reference's log_images (dino_detector/utils.py:360-384, whose box drawing is a TODO) and of
  * visualize_predictions (analyze_results.py:81-203, matplotlib on the host): up to two LAYERS of boxes -- `below` (ground truth) first,
@@ -883,7 +917,7 @@ const char* dod_version(void);
  * dod_op_linear_f32x3; the training entry points reading cfg->precision changes no signature either) and the train-time augmentation
  * (dod_preprocess_aug, dod_preprocess_aug_u8), the host-side dispatch query (dod_test_gemm_plan), the detection output (dod_detect*)
  * and the drawing entry (dod_draw_detections with its two new structs, which no earlier entry reads) and the merge of sliced
- * inference (dod_detect_views*).
+ * inference (dod_detect_views*) and its fusing form (dod_fuse_views*).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);

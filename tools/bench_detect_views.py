@@ -15,8 +15,13 @@ stable compaction; torchvision is not a dependency), all without a host sync.
   step       what slicing costs end to end: model.detect_sliced(raw images) against preprocess_batch + model.detect of the same images
              (ViT-B/14, 224 x 224 views, 100 queries, bf16), for 8 images and for 1 image, host staging included; and for the
              single image the forward of its 13 views against the merge of them, which runs on one workgroup, i.e. one CU
+  --fuse     instead of the legs above: dod_fuse_views (weighted boxes fusion, IoU 0.5, per class, "avg" scores) beside dod_detect_views
+             with NMS (the settings above) on the same inputs, both as C calls into preallocated buffers, samples alternating: the
+             two shapes above and the second one again at K = 1024; per scene the clusters and survivors per image and the largest
+             cluster.  The fusion's chain over the candidates is serial on one wave, so its time grows with K and with the number
+             of clusters a candidate is compared with.
 One JSON line on stdout.
-    python tools/bench_detect_views.py [--steps 30] [--warmup 5]"""
+    python tools/bench_detect_views.py [--steps 30] [--warmup 5] [--fuse]"""
 import argparse
 import json
 import os
@@ -102,6 +107,47 @@ def c_call(det, B, C, K, pd, st, iou):
                                      nat.ptr(qs), nat.ptr(bx), nat.ptr(ct), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
         return keep
     return call
+
+
+def c_call_fuse(det, B, C, K, pd, st, iou, conf):
+    """dod_fuse_views into buffers allocated once"""
+    L = nat.lib()
+    V, Q, _ = det.shape
+    dev = det.device
+    sc, bx = torch.empty(B, K, device=dev), torch.empty(B, K, 4, device=dev)
+    lb, vs, qs, mb, ct = (torch.empty(n, dtype=torch.int32, device=dev) for n in ((B, K), (B, K), (B, K), (B, K), (B,)))
+    ws = torch.empty(L.dod_fuse_views_workspace_bytes(V, Q, C, K), dtype=torch.uint8, device=dev)
+    keep = (sc, bx, lb, vs, qs, ct, ws, mb)
+
+    def call():
+        nat.check(L.dod_fuse_views(nat.ptr(det), B, V, Q, C, nat.ptr(pd.offsets), nat.ptr(pd.rects), nat.ptr(pd.flips), nat.ptr(st), 1, -1.0, K, iou, 0, 1,
+                                   0.0, slicing.FUSE_CONFS[conf], nat.ptr(sc), nat.ptr(lb), nat.ptr(vs), nat.ptr(qs), nat.ptr(bx), nat.ptr(mb),
+                                   nat.ptr(ct), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+        return keep
+    return call
+
+
+def fuse_legs(out, steps, warmup):
+    reps = 50
+    for B, tile, Q, C, K in SHAPES + [SHAPES[1][:4] + (1024,)]:
+        det, plan = make_case(B, tile, Q, C)
+        nv = len(plan.rects) // B
+        pd = slicing.plan_to_device(plan, det.device)
+        st = torch.tensor([HW] * B, dtype=torch.float32, device=det.device)
+        nms, fuse = c_call(det, B, C, K, pd, st, IOU), c_call_fuse(det, B, C, K, pd, st, IOU, "avg")
+        rn, rf = nms(), fuse()
+        torch.cuda.synchronize()
+        leg = {"nms_kept_per_image": round(float(rn[5].float().mean()), 1), "clusters_per_image": round(float(rf[5].float().mean()), 1),
+               "largest_cluster": int(rf[7].max()), "members_per_image": round(float(rf[7].sum()) / B, 1)}
+        for _ in range(warmup):
+            _time(nms, reps), _time(fuse, reps)
+        tn, tf = [], []
+        for _ in range(steps):                                # alternating: both sides see the same machine
+            tn.append(_time(nms, reps))
+            tf.append(_time(fuse, reps))
+        leg["nms_c_call"], leg["fuse_c_call"] = _stats(tn, reps), _stats(tf, reps)
+        leg["fuse_over_nms_median"] = round(leg["fuse_c_call"]["median_ms"] / leg["nms_c_call"]["median_ms"], 2)
+        out[f"B{B}_V{nv}_Q{Q}_C{C}_K{K}_fuse"] = leg
 
 
 def _time(fn, reps):
@@ -197,12 +243,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--fuse", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_detect_views needs a GPU"
     out = {"tool": "bench_detect_views", "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "sizes": HW, "nms_iou": IOU,
            "nms_metric": METRIC}
-    merge_legs(out, a.steps, a.warmup)
-    step_legs(out, a.steps, a.warmup)
+    if a.fuse:
+        fuse_legs(out, a.steps, a.warmup)
+    else:
+        merge_legs(out, a.steps, a.warmup)
+        step_legs(out, a.steps, a.warmup)
     print(json.dumps(out))
 
 
