@@ -11,6 +11,10 @@ bit for bit.  `augment_batch` takes the parameters explicitly; `sample_params` d
 `torch.Generator`; `TrainAugment` is the two together, the training counterpart of `ResizeToTensor`.  The targets (the
 reference's dicts, dataset.py:101-111: normalised cxcywh `boxes`, `labels`) are transformed on the host in float32: they are a
 few hundred bytes and their output shape depends on the data.  No CPU fallback for the images.
+
+Mosaic and zoom-out are composed canvases (`dod_preprocess_compose`): `compose_batch` pastes disjoint pieces, each the chain above at
+its own output size, onto a fill colour; `sample_mosaic` and `sample_zoom_out` draw the plans; `TrainAugment(mosaic_prob=...,
+zoom_out_prob=...)` mixes them with the plain chain.
 """
 import math
 
@@ -120,9 +124,216 @@ def augment_batch(images, targets, crops, flips, jitter=None, size=(224, 224), d
     return out, new_targets
 
 
+# ------------------------------------------------------------------------------------------------------------ composed canvases
+# Mosaic and zoom-out are one primitive (`dod_preprocess_compose`, include/dinodet.h): a canvas of a fill colour with disjoint
+# rectangular pieces pasted into it, each piece the chain above at its own output size.  Pillow's semantics, per canvas:
+#     canvas = Image.new("RGB", (out_w, out_h), fill)
+#     for (src, crop, flip, jitter, dest) in pieces:  canvas.paste(chain(images[src], crop, jitter, (dw, dh), flip), (dx, dy))
+MAX_PIECES = 16        # csrc/preproc.hip PP_MAXP: pieces per canvas
+
+
+def _taps(crop, dest):
+    return -(-int(crop) // int(dest)) * 2 + 1
+
+
+def _check_fill(fill, N):
+    """the fill as (uint8 [3] or [N, 3], per-canvas flag)"""
+    f = np.asarray(fill)
+    if f.dtype.kind not in "iuf" or f.shape not in ((3,), (N, 3)) or not np.isfinite(f).all() or (f != np.floor(f)).any() \
+            or (f < 0).any() or (f > 255).any():
+        raise ValueError(f"fill: expected (r, g, b) integers in 0..255, or one such triple per canvas ({N}), got {fill!r}")
+    return np.ascontiguousarray(f.astype(np.uint8)), f.ndim == 2
+
+
+def _check_pieces(shapes, pieces, out_h, out_w):
+    """the plan as (int32 [P, 10] rows (src, l, t, cw, ch, flip, dx, dy, dw, dh), int32 [N + 1] offsets, float32 [P, 3] or None);
+    ValueError for anything the kernels must not see"""
+    S = len(shapes)
+    rows, jit, offs, any_jitter = [], [], [0], False
+    for n, canvas in enumerate(pieces):
+        canvas = list(canvas)
+        if len(canvas) > MAX_PIECES:
+            raise ValueError(f"canvas {n}: {len(canvas)} pieces, at most {MAX_PIECES}")
+        rects = []
+        for i, piece in enumerate(canvas):
+            where = f"canvas {n}, piece {i}"
+            try:
+                src, crop, flip, jitter, dest = piece
+                vals = [src] + list(crop) + list(dest)
+                if len(crop) != 4 or len(dest) != 4 or any(int(v) != v for v in vals):
+                    raise TypeError
+                src, (l, t, cw, ch), (dx, dy, dw, dh) = int(src), (int(v) for v in crop), (int(v) for v in dest)
+            except (TypeError, ValueError):
+                raise ValueError(f"{where}: expected (src, (left, top, width, height), flip, jitter or None, (dx, dy, dw, dh)) with integer "
+                                 f"boxes, got {piece!r}") from None
+            if not 0 <= src < S:
+                raise ValueError(f"{where}: source index {src} is not in 0..{S - 1}")
+            H, W = shapes[src]
+            if cw < 1 or ch < 1 or l < 0 or t < 0 or l + cw > W or t + ch > H:
+                raise ValueError(f"{where}: crop (left {l}, top {t}, width {cw}, height {ch}) is empty or not inside its {H}x{W} image")
+            if dw < 1 or dh < 1 or dx < 0 or dy < 0 or dx + dw > out_w or dy + dh > out_h:
+                raise ValueError(f"{where}: dest rect (x {dx}, y {dy}, width {dw}, height {dh}) is empty or not inside the {out_h}x{out_w} canvas")
+            k = max(_taps(cw, dw), _taps(ch, dh))
+            if k > MAX_TAPS:
+                raise ValueError(f"{where}: the {ch}x{cw} crop is more than 15x its {dh}x{dw} dest rect: the filter would need {k} taps "
+                                 f"(> {MAX_TAPS})")
+            if jitter is None:
+                fs = (1.0, 1.0, 1.0)
+            else:
+                fs = np.asarray(jitter, dtype=np.float32)
+                if fs.shape != (3,) or not np.isfinite(fs).all() or (fs < 0).any():
+                    raise ValueError(f"{where}: jitter: expected three finite factors >= 0 (brightness, contrast, saturation) or None, "
+                                     f"got {jitter!r}")
+                any_jitter = True
+            for j, (ox, oy, ow, oh) in enumerate(rects):
+                if dx < ox + ow and ox < dx + dw and dy < oy + oh and oy < dy + dh:
+                    raise ValueError(f"{where}: its dest rect overlaps piece {j}'s: the pieces of a canvas must be disjoint")
+            rects.append((dx, dy, dw, dh))
+            rows.append((src, l, t, cw, ch, 1 if flip else 0, dx, dy, dw, dh))
+            jit.append(fs)
+        offs.append(len(rows))
+    if not rows:
+        raise ValueError("no canvas has a piece: nothing to compose")
+    jitter = np.asarray(jit, dtype=np.float32).reshape(-1, 3) if any_jitter else None
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 10), np.asarray(offs, dtype=np.int32), jitter
+
+
+def compose_targets(targets, shapes, pieces, size, min_visibility=0.0):
+    """the target dicts of composed canvases, on the host in float32: one dict per canvas.  Per piece (src, crop, flip, _, dest) the
+    boxes of targets[src] go through `transform_targets`' steps relative to the crop -- corners in crop pixels clamped to the crop,
+    the same keep rule (0.001 of the crop, min_visibility of the box's area), mirrored if flipped -- and are then mapped into the
+    canvas, x = dx + x_crop * dw / cw and y = dy + y_crop * dh / ch, and normalised by the canvas (cxcywh).  A canvas's boxes and
+    labels are the concatenation over its pieces in piece order.  `size` becomes the canvas size; every other key is taken from the
+    target of the canvas's FIRST piece (image_id, orig_size ... then name that source only: a canvas mixes several).  A canvas without
+    pieces gives empty [0, 4] boxes and [0] int64 labels."""
+    out_h, out_w = _pre._out_size(size)
+    new = []
+    for canvas in pieces:
+        canvas = list(canvas)
+        if not canvas:
+            new.append({"boxes": torch.zeros((0, 4), dtype=torch.float32), "labels": torch.zeros((0,), dtype=torch.int64),
+                        "size": torch.as_tensor([out_h, out_w])})
+            continue
+        first = targets[int(canvas[0][0])]
+        nt = dict(first)
+        if "size" in nt:
+            nt["size"] = torch.as_tensor([out_h, out_w]).to(torch.as_tensor(first["size"]))
+        boxes, labels = [], []
+        for src, (l, t, cw, ch), fl, _, (dx, dy, dw, dh) in canvas:
+            tg = targets[int(src)]
+            if "boxes" not in tg:
+                continue
+            H, W = shapes[int(src)]
+            bx = tg["boxes"].detach().to("cpu", torch.float32).reshape(-1, 4)
+            cx, cy, bw, bh = bx.unbind(1)
+            x1 = ((cx - 0.5 * bw) * W - l).clamp(0, cw)
+            x2 = ((cx + 0.5 * bw) * W - l).clamp(0, cw)
+            y1 = ((cy - 0.5 * bh) * H - t).clamp(0, ch)
+            y2 = ((cy + 0.5 * bh) * H - t).clamp(0, ch)
+            keep = (x2 > x1) & (y2 > y1) & ((x2 - x1) / cw >= MIN_BOX) & ((y2 - y1) / ch >= MIN_BOX) \
+                & ((x2 - x1) * (y2 - y1) >= min_visibility * ((bw * W) * (bh * H)))
+            if fl:
+                x1, x2 = cw - x2, cw - x1
+            x1, x2, y1, y2 = dx + x1 * dw / cw, dx + x2 * dw / cw, dy + y1 * dh / ch, dy + y2 * dh / ch
+            boxes.append(torch.stack([(x1 + x2) / (2 * out_w), (y1 + y2) / (2 * out_h), (x2 - x1) / out_w, (y2 - y1) / out_h], dim=1)[keep])
+            if "labels" in tg:
+                labels.append(tg["labels"][keep.to(tg["labels"].device)])
+        if "boxes" in first:
+            nt["boxes"] = torch.cat(boxes).to(first["boxes"].device)
+        if "labels" in first:
+            nt["labels"] = torch.cat([lb.to(first["labels"].device) for lb in labels]) if labels else first["labels"][:0]
+        new.append(nt)
+    return new
+
+
+def _launch_compose(src, src_offs, hs, ws, rows, offs, jitter, fill, per_canvas, out_h, out_w, as_uint8, out=None):
+    """`dod_preprocess_compose*` on staged sources: src on the device, the rest host arrays as `_check_pieces` / `_check_fill` return
+    them.  Nothing is validated here (the tests hand the kernels plans that the host would refuse); out: None or the buffer to write."""
+    dev = src.device
+    S, P, N = len(hs), len(rows), len(offs) - 1
+    cw, ch, dw = (rows[:, k].astype(np.int64) for k in (3, 4, 8))
+    # per piece: the horizontal pass's rows and, with jitter, the jittered crop behind them
+    tsz = np.maximum(ch, 0) * (np.maximum(dw, 0) + (np.maximum(cw, 0) if jitter is not None else 0)) * 3
+    tmp_offs = np.concatenate([[0], np.cumsum(tsz)[:-1]]).astype(np.int64)
+    meta = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (src_offs, hs, ws, rows, offs, tmp_offs, fill)]
+    jit = torch.from_numpy(jitter).to(dev) if jitter is not None else None
+    lsum = torch.empty(P, dtype=torch.int64, device=dev) if jitter is not None and (jitter[:, 1] != 1.0).any() else None
+    tmp = torch.empty(max(1, int(tsz.sum())), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty((N, out_h, out_w, 3), dtype=torch.uint8, device=dev) if as_uint8 \
+            else torch.empty((N, 3, out_h, out_w), dtype=torch.float32, device=dev)
+    fn = nat.lib().dod_preprocess_compose_u8 if as_uint8 else nat.lib().dod_preprocess_compose
+    nat.check(fn(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), S, nat.ptr(meta[3]), nat.ptr(meta[4]), N, P, nat.ptr(jit),
+                 nat.ptr(lsum), nat.ptr(meta[6]), int(per_canvas), int(ch.max()), int(cw.max()), int(dw.max()), out_h, out_w, nat.ptr(tmp),
+                 nat.ptr(meta[5]), nat.ptr(out), nat.stream_ptr()))
+    return out
+
+
+def compose_batch(images, targets, pieces, size, fill=(124, 116, 104), device="cuda", as_uint8=False, min_visibility=0.0):
+    """images: the sources, as `preprocess_batch` takes them; targets: one target dict per source, or None; pieces: per canvas a list
+    of (src, crop, flip, jitter, dest): the source index, the crop (left, top, width, height) inside that source, the flip flag, None
+    or the three jitter factors, and the dest rect (dx, dy, dw, dh) inside the canvas the piece is resized into.  The dest rects of a
+    canvas are pairwise disjoint; a canvas holds at most 16 pieces (none: it is all fill) and some canvas must hold one; a piece may be
+    down-scaled by at most 15x in each direction (32 filter taps).  The contrast mean is that of the piece's crop, the flip mirrors
+    inside the dest rect, and pieces may share a source.  fill: (r, g, b) bytes, or one triple per canvas.  Returns (batch,
+    new_targets): float32 [N, 3, height, width] on `device`, or with as_uint8 the uint8 [N, height, width, 3] bytes for
+    `model.forward_packed_u8`; the targets as `compose_targets` documents them.  Only the sources some piece names are staged, each
+    once.  Anything wrong with the arguments raises ValueError before anything is copied or launched."""
+    out_h, out_w = _pre._out_size(size)
+    arrs = _pre._as_arrays(images)
+    shapes = [a.shape[:2] for a in arrs]
+    pieces = [list(c) for c in pieces]
+    rows, offs, jitter = _check_pieces(shapes, pieces, out_h, out_w)
+    fill, per_canvas = _check_fill(fill, len(pieces))
+    if targets is not None and len(targets) != len(arrs):
+        raise ValueError(f"targets: expected {len(arrs)} dicts (one per source), got {len(targets)}")
+    if jitter is not None and (jitter == 1.0).all():
+        jitter = None                                   # the geometric-only kernels
+    used = np.unique(rows[:, 0])
+    remap = np.full(len(arrs), -1, dtype=np.int32)
+    remap[used] = np.arange(len(used), dtype=np.int32)
+    staged = rows.copy()
+    staged[:, 0] = remap[rows[:, 0]]
+    src, src_offs, hs, ws = _pre._stage([arrs[i] for i in used], torch.device(device))
+    out = _launch_compose(src, src_offs, hs, ws, staged, offs, jitter, fill, per_canvas, out_h, out_w, as_uint8)
+    new_targets = compose_targets(targets, shapes, pieces, (out_h, out_w), min_visibility) if targets is not None else None
+    return out, new_targets
+
+
 def _uniform_int(u, lo, hi):
     """u in [0, 1) -> an integer uniform in [lo, hi]"""
     return min(hi, lo + int(u * (hi - lo + 1)))
+
+
+def _check_sampler(crop_frac, brightness, contrast, saturation):
+    f_lo, f_hi = float(crop_frac[0]), float(crop_frac[1])
+    if not (0.0 < f_lo <= f_hi <= 1.0):
+        raise ValueError(f"crop_frac: expected 0 < lo <= hi <= 1, got {crop_frac}")
+    for name, x in (("brightness", brightness), ("contrast", contrast), ("saturation", saturation)):
+        if not (math.isfinite(x) and x >= 0):
+            raise ValueError(f"{name}: expected a finite range >= 0, got {x}")
+    return f_lo, f_hi
+
+
+def _draw_one(u, H, W, crop_prob, f_lo, f_hi, hflip_prob, ranges):
+    """one image's (crop (l, t, w, h), flip, three float32 factors) from its nine uniform numbers u"""
+    H, W = int(H), int(W)
+    w, h, l, t = W, H, 0, 0
+    if u[0] < crop_prob:
+        w_lo, h_lo = max(1, math.ceil(f_lo * W)), max(1, math.ceil(f_lo * H))
+        w = _uniform_int(u[1], w_lo, max(w_lo, math.floor(f_hi * W)))
+        h = _uniform_int(u[2], h_lo, max(h_lo, math.floor(f_hi * H)))
+        l, t = _uniform_int(u[3], 0, W - w), _uniform_int(u[4], 0, H - h)
+    fs = []
+    for k, x in enumerate(ranges):
+        lo, hi = max(0.0, 1.0 - x), 1.0 + x
+        f = np.float32(lo + u[6 + k] * (hi - lo))
+        if float(f) > hi:                     # float32 rounding must not leave the range
+            f = np.nextafter(f, np.float32(0))
+        elif float(f) < lo:
+            f = np.nextafter(f, np.float32(2))
+        fs.append(f)
+    return (l, t, w, h), bool(u[5] < hflip_prob), fs
 
 
 def sample_params(shapes, generator, crop_prob=0.5, crop_frac=(0.5, 1.0), hflip_prob=0.5, brightness=0.0, contrast=0.0, saturation=0.0):
@@ -132,52 +343,136 @@ def sample_params(shapes, generator, crop_prob=0.5, crop_frac=(0.5, 1.0), hflip_
     convention; x = 0 gives exactly 1.0).  Returns (crops int32 [B, 4], flips uint8 [B], jitter float32 [B, 3]); every call draws
     the same nine numbers per image, so the same seed and shapes give the same parameters whatever the outcomes."""
     B = len(shapes)
-    f_lo, f_hi = float(crop_frac[0]), float(crop_frac[1])
-    if not (0.0 < f_lo <= f_hi <= 1.0):
-        raise ValueError(f"crop_frac: expected 0 < lo <= hi <= 1, got {crop_frac}")
-    for name, x in (("brightness", brightness), ("contrast", contrast), ("saturation", saturation)):
-        if not (math.isfinite(x) and x >= 0):
-            raise ValueError(f"{name}: expected a finite range >= 0, got {x}")
+    f_lo, f_hi = _check_sampler(crop_frac, brightness, contrast, saturation)
     u = torch.rand(B, 9, generator=generator, dtype=torch.float64).numpy()
     crops = np.zeros((B, 4), dtype=np.int32)
     flips = np.zeros(B, dtype=np.uint8)
     jitter = np.ones((B, 3), dtype=np.float32)
     for b, (H, W) in enumerate(shapes):
-        H, W = int(H), int(W)
-        w, h, l, t = W, H, 0, 0
-        if u[b, 0] < crop_prob:
-            w_lo, h_lo = max(1, math.ceil(f_lo * W)), max(1, math.ceil(f_lo * H))
-            w = _uniform_int(u[b, 1], w_lo, max(w_lo, math.floor(f_hi * W)))
-            h = _uniform_int(u[b, 2], h_lo, max(h_lo, math.floor(f_hi * H)))
-            l, t = _uniform_int(u[b, 3], 0, W - w), _uniform_int(u[b, 4], 0, H - h)
-        crops[b] = (l, t, w, h)
-        flips[b] = u[b, 5] < hflip_prob
-        for k, x in enumerate((brightness, contrast, saturation)):
-            lo, hi = max(0.0, 1.0 - x), 1.0 + x
-            f = np.float32(lo + u[b, 6 + k] * (hi - lo))
-            if float(f) > hi:                     # float32 rounding must not leave the range
-                f = np.nextafter(f, np.float32(0))
-            elif float(f) < lo:
-                f = np.nextafter(f, np.float32(2))
-            jitter[b, k] = f
+        crops[b], flips[b], jitter[b] = _draw_one(u[b], H, W, crop_prob, f_lo, f_hi, hflip_prob, (brightness, contrast, saturation))
     return crops, flips, jitter
+
+
+def _fit_taps(crop, dw, dh):
+    """the crop (l, t, w, h) shrunk, about its own centre, until a dw x dh dest rect needs at most 32 taps: a width above 15 dw
+    becomes 15 dw and the left edge moves right by half the difference (rounded down); likewise vertically.  Deterministic; a crop
+    within the bound comes back unchanged."""
+    l, t, w, h = crop
+    lim = (MAX_TAPS - 1) // 2
+    if w > lim * dw:
+        l, w = l + (w - lim * dw) // 2, lim * dw
+    if h > lim * dh:
+        t, h = t + (h - lim * dh) // 2, lim * dh
+    return l, t, w, h
+
+
+def _piece(src, u, shape, dest, crop_prob, f_lo, f_hi, hflip_prob, ranges):
+    crop, flip, fs = _draw_one(u, shape[0], shape[1], crop_prob, f_lo, f_hi, hflip_prob, ranges)
+    jitter = None if all(x == 0 for x in ranges) else tuple(float(f) for f in fs)
+    return src, _fit_taps(crop, dest[2], dest[3]), flip, jitter, dest
+
+
+def sample_mosaic(shapes, generator, size=(224, 224), center=(0.25, 0.75), crop_prob=0.5, crop_frac=(0.5, 1.0), hflip_prob=0.5,
+                  brightness=0.0, contrast=0.0, saturation=0.0):
+    """one four-piece mosaic per image of the batch, as `compose_batch` takes it: a list per canvas of (src, crop, flip, jitter,
+    dest).  Per canvas n of size (out_h, out_w): the centre cx is uniform over the integers of [c_lo out_w, c_hi out_w] clamped to
+    1 .. out_w - 1, cy likewise, so every quadrant is at least one pixel wide; the quadrants (top left, top right, bottom left,
+    bottom right) tile the canvas.  The top left one shows image n; the other three show partners drawn from the batch: without
+    replacement from the other images when the batch has at least four, else with replacement from all of it.  Every piece draws its
+    crop, flip and jitter by `sample_params`' rules on its own image; a crop that would need more than 32 filter taps for its
+    quadrant is shrunk about its centre to 15x the quadrant (`_fit_taps`), so every plan is valid.  41 numbers are drawn per canvas
+    whatever the outcomes: the same seed and shapes give the same plan."""
+    out_h, out_w = _pre._out_size(size)
+    B = len(shapes)
+    f_lo, f_hi = _check_sampler(crop_frac, brightness, contrast, saturation)
+    c_lo, c_hi = float(center[0]), float(center[1])
+    if not (0.0 <= c_lo <= c_hi <= 1.0):
+        raise ValueError(f"center: expected 0 <= lo <= hi <= 1, got {center}")
+    if out_h < 2 or out_w < 2:
+        raise ValueError(f"a mosaic needs a canvas of at least 2x2, got {out_h}x{out_w}")
+    ranges = (brightness, contrast, saturation)
+    u = torch.rand(B, 41, generator=generator, dtype=torch.float64).numpy()
+    plan = []
+    for n in range(B):
+        cs = []
+        for k, o in enumerate((out_w, out_h)):
+            lo = min(o - 1, max(1, math.ceil(c_lo * o)))
+            cs.append(_uniform_int(u[n, k], lo, min(o - 1, max(lo, math.floor(c_hi * o)))))
+        cx, cy = cs
+        if B >= 4:
+            pool = [i for i in range(B) if i != n]
+            partners = [pool.pop(_uniform_int(u[n, 2 + k], 0, len(pool) - 1)) for k in range(3)]
+        else:
+            partners = [_uniform_int(u[n, 2 + k], 0, B - 1) for k in range(3)]
+        dests = [(0, 0, cx, cy), (cx, 0, out_w - cx, cy), (0, cy, cx, out_h - cy), (cx, cy, out_w - cx, out_h - cy)]
+        plan.append([_piece(s, u[n, 5 + 9 * q:14 + 9 * q], shapes[s], dests[q], crop_prob, f_lo, f_hi, hflip_prob, ranges)
+                     for q, s in enumerate([n] + partners)])
+    return plan
+
+
+def sample_zoom_out(shapes, generator, size=(224, 224), ratio=(1.0, 2.0), crop_prob=0.5, crop_frac=(0.5, 1.0), hflip_prob=0.5,
+                    brightness=0.0, contrast=0.0, saturation=0.0):
+    """one zoom-out (SSD "expand") per image, as `compose_batch` takes it: canvas n holds one piece of image n, of size
+    round(out / r) (at least one pixel) with r uniform in [r_lo, r_hi] (1 <= r_lo), at an offset uniform over what fits; the rest of
+    the canvas is the fill.  Crop, flip and jitter by `sample_params`' rules, the crop shrunk by `_fit_taps` where the piece would
+    need more than 32 taps.  12 numbers per canvas."""
+    out_h, out_w = _pre._out_size(size)
+    f_lo, f_hi = _check_sampler(crop_frac, brightness, contrast, saturation)
+    r_lo, r_hi = float(ratio[0]), float(ratio[1])
+    if not (1.0 <= r_lo <= r_hi and math.isfinite(r_hi)):
+        raise ValueError(f"ratio: expected 1 <= lo <= hi, got {ratio}")
+    u = torch.rand(len(shapes), 12, generator=generator, dtype=torch.float64).numpy()
+    plan = []
+    for n, shape in enumerate(shapes):
+        r = r_lo + u[n, 0] * (r_hi - r_lo)
+        dw, dh = min(out_w, max(1, round(out_w / r))), min(out_h, max(1, round(out_h / r)))
+        dest = (_uniform_int(u[n, 1], 0, out_w - dw), _uniform_int(u[n, 2], 0, out_h - dh), dw, dh)
+        plan.append([_piece(n, u[n, 3:12], shape, dest, crop_prob, f_lo, f_hi, hflip_prob, (brightness, contrast, saturation))])
+    return plan
 
 
 class TrainAugment:
     """Training counterpart of `ResizeToTensor`: `TrainAugment((224, 224), brightness=0.4, ...)(images, targets)` draws one crop,
-    flip flag and jitter per image (`sample_params`) and returns `augment_batch`'s (batch, new_targets)."""
+    flip flag and jitter per image (`sample_params`) and returns `augment_batch`'s (batch, new_targets).
+
+    With mosaic_prob or zoom_out_prob above 0 every output image is a composed canvas: per canvas a mosaic (`sample_mosaic`) with
+    probability mosaic_prob, else a zoom-out (`sample_zoom_out`) with probability zoom_out_prob, else the plain chain as a single
+    piece covering the canvas; the whole batch is one `compose_batch` call on the `fill` colour.  With both at 0 the call is the
+    one above: the same random numbers, the same `augment_batch`."""
 
     def __init__(self, size=(224, 224), crop_prob=0.5, crop_frac=(0.5, 1.0), hflip_prob=0.5, brightness=0.0, contrast=0.0, saturation=0.0,
-                 generator=None, device="cuda", as_uint8=False, min_visibility=0.0):
+                 generator=None, device="cuda", as_uint8=False, min_visibility=0.0, mosaic_prob=0.0, mosaic_center=(0.25, 0.75),
+                 zoom_out_prob=0.0, zoom_out_ratio=(1.0, 2.0), fill=(124, 116, 104)):
         self.size, self.device, self.as_uint8, self.min_visibility = size, device, as_uint8, min_visibility
         self.sampler = dict(crop_prob=crop_prob, crop_frac=crop_frac, hflip_prob=hflip_prob, brightness=brightness, contrast=contrast,
                             saturation=saturation)
         self.generator = generator if generator is not None else torch.default_generator
+        for name, p in (("mosaic_prob", mosaic_prob), ("zoom_out_prob", zoom_out_prob)):
+            if not 0.0 <= p <= 1.0:
+                raise ValueError(f"{name}: expected a probability, got {p}")
+        self.mosaic_prob, self.mosaic_center, self.zoom_out_prob, self.zoom_out_ratio, self.fill = \
+            mosaic_prob, mosaic_center, zoom_out_prob, zoom_out_ratio, fill
+
+    def sample_plan(self, shapes):
+        """the pieces of one batch (`compose_batch`'s `pieces`): a fixed count of numbers per call, whichever kinds come out"""
+        B = len(shapes)
+        kind = torch.rand(B, 2, generator=self.generator, dtype=torch.float64).numpy()
+        mosaic = sample_mosaic(shapes, self.generator, self.size, self.mosaic_center, **self.sampler)
+        zoom = sample_zoom_out(shapes, self.generator, self.size, self.zoom_out_ratio, **self.sampler)
+        crops, flips, jitter = sample_params(shapes, self.generator, **self.sampler)
+        out_h, out_w = _pre._out_size(self.size)
+        # (a plain crop beyond 15x the canvas is shrunk like any other piece; `augment_batch` would refuse it)
+        plain = [[(n, _fit_taps(tuple(int(v) for v in crops[n]), out_w, out_h), bool(flips[n]), tuple(float(f) for f in jitter[n]),
+                   (0, 0, out_w, out_h))] for n in range(B)]
+        return [mosaic[n] if kind[n, 0] < self.mosaic_prob else zoom[n] if kind[n, 1] < self.zoom_out_prob else plain[n] for n in range(B)]
 
     def __call__(self, images, targets=None):
         arrs = _pre._as_arrays(images)
-        crops, flips, jitter = sample_params([a.shape[:2] for a in arrs], self.generator, **self.sampler)
-        return augment_batch(arrs, targets, crops, flips, jitter, self.size, self.device, self.as_uint8, self.min_visibility)
+        shapes = [a.shape[:2] for a in arrs]
+        if self.mosaic_prob == 0.0 and self.zoom_out_prob == 0.0:
+            crops, flips, jitter = sample_params(shapes, self.generator, **self.sampler)
+            return augment_batch(arrs, targets, crops, flips, jitter, self.size, self.device, self.as_uint8, self.min_visibility)
+        return compose_batch(arrs, targets, self.sample_plan(shapes), self.size, self.fill, self.device, self.as_uint8, self.min_visibility)
 
 
 def collate_raw(batch):

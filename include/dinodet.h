@@ -521,6 +521,40 @@ int dod_preprocess_aug_u8(const uint8_t* src, const int64_t* src_offs, const int
                           int max_crop_w, int out_h, int out_w, uint8_t* tmp, const int64_t* tmp_offs, uint8_t* out_hwc,
                           void* stream);
 
+/* Composed canvases (mosaic, zoom-out; Python mirror: dinov2_od_amd/augment.py compose_batch): N canvases of out_h x out_w, each a
+ * fill colour with disjoint rectangular pieces pasted into it, every piece the chain of dod_preprocess_aug at its own output size.
+ * Pillow-exact, per canvas n:
+ *   canvas = Image.new("RGB", (out_w, out_h), fill);   for each piece p of n:
+ *     im = source[p.src].crop(box) -> Brightness / Contrast / Color -> resize((dw, dh), BILINEAR) -> transpose(FLIP_LEFT_RIGHT) if flip
+ *     canvas.paste(im, (dx, dy))                        -> ToTensor
+ *   src, src_offs, heights, widths: S staged sources, as in dod_preprocess; several pieces may read one source.
+ *   pieces         int32 [P, 10]: (source index, crop left, top, width, height, flip, dest dx, dy, dw, dh), sorted by canvas.  The contrast
+ *                  mean is that of the piece's crop; the flip mirrors inside the dest rect.
+ *   piece_offsets  int32 [N + 1]: canvas n owns pieces piece_offsets[n] .. piece_offsets[n + 1] - 1, at most 16 of them (a canvas may
+ *                  own none: it is all fill); piece_offsets[N] = P.
+ *   jitter         float [P, 3] or NULL, lsum uint64 [P] or NULL: as in dod_preprocess_aug, per piece.
+ *   fills          uint8 [N, 3] when fill_per_canvas is non-zero, else uint8 [3]: the RGB fill colour.
+ *   max_crop_h / max_crop_w / max_dw (host): the largest crop height and width and the largest dest width; they bound the grids.
+ *   tmp            piece p at tmp + tmp_offs[p]: (crop height) * dw * 3 bytes when jitter is NULL, (crop height) * (dw + crop width) * 3
+ *                  bytes otherwise (the jittered crop behind the horizontal pass's rows).
+ * Every output byte of every canvas is written exactly once (one vertical + compose pass; no fill pre-pass, no atomics but the luma
+ * sums).  A piece is treated as absent -- its area takes the fill -- when its source index is not in [0, S), its crop is not inside
+ * its source, its dest rect is empty or not inside the canvas, it needs more than 32 filter taps (ceil(crop / dest) * 2 + 1) in
+ * either direction, it exceeds one of the three host bounds, or it is the 17th or later of its canvas: a caller's mistake does not
+ * fault.  The dest rects of one canvas must be pairwise disjoint (the caller checks): overlapping pieces give an unspecified but
+ * in-bounds result.  DOD_ERR_INVALID when a pointer is missing, N or P <= 0, or the largest crop would need more than 32 taps even
+ * for a piece as large as the canvas. */
+int dod_preprocess_compose(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int S,
+                           const int32_t* pieces, const int32_t* piece_offsets, int N, int P, const float* jitter, uint64_t* lsum,
+                           const uint8_t* fills, int fill_per_canvas, int max_crop_h, int max_crop_w, int max_dw, int out_h,
+                           int out_w, uint8_t* tmp, const int64_t* tmp_offs, float* out, void* stream);
+
+/* as dod_preprocess_compose, stopping before ToTensor: out_hwc = uint8 [N, out_h, out_w, 3], the input of dod_forward_u8 */
+int dod_preprocess_compose_u8(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int S,
+                              const int32_t* pieces, const int32_t* piece_offsets, int N, int P, const float* jitter, uint64_t* lsum,
+                              const uint8_t* fills, int fill_per_canvas, int max_crop_h, int max_crop_w, int max_dw, int out_h,
+                              int out_w, uint8_t* tmp, const int64_t* tmp_offs, uint8_t* out_hwc, void* stream);
+
 /* ---- Hungarian-matcher cost matrices on device -------------------------------------
  * Replaces the per-image cost computation of HungarianMatcher.forward, dino_detector/matching.py:79-98 (focal class
  * cost :80-86, L1 box cost :89, GIoU cost :92-95 with utils.py:124-164, weighted sum :98) for the whole batch.
@@ -917,7 +951,8 @@ const char* dod_version(void);
  * dod_op_linear_f32x3; the training entry points reading cfg->precision changes no signature either) and the train-time augmentation
  * (dod_preprocess_aug, dod_preprocess_aug_u8), the host-side dispatch query (dod_test_gemm_plan), the detection output (dod_detect*)
  * and the drawing entry (dod_draw_detections with its two new structs, which no earlier entry reads) and the merge of sliced
- * inference (dod_detect_views*) and its fusing form (dod_fuse_views*).
+ * inference (dod_detect_views*) and its fusing form (dod_fuse_views*) and the composed canvases (dod_preprocess_compose,
+ * dod_preprocess_compose_u8).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Device input pipeline (dod_preprocess) vs Pillow on the host: 64 COCO-sized images (480x640) -> 224^2 and 518^2.
 --augment: on the same images, the plain call against the augmented one (dod_preprocess_aug) with a crop + flip, with a crop +
-flip + all three jitters, and the same chain in Pillow on one host core; the device calls are timed interleaved in one process."""
+flip + all three jitters, and the same chain in Pillow on one host core; the device calls are timed interleaved in one process.
+--mosaic: 64 composed canvases from the same images (dod_preprocess_compose): mosaics of four with and without jitter, zoom-out,
+against dod_preprocess_aug writing as many output bytes and Pillow's paste chain on one host core; interleaved likewise."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -73,6 +75,85 @@ def augment_leg(R):
         print(f"  {n:40s} {med:7.1f} / {mn:7.1f}")
     print(f"  {'Pillow, crop + flip + 3 jitters, one core':40s} {t_cpu*1e3:7.0f} ms")
 
+
+def mosaic_leg(R):
+    """64 composed canvases from the 64 sources (dod_preprocess_compose): mosaic without jitter, mosaic with all three jitters, zoom-out;
+    against dod_preprocess_aug writing the same number of output bytes (64 images, crop + flip, without and with jitter) and
+    dod_preprocess on the full images; and the Pillow paste chain of the jittered mosaic on one host core"""
+    from dinov2_od_amd import augment as aug
+    L = nat.lib(); B = len(imgs)
+    shapes = [(480, 640)] * B
+    kw = dict(crop_prob=1.0, crop_frac=(0.5, 1.0), hflip_prob=0.5)
+    jkw = dict(brightness=0.4, contrast=0.4, saturation=0.4)
+    hs = np.full(B, 480, np.int32); ws = np.full(B, 640, np.int32)
+    so = (np.arange(B, dtype=np.int64) * 480 * 640 * 3)
+    src = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).cuda()
+    out = torch.empty(B, 3, R, R, device="cuda")
+    fill = torch.tensor([124, 116, 104], dtype=torch.uint8, device="cuda")
+    base = [torch.from_numpy(x).cuda() for x in (so, hs, ws)]
+    keep = []
+
+    def compose(plan):
+        rows, offs, jitter = aug._check_pieces(shapes, plan, R, R)
+        if jitter is not None and (jitter == 1.0).all():
+            jitter = None
+        cw, ch, dw = (rows[:, k].astype(np.int64) for k in (3, 4, 8))
+        sz = ch * (dw + (cw if jitter is not None else 0)) * 3
+        to = np.concatenate([[0], np.cumsum(sz)[:-1]]).astype(np.int64)
+        d = [torch.from_numpy(x).cuda() for x in (rows, offs, to)] + [torch.from_numpy(jitter).cuda() if jitter is not None else None,
+                                                                      torch.empty(len(rows), dtype=torch.int64, device="cuda") if jitter is not None else None,
+                                                                      torch.empty(int(sz.sum()), dtype=torch.uint8, device="cuda")]
+        keep.append(d)
+        frac = float((cw * ch).sum()) / (B * 480 * 640)
+        return frac, lambda: nat.check(L.dod_preprocess_compose(nat.ptr(src), nat.ptr(base[0]), nat.ptr(base[1]), nat.ptr(base[2]), B, nat.ptr(d[0]), nat.ptr(d[1]),
+                                                                B, len(rows), nat.ptr(d[3]), nat.ptr(d[4]), nat.ptr(fill), 0, int(ch.max()), int(cw.max()), int(dw.max()),
+                                                                R, R, nat.ptr(d[5]), nat.ptr(d[2]), nat.ptr(out), nat.stream_ptr()))
+
+    def single(c, f, j):
+        sz = c[:, 3].astype(np.int64) * (R + (c[:, 2].astype(np.int64) if j is not None else 0)) * 3
+        to = np.concatenate([[0], np.cumsum(sz)[:-1]]).astype(np.int64)
+        d = [torch.from_numpy(x).cuda() for x in (to, c, f)] + [torch.from_numpy(j).cuda() if j is not None else None,
+                                                                torch.empty(B, dtype=torch.int64, device="cuda") if j is not None else None,
+                                                                torch.empty(int(sz.sum()), dtype=torch.uint8, device="cuda")]
+        keep.append(d)
+        frac = float((c[:, 2].astype(np.int64) * c[:, 3]).sum()) / (B * 480 * 640)
+        return frac, lambda: nat.check(L.dod_preprocess_aug(nat.ptr(src), nat.ptr(base[0]), nat.ptr(base[1]), nat.ptr(base[2]), B, nat.ptr(d[1]), nat.ptr(d[2]), nat.ptr(d[3]),
+                                                            nat.ptr(d[4]), int(c[:, 3].max()), int(c[:, 2].max()), R, R, nat.ptr(d[5]), nat.ptr(d[0]), nat.ptr(out), nat.stream_ptr()))
+    gen = lambda: torch.Generator().manual_seed(0)
+    plan_j = aug.sample_mosaic(shapes, gen(), (R, R), **kw, **jkw)
+    crops, flips, jitter = aug.sample_params(shapes, gen(), **kw, **jkw)
+    full = np.array([(0, 0, 640, 480)] * B, np.int32)
+    legs = [("aug, full image, no flip, no jitter", single(full, np.zeros(B, np.uint8), None)),
+            ("aug, crop + flip", single(crops, flips, None)),
+            ("aug, crop + flip + 3 jitters", single(crops, flips, jitter)),
+            ("mosaic of 4, crop + flip", compose(aug.sample_mosaic(shapes, gen(), (R, R), **kw))),
+            ("mosaic of 4, crop + flip + 3 jitters", compose(plan_j)),
+            ("mosaic of 4 quarter-image crops + flip", compose(aug.sample_mosaic(shapes, gen(), (R, R), crop_prob=1.0, crop_frac=(0.5, 0.5), hflip_prob=0.5))),
+            ("mosaic of 4 full images, no flip", compose(aug.sample_mosaic(shapes, gen(), (R, R), crop_prob=0.0, hflip_prob=0.0))),
+            ("zoom-out 1..2, crop + flip", compose(aug.sample_zoom_out(shapes, gen(), (R, R), (1.0, 2.0), **kw))),
+            ("one full-canvas piece per canvas, crop + flip", compose([[(n, tuple(int(v) for v in crops[n]), bool(flips[n]), None, (0, 0, R, R))] for n in range(B)]))]
+    res = timed([run for _, (_, run) in legs])
+    t0 = time.perf_counter()
+    for canvas in plan_j:
+        cv = Image.new("RGB", (R, R), (124, 116, 104))
+        for s, (l, t, w, h), f, fs, (dx, dy, dw, dh) in canvas:
+            p = Image.fromarray(imgs[s]).crop((l, t, l + w, t + h))
+            for enh, x in zip((ImageEnhance.Brightness, ImageEnhance.Contrast, ImageEnhance.Color), fs):
+                p = enh(p).enhance(x)
+            p = p.resize((dw, dh), Image.BILINEAR)
+            cv.paste(p.transpose(Image.FLIP_LEFT_RIGHT) if f else p, (dx, dy))
+        np.transpose(np.array(cv), (2, 0, 1)).astype(np.float32) / 255
+    t_cpu = time.perf_counter() - t0
+    print(f"mosaic, 64 canvases from 64 x 480x640 -> {R}^2, median / min us over 20 interleaved rounds (source pixels read, in full images' worth of the 64):")
+    for (n, (frac, _)), (med, mn) in zip(legs, res):
+        print(f"  {n:48s} {med:7.1f} / {mn:7.1f}   ({frac:.2f})")
+    print(f"  {'Pillow paste chain, mosaic + 3 jitters, one core':48s} {t_cpu*1e3:7.0f} ms")
+
+
+if "--mosaic" in sys.argv:
+    for R in (224, 518):
+        mosaic_leg(R)
+    sys.exit(0)
 
 if "--augment" in sys.argv:
     for R in (224, 518):
