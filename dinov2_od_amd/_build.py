@@ -32,13 +32,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # per-source extra flags.  The flash attention kernels are built WITHOUT SLP vectorisation: hipcc packs adjacent fp32 adds / multiplies /
 # fmas of the softmax into v_pk_*_f32, and on gfx950 packed fp32 does not overlap an executing MFMA (it takes the sum of the two times,
 # tools/probes/mfma_valu_overlap.hip, profiles/r04_mfma_valu_overlap_probe.txt) while plain VALU does.
-# cocoeval.hip restates pycocotools' double arithmetic: `da + ga - i` must round twice, so no FMA contraction there.
-# detect.hip: every box / IoU operation of dod_detect is one fp32 rounding (`cx - 0.5 w` then `* width`, `iou * union`), likewise.
-# detect_views.hip: dod_detect's arithmetic again, plus the view mapping (`x * vw` then `+ vl`) and the edge test (`vl + m`).
-#   dod_fuse_views in the same file: `sum + s * x` is a rounded product, then a rounded sum, and `mean * T / N` rounds twice.
-# draw.hip: the same box conversion, and `x * 255 + 0.5` of the fp32 -> byte rule, round once per operation.
-EXTRA = {"attn_bf16.hip": ["-fno-slp-vectorize"], "attn_x3.hip": ["-fno-slp-vectorize"], "cocoeval.hip": ["-ffp-contract=off"], "detect.hip": ["-ffp-contract=off"],
-         "draw.hip": ["-ffp-contract=off"], "detect_views.hip": ["-ffp-contract=off"]}
+# (The files whose arithmetic must round once per operation say so themselves with `#pragma clang fp contract(off)`; no flag sets it.)
+EXTRA = {"attn_bf16.hip": ["-fno-slp-vectorize"], "attn_x3.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc():

@@ -54,6 +54,23 @@ def _check_params(shapes, crops, flips, jitter, out_h, out_w):
     return crops.astype(np.int32), flips, jitter
 
 
+def _boxes_in_crop(boxes, H, W, crop, flip, min_visibility):
+    """normalised cxcywh boxes of an [H, W] image under crop (left, top, width, height) and flip, on the host in float32 ->
+    (x1, y1, x2, y2, keep): the corners in crop pixels, clamped to the crop and mirrored if flipped, and the keep rule of
+    `transform_targets` (decided before the mirror, which changes none of its terms)"""
+    l, t, cw, ch = crop
+    cx, cy, bw, bh = boxes.detach().to("cpu", torch.float32).reshape(-1, 4).unbind(1)
+    x1 = ((cx - 0.5 * bw) * W - l).clamp(0, cw)
+    x2 = ((cx + 0.5 * bw) * W - l).clamp(0, cw)
+    y1 = ((cy - 0.5 * bh) * H - t).clamp(0, ch)
+    y2 = ((cy + 0.5 * bh) * H - t).clamp(0, ch)
+    keep = (x2 > x1) & (y2 > y1) & ((x2 - x1) / cw >= MIN_BOX) & ((y2 - y1) / ch >= MIN_BOX) \
+        & ((x2 - x1) * (y2 - y1) >= min_visibility * ((bw * W) * (bh * H)))
+    if flip:
+        x1, x2 = cw - x2, cw - x1
+    return x1, y1, x2, y2, keep
+
+
 def transform_targets(targets, shapes, crops, flips, size, min_visibility=0.0):
     """the reference's target dicts under the crops and flips, on the host in float32.  Per box of an image [H, W] and its crop
     (left, top, width, height): the corners in crop pixels, clamped to the crop; kept iff it is not empty, its clipped width /
@@ -68,16 +85,7 @@ def transform_targets(targets, shapes, crops, flips, size, min_visibility=0.0):
             nt["size"] = torch.as_tensor([out_h, out_w]).to(torch.as_tensor(tg["size"]))
         if "boxes" in nt and not (l == 0 and t == 0 and cw == W and ch == H and not fl):
             src = tg["boxes"]
-            bx = src.detach().to("cpu", torch.float32).reshape(-1, 4)
-            cx, cy, bw, bh = bx.unbind(1)
-            x1 = ((cx - 0.5 * bw) * W - l).clamp(0, cw)
-            x2 = ((cx + 0.5 * bw) * W - l).clamp(0, cw)
-            y1 = ((cy - 0.5 * bh) * H - t).clamp(0, ch)
-            y2 = ((cy + 0.5 * bh) * H - t).clamp(0, ch)
-            keep = (x2 > x1) & (y2 > y1) & ((x2 - x1) / cw >= MIN_BOX) & ((y2 - y1) / ch >= MIN_BOX) \
-                & ((x2 - x1) * (y2 - y1) >= min_visibility * ((bw * W) * (bh * H)))
-            if fl:
-                x1, x2 = cw - x2, cw - x1
+            x1, y1, x2, y2, keep = _boxes_in_crop(src, H, W, (l, t, cw, ch), fl, min_visibility)
             out = torch.stack([(x1 + x2) / (2 * cw), (y1 + y2) / (2 * ch), (x2 - x1) / cw, (y2 - y1) / ch], dim=1)[keep]
             nt["boxes"] = out.to(src.device)
             if "labels" in nt:
@@ -101,27 +109,31 @@ def augment_batch(images, targets, crops, flips, jitter=None, size=(224, 224), d
         raise ValueError(f"targets: expected {B} dicts, got {len(targets)}")
     if jitter is not None and (jitter == 1.0).all():
         jitter = None                                   # the geometric-only kernel
-    dev = torch.device(device)
-    src, src_offs, hs, ws = _pre._stage(arrs, dev)
-    # per image: the horizontal pass's rows and, with jitter, the jittered crop behind them
-    tsz = crops[:, 3].astype(np.int64) * (out_w + (crops[:, 2].astype(np.int64) if jitter is not None else 0)) * 3
-    tmp_offs = np.concatenate([[0], np.cumsum(tsz)[:-1]]).astype(np.int64)
-    meta = [torch.from_numpy(x).to(dev) for x in (src_offs, hs, ws, tmp_offs, crops, flips)]
+    src, src_offs, hs, ws = _pre._stage(arrs, torch.device(device))
+    out = _launch_aug(src, src_offs, hs, ws, crops, flips, jitter, out_h, out_w, as_uint8)
+    new_targets = transform_targets(targets, shapes, crops, flips, (out_h, out_w), min_visibility) if targets is not None else None
+    return out, new_targets
+
+
+def _launch_aug(src, src_offs, hs, ws, crops, flips, jitter, out_h, out_w, as_uint8, staged=None):
+    """`dod_preprocess_aug*` on staged sources: src on the device, the rest host arrays with one row per output image -- src_offs / hs /
+    ws name its source (outputs may share one), crops / flips / jitter are as `_check_params` returns them.  staged: the (crops, flips)
+    tensors of a caller that has them on the device already."""
+    dev = src.device
+    B = len(crops)
+    tmp_offs, tmp_bytes = _pre._tmp_layout(crops[:, 3], out_w, crops[:, 2] if jitter is not None else None)
+    meta = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (src_offs, hs, ws, tmp_offs)]
+    crops_t, flips_t = staged if staged is not None else (torch.from_numpy(crops).to(dev), torch.from_numpy(flips).to(dev))
     jit = torch.from_numpy(jitter).to(dev) if jitter is not None else None
     # the luma sums of the contrast step: only when some image has a contrast factor != 1 (the reduction is not launched otherwise)
     lsum = torch.empty(B, dtype=torch.int64, device=dev) if jitter is not None and (jitter[:, 1] != 1.0).any() else None
-    tmp = torch.empty(int(tsz.sum()), dtype=torch.uint8, device=dev)
-    if as_uint8:
-        out = torch.empty(B, out_h, out_w, 3, dtype=torch.uint8, device=dev)
-        fn = nat.lib().dod_preprocess_aug_u8
-    else:
-        out = torch.empty(B, 3, out_h, out_w, dtype=torch.float32, device=dev)
-        fn = nat.lib().dod_preprocess_aug
-    nat.check(fn(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), B, nat.ptr(meta[4]), nat.ptr(meta[5]), nat.ptr(jit),
+    tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
+    out = _pre._out_buffer(B, out_h, out_w, as_uint8, dev)
+    fn = nat.lib().dod_preprocess_aug_u8 if as_uint8 else nat.lib().dod_preprocess_aug
+    nat.check(fn(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), B, nat.ptr(crops_t), nat.ptr(flips_t), nat.ptr(jit),
                  nat.ptr(lsum), int(crops[:, 3].max()), int(crops[:, 2].max()), out_h, out_w, nat.ptr(tmp), nat.ptr(meta[3]), nat.ptr(out),
                  nat.stream_ptr()))
-    new_targets = transform_targets(targets, shapes, crops, flips, (out_h, out_w), min_visibility) if targets is not None else None
-    return out, new_targets
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------ composed canvases
@@ -224,16 +236,7 @@ def compose_targets(targets, shapes, pieces, size, min_visibility=0.0):
             if "boxes" not in tg:
                 continue
             H, W = shapes[int(src)]
-            bx = tg["boxes"].detach().to("cpu", torch.float32).reshape(-1, 4)
-            cx, cy, bw, bh = bx.unbind(1)
-            x1 = ((cx - 0.5 * bw) * W - l).clamp(0, cw)
-            x2 = ((cx + 0.5 * bw) * W - l).clamp(0, cw)
-            y1 = ((cy - 0.5 * bh) * H - t).clamp(0, ch)
-            y2 = ((cy + 0.5 * bh) * H - t).clamp(0, ch)
-            keep = (x2 > x1) & (y2 > y1) & ((x2 - x1) / cw >= MIN_BOX) & ((y2 - y1) / ch >= MIN_BOX) \
-                & ((x2 - x1) * (y2 - y1) >= min_visibility * ((bw * W) * (bh * H)))
-            if fl:
-                x1, x2 = cw - x2, cw - x1
+            x1, y1, x2, y2, keep = _boxes_in_crop(tg["boxes"], H, W, (l, t, cw, ch), fl, min_visibility)
             x1, x2, y1, y2 = dx + x1 * dw / cw, dx + x2 * dw / cw, dy + y1 * dh / ch, dy + y2 * dh / ch
             boxes.append(torch.stack([(x1 + x2) / (2 * out_w), (y1 + y2) / (2 * out_h), (x2 - x1) / out_w, (y2 - y1) / out_h], dim=1)[keep])
             if "labels" in tg:
@@ -252,16 +255,13 @@ def _launch_compose(src, src_offs, hs, ws, rows, offs, jitter, fill, per_canvas,
     dev = src.device
     S, P, N = len(hs), len(rows), len(offs) - 1
     cw, ch, dw = (rows[:, k].astype(np.int64) for k in (3, 4, 8))
-    # per piece: the horizontal pass's rows and, with jitter, the jittered crop behind them
-    tsz = np.maximum(ch, 0) * (np.maximum(dw, 0) + (np.maximum(cw, 0) if jitter is not None else 0)) * 3
-    tmp_offs = np.concatenate([[0], np.cumsum(tsz)[:-1]]).astype(np.int64)
+    tmp_offs, tmp_bytes = _pre._tmp_layout(np.maximum(ch, 0), np.maximum(dw, 0), np.maximum(cw, 0) if jitter is not None else None)
     meta = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (src_offs, hs, ws, rows, offs, tmp_offs, fill)]
     jit = torch.from_numpy(jitter).to(dev) if jitter is not None else None
     lsum = torch.empty(P, dtype=torch.int64, device=dev) if jitter is not None and (jitter[:, 1] != 1.0).any() else None
-    tmp = torch.empty(max(1, int(tsz.sum())), dtype=torch.uint8, device=dev)
+    tmp = torch.empty(max(1, tmp_bytes), dtype=torch.uint8, device=dev)
     if out is None:
-        out = torch.empty((N, out_h, out_w, 3), dtype=torch.uint8, device=dev) if as_uint8 \
-            else torch.empty((N, 3, out_h, out_w), dtype=torch.float32, device=dev)
+        out = _pre._out_buffer(N, out_h, out_w, as_uint8, dev)
     fn = nat.lib().dod_preprocess_compose_u8 if as_uint8 else nat.lib().dod_preprocess_compose
     nat.check(fn(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), S, nat.ptr(meta[3]), nat.ptr(meta[4]), N, P, nat.ptr(jit),
                  nat.ptr(lsum), nat.ptr(meta[6]), int(per_canvas), int(ch.max()), int(cw.max()), int(dw.max()), out_h, out_w, nat.ptr(tmp),

@@ -1,6 +1,6 @@
 // COCO bbox evaluation on device: pycocotools' COCOeval (iouType 'bbox', useCats = 1, default parameters) restated operation
 // for operation, from the records dod_postprocess compacts to the 12 summary numbers.  All evaluation arithmetic is double and
-// this file is built with -ffp-contract=off (dinov2_od_amd/_build.py), so `da + ga - i` rounds twice as maskApi.c's does and
+// no multiply-add is contracted anywhere in this file (the pragma below), so `da + ga - i` rounds twice as maskApi.c's does and
 // every count, quotient and comparison equals the host library's.  DESIGN.md section 6b states the algorithm.
 //
 //   sort      stable LSD radix sort of (64-bit key, 32-bit payload) pairs, 8-bit digits: histogram -> scan -> scatter.  One wave
@@ -16,6 +16,7 @@
 //             maxDet, threshold) runs the integer cumulative sums forward (searchsorted positions) and backward (running maximum).
 //   summarize one workgroup per statistic, a fixed-order tree sum.
 // No atomics on results, no float atomics anywhere: two evaluations of the same input are bit-identical.
+#pragma clang fp contract(off)
 #include "dod_internal.h"
 
 using namespace dod;
@@ -57,12 +58,10 @@ struct Lay {
   int nb;
 };
 
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 Lay layout(i64 cap, int I, int K, i64 G) {
   Lay L;
   size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes ? bytes : 1); return at; };
+  auto take = [&](size_t bytes) { const size_t at = o; o += align_up(bytes ? bytes : 1); return at; };
   const size_t c = (size_t)cap, g = (size_t)(G > 0 ? G : 1);
   L.nb = (int)((c + kTile - 1) / kTile);
   L.hdr = take(sizeof(Hdr));
@@ -502,7 +501,7 @@ extern "C" {
 
 size_t dod_op_sort_pairs_workspace_bytes(int64_t n) {
   if (n <= 0 || n > kMaxDets) return 0;
-  return al((size_t)((n + kTile - 1) / kTile) * 256 * 4);
+  return align_up((size_t)((n + kTile - 1) / kTile) * 256 * 4);
 }
 
 int dod_op_sort_pairs_u64(uint64_t* keys, uint32_t* vals, uint64_t* keys_alt, uint32_t* vals_alt, int64_t n, int begin_bit, int end_bit,

@@ -17,15 +17,15 @@
 //   4. thread t turns word t into score / label / query / box; without NMS it stores row t.
 //   5. NMS: a bit-matrix of the K x K suppression relation in LDS, upper-triangular (one ballot per 64 pairs), a serial sweep by one
 //      wave that carries the removed set as one 64-bit word per lane, and an ordered compaction by population count.
-// The box and IoU arithmetic must round once per operation: this file is compiled with -ffp-contract=off (_build.EXTRA).
-#include "detect_select.h"       // stages 1 - 3 and 5 and the key / word helpers, shared with detect_views.hip
+// The box and IoU arithmetic must round once per operation: detect_select.h turns fp contraction off for the whole file.
+#include "detect_select.h"       // stages 1 - 3 and 5, the output tail and the key / word helpers, shared with detect_views.hip
 #include "../../include/dinodet.h"
 
 #define DET_NMS_MAX_K 512        // dod_detect's documented limit with NMS
 
 struct DetArgs {
   const float* det; const float* sizes; unsigned* keys;
-  float* scores; int* labels; int* queries; float* boxes; int* counts;
+  DetOut out;                    // views and members null
   int Q, C, first_class, K;
   float threshold, iou;
   int agnostic, clamp;
@@ -34,11 +34,6 @@ struct DetArgs {
 __device__ __forceinline__ float det_logit(const DetArgs& a, const float* dp, int i) {
   const int q = i / a.C, c = i - q * a.C;
   return dp[(size_t)q * (a.C + 4) + c];
-}
-__device__ __forceinline__ unsigned det_make_key(const DetArgs& a, int i, float x) {
-  const int c = i % a.C;
-  const bool cand = c >= a.first_class && x == x && (a.threshold < 0.0f || det_sigmoid(x) > a.threshold);
-  return cand ? det_key(x) : 0u;
 }
 
 template <bool NMS>
@@ -51,49 +46,29 @@ __global__ __launch_bounds__(DET_THREADS) void det_kernel(const DetArgs a) {
   unsigned* kp = a.keys + (size_t)b * N;
 
   // ---- 1 - 3: keys, radix select, gather and sort (detect_select.h)
-  const int n = det_select_sort(L, N, K, tid, kp, [&](int i) { return det_logit(a, dp, i); }, [&](int i, float x) { return det_make_key(a, i, x); });
+  const int n = det_select_sort(L, N, K, tid, kp, [&](int i) { return det_logit(a, dp, i); },
+                                [&](int i, float x) { return det_cand_key(i % C, x, a.first_class, a.threshold); });
   const unsigned long long* const sel = L.sel;
 
   // ---- 4: thread t decodes word t
-  float sc = 0.0f, x1 = 0.0f, y1 = 0.0f, x2 = 0.0f, y2 = 0.0f;
-  int lab = -1, qi = -1;
+  DetRow row = det_pad_row();
   if (tid < n) {
     const int idx = (int)(0xFFFFFu - (unsigned)((sel[tid] >> 4) & 0xFFFFFu));
-    qi = idx / C; lab = idx - qi * C;
-    const float* row = dp + (size_t)qi * (C + 4);
-    sc = det_sigmoid(row[lab]);
-    const float cx = row[C], cy = row[C + 1], w = row[C + 2], h = row[C + 3];
+    row.query = idx / C; row.label = idx - row.query * C;
+    const float* p = dp + (size_t)row.query * (C + 4);
+    row.score = det_sigmoid(p[row.label]);
+    const float cx = p[C], cy = p[C + 1], w = p[C + 2], h = p[C + 3];
     const float ih = a.sizes ? a.sizes[2 * b] : 1.0f, iw = a.sizes ? a.sizes[2 * b + 1] : 1.0f;
-    x1 = cx - 0.5f * w; y1 = cy - 0.5f * h; x2 = cx + 0.5f * w; y2 = cy + 0.5f * h;
+    float x1 = cx - 0.5f * w, y1 = cy - 0.5f * h, x2 = cx + 0.5f * w, y2 = cy + 0.5f * h;
     x1 *= iw; y1 *= ih; x2 *= iw; y2 *= ih;
     if (a.clamp) { x1 = det_clamp(x1, iw); y1 = det_clamp(y1, ih); x2 = det_clamp(x2, iw); y2 = det_clamp(y2, ih); }
+    row.box = make_float4(x1, y1, x2, y2);
   }
-  const size_t o = (size_t)b * K;
-  if constexpr (!NMS) {
-    if (tid < K) {
-      a.scores[o + tid] = sc; a.labels[o + tid] = lab; a.queries[o + tid] = qi;
-      reinterpret_cast<float4*>(a.boxes)[o + tid] = make_float4(x1, y1, x2, y2);
-    }
-    if (tid == 0) a.counts[b] = n;
-  } else {
-    // ---- 5: greedy NMS over the n sorted candidates (n <= DET_NMS_MAX_K: the host refuses a larger K), detect_select.h
-    __shared__ DetNmsLds<DET_NMS_MAX_K> S;
-    det_nms(S, n, tid, make_float4(x1, y1, x2, y2), lab, a.iou, a.agnostic != 0, false);
-    int rank;
-    const int total = det_nms_rank(S, n, tid, rank);
-    if (tid >= total && tid < K) {                             // padding rows
-      a.scores[o + tid] = 0.0f; a.labels[o + tid] = -1; a.queries[o + tid] = -1;
-      reinterpret_cast<float4*>(a.boxes)[o + tid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    if (tid < n && !((S.rem[tid >> 6] >> (tid & 63)) & 1ull)) { // a survivor moves to row rank <= tid, rank < total
-      a.scores[o + rank] = sc; a.labels[o + rank] = lab; a.queries[o + rank] = qi;
-      reinterpret_cast<float4*>(a.boxes)[o + rank] = make_float4(x1, y1, x2, y2);
-    }
-    if (tid == 0) a.counts[b] = total;
-  }
+  // ---- 5 and the rows: with NMS n <= DET_NMS_MAX_K (the host refuses a larger K), detect_select.h
+  DetOut out = a.out;
+  out.views = out.members = nullptr;                             // known here, not only to the host: their stores fold away
+  det_finish<NMS ? DET_NMS_MAX_K : 0>(out, b, K, n, tid, row, a.iou, a.agnostic != 0, false);
 }
-
-static inline size_t det_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static bool det_shape_ok(int B, int Q, int C, int K) {
   return B > 0 && Q > 0 && C >= 1 && K >= 1 && K <= DET_MAX_K && (long long)Q * C <= DET_MAX_PAIRS;
@@ -101,7 +76,7 @@ static bool det_shape_ok(int B, int Q, int C, int K) {
 
 extern "C" size_t dod_detect_workspace_bytes(int B, int Q, int C, int K) {
   if (!det_shape_ok(B, Q, C, K)) return 0;
-  return det_align((size_t)B * Q * C * sizeof(unsigned));
+  return dod::align_up((size_t)B * Q * C * sizeof(unsigned));
 }
 
 extern "C" int dod_detect(const float* det, int B, int Q, int C, int first_class, const float* sizes, float threshold, int K,
@@ -115,7 +90,7 @@ extern "C" int dod_detect(const float* det, int B, int Q, int C, int first_class
   if (!workspace || workspace_bytes < dod_detect_workspace_bytes(B, Q, C, K)) return DOD_ERR_INVALID;
   DetArgs a;
   a.det = det; a.sizes = sizes; a.keys = (unsigned*)workspace;
-  a.scores = scores; a.labels = labels; a.queries = queries; a.boxes = boxes; a.counts = counts;
+  a.out = DetOut{scores, labels, nullptr, queries, boxes, nullptr, counts};
   a.Q = Q; a.C = C; a.first_class = first_class; a.K = K;
   a.threshold = threshold; a.iou = iou_threshold;
   a.agnostic = class_agnostic; a.clamp = clamp;

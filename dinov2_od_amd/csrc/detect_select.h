@@ -1,9 +1,15 @@
 // What dod_detect (detect.hip) and dod_detect_views (detect_views.hip) share: the order-preserving key image of a logit, the 56-bit
 // select word, stages 1 - 3 of the one-workgroup-per-image design -- key pass, radix select of the K-th largest word, gather and
 // bitonic sort in LDS (det_sort_desc, which the fusing merge of detect_views.hip runs a second time over its fused scores) -- and
-// stage 5, greedy NMS through a bit matrix in LDS.  Both files are compiled with -ffp-contract=off (_build.EXTRA): the overlap
-// arithmetic of stage 5 rounds once per operation.
+// stage 5, greedy NMS through a bit matrix in LDS, and the output tail of every entry point: the row store, the padding row and
+// det_finish (rows as sorted, or NMS and ordered compaction).
 #pragma once
+// The rounding contract of every file that includes this header, set here and not in the build script: no multiply-add is contracted
+// from here to the end of the translation unit, so each fp32 operation rounds once.
+//   dod_detect: `cx - 0.5 w` then `* width`; stage 5's `iou * union`.
+//   dod_detect_views: the same, plus the view mapping (`x * vw` then `+ vl`) and the edge test (`vl + m`).
+//   dod_fuse_views: `sum + s * x` is a rounded product, then a rounded sum, and `mean * T / N` rounds twice.
+#pragma clang fp contract(off)
 #include "dod_common.h"
 
 #define DET_THREADS 1024
@@ -23,6 +29,11 @@ __device__ __forceinline__ unsigned det_key(float x) {
 }
 __device__ __forceinline__ unsigned long long det_word(unsigned key, int i) {
   return ((unsigned long long)key << 24) | ((unsigned long long)(0xFFFFFu - (unsigned)i) << 4);
+}
+// the key of logit x of class c, or 0 when the pair is no candidate: a class below first_class, a NaN, a score not above the threshold
+__device__ __forceinline__ unsigned det_cand_key(int c, float x, int first_class, float threshold) {
+  const bool cand = c >= first_class && x == x && (threshold < 0.0f || det_sigmoid(x) > threshold);
+  return cand ? det_key(x) : 0u;
 }
 // use(i, load(i)) for every i < N of this thread (i = tid, tid + 1024, ...), DET_UNROLL loads in flight before the first use: a pass is
 // a few dozen elements per thread, and one L2 round trip per element would be most of its time
@@ -241,4 +252,35 @@ __device__ __forceinline__ int det_nms_rank(const DetNmsLds<MAXK>& S, int n, int
     else if (w == (tid >> 6)) rank += __popcll(kept & ((1ull << (tid & 63)) - 1ull));
   }
   return total;
+}
+
+// ---- the output tail: where the rows of a call go ([B, K] each, boxes as float4 rows; views / members null in an entry point that has
+// none), one row, and the row every padding position gets
+struct DetOut { float* scores; int* labels; int* views; int* queries; float* boxes; int* members; int* counts; };
+struct DetRow { float score; int label, view, query; float4 box; int members; };
+__device__ __forceinline__ DetRow det_pad_row() { return DetRow{0.0f, -1, -1, -1, make_float4(0.0f, 0.0f, 0.0f, 0.0f), 0}; }
+__device__ __forceinline__ void det_store(const DetOut& out, const DetRow& row, size_t r) {
+  out.scores[r] = row.score; out.labels[r] = row.label; out.queries[r] = row.query;
+  reinterpret_cast<float4*>(out.boxes)[r] = row.box;
+  if (out.views) out.views[r] = row.view;
+  if (out.members) out.members[r] = row.members;
+}
+// By all DET_THREADS threads, behind stage 4: thread t < n holds sorted candidate t in `row`, thread t >= n the padding row.  NMSK == 0
+// writes the rows as they are and the count n.  Otherwise stage 5 (n <= K <= NMSK: the host picks the instance): greedy NMS, the
+// survivors compacted in order into rows 0 .. total - 1, padding behind them, the count total.
+template <int NMSK>
+__device__ __forceinline__ void det_finish(const DetOut& out, int b, int K, int n, int tid, const DetRow& row, float iou, bool agnostic, bool ios) {
+  const size_t o = (size_t)b * K;
+  if constexpr (NMSK == 0) {
+    if (tid < K) det_store(out, row, o + tid);
+    if (tid == 0) out.counts[b] = n;
+  } else {
+    __shared__ DetNmsLds<NMSK> S;
+    det_nms(S, n, tid, row.box, row.label, iou, agnostic, ios);
+    int rank;
+    const int total = det_nms_rank(S, n, tid, rank);
+    if (tid >= total && tid < K) det_store(out, det_pad_row(), o + tid);
+    if (tid < n && !((S.rem[tid >> 6] >> (tid & 63)) & 1ull)) det_store(out, row, o + rank);   // a survivor moves to row rank <= tid, rank < total
+    if (tid == 0) out.counts[b] = total;
+  }
 }

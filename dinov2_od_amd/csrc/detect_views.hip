@@ -13,7 +13,7 @@
 //      so 1024 rows take 68 KiB instead of 128 KiB, and with boxes, areas, labels, select words and histograms the kernel declares about
 //      109 KiB of the CU's 160 KiB of LDS.  K <= 512 runs an instance with an 18 KiB triangle.
 //   5'. dod_fuse_views (fv_kernel, below): weighted boxes fusion in the place of NMS, on the same stages 0 - 4 (dv_candidates).
-// The box, edge, overlap and fusion arithmetic must round once per operation: this file is compiled with -ffp-contract=off (_build.EXTRA).
+// The box, edge, overlap and fusion arithmetic must round once per operation: detect_select.h turns fp contraction off for the whole file.
 #include "detect_select.h"
 #include "../../include/dinodet.h"
 
@@ -22,7 +22,7 @@
 struct DvArgs {
   const float* det; const int* voffs; const int* rects; const unsigned char* flips; const float* sizes;
   unsigned* keys; unsigned char* cut;
-  float* scores; int* labels; int* views; int* queries; float* boxes; int* counts;
+  DetOut out;                    // members null in dod_detect_views
   int V, Q, C, first_class, K;
   float threshold, iou, margin;
   int metric, agnostic, clamp;
@@ -51,8 +51,8 @@ __device__ __forceinline__ bool dv_cut(const DvBox& b, const DvRect& r, float m,
   return (r.l > 0 && b.x1 < (float)r.l + m) || (right < iw && b.x2 > right - m) ||
          (r.t > 0 && b.y1 < (float)r.t + m) || (bottom < ih && b.y2 > bottom - m);
 }
-// what stages 0 - 4 leave in thread t: candidate t of the image's n sorted candidates (score 0, label / view / query -1, box 0 for t >= n)
-struct DvCand { float sc, x1, y1, x2, y2; int lab, vi, qi, n, v0, nv; float ih, iw; };
+// what stages 0 - 4 leave in thread t: candidate t of the image's n sorted candidates (the padding row for t >= n)
+struct DvCand { DetRow row; int n, v0, nv; float ih, iw; };
 
 // Stages 0 - 4 for image b by all DET_THREADS threads, shared by dv_kernel and fv_kernel; v0 / nv / ih / iw: the image's first view, view
 // count (0 when its offsets are out of range) and size.  Ends behind det_select_sort's last barrier: L.sel holds the sorted words.
@@ -85,24 +85,21 @@ __device__ __forceinline__ DvCand dv_candidates(DetSelectLds& L, const DvArgs& a
       const float x = dp[(size_t)r * (C + 4) + c];
       return (edge && cut[r]) ? __uint_as_float(0x7FC00000u) : x;
     },
-    [&](int i, float x) {
-      const int c = i % C;
-      const bool cand = c >= a.first_class && x == x && (a.threshold < 0.0f || det_sigmoid(x) > a.threshold);
-      return cand ? det_key(x) : 0u;
-    });
+    [&](int i, float x) { return det_cand_key(i % C, x, a.first_class, a.threshold); });
   const unsigned long long* const sel = L.sel;
 
   // ---- 4: thread t decodes word t
-  DvCand d{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1, -1, -1, n, v0, nv, ih, iw};
+  DvCand d{det_pad_row(), n, v0, nv, ih, iw};
   if (tid < n) {
+    DetRow& o = d.row;
     const int idx = (int)(0xFFFFFu - (unsigned)((sel[tid] >> 4) & 0xFFFFFu));
     const int r = idx / C;
-    d.lab = idx - r * C; d.vi = r / Q; d.qi = r - d.vi * Q;
-    const float* row = dp + (size_t)r * (C + 4);
-    d.sc = det_sigmoid(row[d.lab]);
-    const DvBox bx = dv_box(row + C, dv_rect(a, v0 + d.vi), a.flips[v0 + d.vi] != 0);
-    d.x1 = bx.x1; d.y1 = bx.y1; d.x2 = bx.x2; d.y2 = bx.y2;
-    if (a.clamp) { d.x1 = det_clamp(d.x1, iw); d.y1 = det_clamp(d.y1, ih); d.x2 = det_clamp(d.x2, iw); d.y2 = det_clamp(d.y2, ih); }
+    o.label = idx - r * C; o.view = r / Q; o.query = r - o.view * Q;
+    const float* p = dp + (size_t)r * (C + 4);
+    o.score = det_sigmoid(p[o.label]);
+    const DvBox bx = dv_box(p + C, dv_rect(a, v0 + o.view), a.flips[v0 + o.view] != 0);
+    o.box = make_float4(bx.x1, bx.y1, bx.x2, bx.y2);
+    if (a.clamp) o.box = make_float4(det_clamp(bx.x1, iw), det_clamp(bx.y1, ih), det_clamp(bx.x2, iw), det_clamp(bx.y2, ih));
   }
   return d;
 }
@@ -111,34 +108,12 @@ __device__ __forceinline__ DvCand dv_candidates(DetSelectLds& L, const DvArgs& a
 template <int NMSK>
 __global__ __launch_bounds__(DET_THREADS) void dv_kernel(const DvArgs a) {
   __shared__ DetSelectLds L;
-  const int tid = threadIdx.x;
-  const int b = blockIdx.x, K = a.K;
+  const int tid = threadIdx.x, b = blockIdx.x;
   const DvCand d = dv_candidates(L, a, b, tid);
-  const int n = d.n, lab = d.lab, vi = d.vi, qi = d.qi;
-  const float sc = d.sc, x1 = d.x1, y1 = d.y1, x2 = d.x2, y2 = d.y2;
-  const size_t o = (size_t)b * K;
-  if constexpr (NMSK == 0) {
-    if (tid < K) {
-      a.scores[o + tid] = sc; a.labels[o + tid] = lab; a.views[o + tid] = vi; a.queries[o + tid] = qi;
-      reinterpret_cast<float4*>(a.boxes)[o + tid] = make_float4(x1, y1, x2, y2);
-    }
-    if (tid == 0) a.counts[b] = n;
-  } else {
-    // ---- 5: greedy NMS over the n sorted candidates (n <= K <= NMSK: the host picks the instance), detect_select.h
-    __shared__ DetNmsLds<NMSK> S;
-    det_nms(S, n, tid, make_float4(x1, y1, x2, y2), lab, a.iou, a.agnostic != 0, a.metric != 0);
-    int rank;
-    const int total = det_nms_rank(S, n, tid, rank);
-    if (tid >= total && tid < K) {                             // padding rows
-      a.scores[o + tid] = 0.0f; a.labels[o + tid] = -1; a.views[o + tid] = -1; a.queries[o + tid] = -1;
-      reinterpret_cast<float4*>(a.boxes)[o + tid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    if (tid < n && !((S.rem[tid >> 6] >> (tid & 63)) & 1ull)) { // a survivor moves to row rank <= tid, rank < total
-      a.scores[o + rank] = sc; a.labels[o + rank] = lab; a.views[o + rank] = vi; a.queries[o + rank] = qi;
-      reinterpret_cast<float4*>(a.boxes)[o + rank] = make_float4(x1, y1, x2, y2);
-    }
-    if (tid == 0) a.counts[b] = total;
-  }
+  // ---- 5 and the rows (detect_select.h)
+  DetOut out = a.out;
+  out.members = nullptr;                                         // known here, not only to the host: the store folds away
+  det_finish<NMSK>(out, b, a.K, d.n, tid, d.row, a.iou, a.agnostic != 0, a.metric != 0);
 }
 
 // ---- weighted boxes fusion across the views (include/dinodet.h dod_fuse_views; tests/fuse_views_cases.py restates it) --------------
@@ -168,7 +143,7 @@ struct FvLds {
 
 __device__ __forceinline__ float fv_area(const float4& b) { return det_max(0.0f, b.z - b.x) * det_max(0.0f, b.w - b.y); }
 
-__global__ __launch_bounds__(DET_THREADS) void fv_kernel(const DvArgs a, int* members, int conf) {
+__global__ __launch_bounds__(DET_THREADS) void fv_kernel(const DvArgs a, int conf) {
   __shared__ DetSelectLds L;
   __shared__ FvLds F;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -176,8 +151,8 @@ __global__ __launch_bounds__(DET_THREADS) void fv_kernel(const DvArgs a, int* me
   const DvCand d = dv_candidates(L, a, b, tid);
   const int n = d.n;                                           // uniform: det_select_sort reads it from LDS behind a barrier
   if (tid < n) {
-    F.cbox[tid] = make_float4(d.x1, d.y1, d.x2, d.y2);
-    F.clab[tid] = d.lab; F.csc[tid] = d.sc; F.crow[tid] = d.vi * a.Q + d.qi;
+    F.cbox[tid] = d.row.box;
+    F.clab[tid] = d.row.label; F.csc[tid] = d.row.score; F.crow[tid] = d.row.view * a.Q + d.row.query;
   }
   __syncthreads();
 
@@ -233,7 +208,7 @@ __global__ __launch_bounds__(DET_THREADS) void fv_kernel(const DvArgs a, int* me
     }
     const int c = win ? (int)(0xFFFFFFFFu - (unsigned)win) : nc;
     if (tid == c) {
-      if (win) {                                               // each product rounds, then each sum (-ffp-contract=off)
+      if (win) {                                               // each product rounds, then each sum (fp contract off)
         sx1 = sx1 + s * cb.x; sy1 = sy1 + s * cb.y; sx2 = sx2 + s * cb.z; sy2 = sy2 + s * cb.w; ss = ss + s;
         kb = make_float4(sx1 / ss, sy1 / ss, sx2 / ss, sy2 / ss);
         if (a.clamp) { kb.x = det_clamp(kb.x, d.iw); kb.y = det_clamp(kb.y, d.ih); kb.z = det_clamp(kb.z, d.iw); kb.w = det_clamp(kb.w, d.ih); }
@@ -275,27 +250,42 @@ __global__ __launch_bounds__(DET_THREADS) void fv_kernel(const DvArgs a, int* me
   const size_t o = (size_t)b * K;
   if (tid < nc) {
     const int row = F.crow[F.kfirst[c]], vi = row / a.Q;
-    a.scores[o + tid] = F.kscore[c]; a.labels[o + tid] = F.klab[c]; a.views[o + tid] = vi; a.queries[o + tid] = row - vi * a.Q;
-    reinterpret_cast<float4*>(a.boxes)[o + tid] = F.kbox[c];
-    members[o + tid] = F.kcnt[c];
-  } else if (tid < K) {                                        // padding rows
-    a.scores[o + tid] = 0.0f; a.labels[o + tid] = -1; a.views[o + tid] = -1; a.queries[o + tid] = -1;
-    reinterpret_cast<float4*>(a.boxes)[o + tid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    members[o + tid] = 0;
+    det_store(a.out, DetRow{F.kscore[c], F.klab[c], vi, row - vi * a.Q, F.kbox[c], F.kcnt[c]}, o + tid);
+  } else if (tid < K) {
+    det_store(a.out, det_pad_row(), o + tid);
   }
-  if (tid == 0) a.counts[b] = nc;
+  if (tid == 0) a.out.counts[b] = nc;
 }
-
-static inline size_t dv_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static bool dv_shape_ok(int V, int Q, int C, int K) {
   return V >= 0 && Q > 0 && C >= 1 && K >= 1 && K <= DET_MAX_K && (long long)Q * C <= DET_MAX_PAIRS;
 }
-static size_t dv_keys_bytes(int V, int Q, int C) { return dv_align((size_t)V * Q * C * sizeof(unsigned) + 1); }
+static size_t dv_keys_bytes(int V, int Q, int C) { return dod::align_up((size_t)V * Q * C * sizeof(unsigned) + 1); }
 
 extern "C" size_t dod_detect_views_workspace_bytes(int V, int Q, int C, int K) {
   if (!dv_shape_ok(V, Q, C, K)) return 0;
-  return dv_keys_bytes(V, Q, C) + dv_align((size_t)V * Q + 1);   // keys, then one edge byte per row; never 0 inside the limits
+  return dv_keys_bytes(V, Q, C) + dod::align_up((size_t)V * Q + 1);   // keys, then one edge byte per row; never 0 inside the limits
+}
+extern "C" size_t dod_fuse_views_workspace_bytes(int V, int Q, int C, int K) { return dod_detect_views_workspace_bytes(V, Q, C, K); }
+
+// What dod_detect_views and dod_fuse_views check alike, and the DvArgs of both; false = DOD_ERR_INVALID.  `out` is complete: an entry
+// point checks its own arguments (nms_metric, conf, members) itself.
+static bool dv_prepare(DvArgs& a, const float* det, int B, int V, int Q, int C, const int32_t* view_offsets, const int32_t* view_rects,
+                       const uint8_t* view_flips, const float* sizes, int first_class, float threshold, int K, float iou_threshold,
+                       int nms_metric, int class_agnostic, int clamp, float edge_margin, const DetOut& out, void* workspace,
+                       size_t workspace_bytes) {
+  if (!view_offsets || !sizes || !out.scores || !out.labels || !out.views || !out.queries || !out.boxes || !out.counts) return false;
+  if (B < 1 || !dv_shape_ok(V, Q, C, K) || first_class < 0 || first_class >= C) return false;
+  if (V > 0 && (!det || !view_rects || !view_flips)) return false;
+  if (((uintptr_t)out.boxes & 15) != 0) return false;            // rows are stored as float4
+  if (!workspace || workspace_bytes < dod_detect_views_workspace_bytes(V, Q, C, K)) return false;
+  a.det = det; a.voffs = view_offsets; a.rects = view_rects; a.flips = view_flips; a.sizes = sizes;
+  a.keys = (unsigned*)workspace; a.cut = (unsigned char*)workspace + dv_keys_bytes(V, Q, C);
+  a.out = out;
+  a.V = V; a.Q = Q; a.C = C; a.first_class = first_class; a.K = K;
+  a.threshold = threshold; a.iou = iou_threshold; a.margin = edge_margin;
+  a.metric = nms_metric; a.agnostic = class_agnostic; a.clamp = clamp;
+  return true;
 }
 
 extern "C" int dod_detect_views(const float* det, int B, int V, int Q, int C, const int32_t* view_offsets, const int32_t* view_rects,
@@ -303,19 +293,11 @@ extern "C" int dod_detect_views(const float* det, int B, int V, int Q, int C, co
                                 float iou_threshold, int nms_metric, int class_agnostic, int clamp, float edge_margin, float* scores,
                                 int32_t* labels, int32_t* views, int32_t* queries, float* boxes, int32_t* counts, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-  if (!view_offsets || !sizes || !scores || !labels || !views || !queries || !boxes || !counts) return DOD_ERR_INVALID;
-  if (B < 1 || !dv_shape_ok(V, Q, C, K) || first_class < 0 || first_class >= C) return DOD_ERR_INVALID;
-  if (V > 0 && (!det || !view_rects || !view_flips)) return DOD_ERR_INVALID;
-  if (nms_metric != 0 && nms_metric != 1) return DOD_ERR_INVALID;
-  if (((uintptr_t)boxes & 15) != 0) return DOD_ERR_INVALID;      // rows are stored as float4
-  if (!workspace || workspace_bytes < dod_detect_views_workspace_bytes(V, Q, C, K)) return DOD_ERR_INVALID;
   DvArgs a;
-  a.det = det; a.voffs = view_offsets; a.rects = view_rects; a.flips = view_flips; a.sizes = sizes;
-  a.keys = (unsigned*)workspace; a.cut = (unsigned char*)workspace + dv_keys_bytes(V, Q, C);
-  a.scores = scores; a.labels = labels; a.views = views; a.queries = queries; a.boxes = boxes; a.counts = counts;
-  a.V = V; a.Q = Q; a.C = C; a.first_class = first_class; a.K = K;
-  a.threshold = threshold; a.iou = iou_threshold; a.margin = edge_margin;
-  a.metric = nms_metric; a.agnostic = class_agnostic; a.clamp = clamp;
+  if (nms_metric != 0 && nms_metric != 1) return DOD_ERR_INVALID;
+  if (!dv_prepare(a, det, B, V, Q, C, view_offsets, view_rects, view_flips, sizes, first_class, threshold, K, iou_threshold, nms_metric,
+                  class_agnostic, clamp, edge_margin, DetOut{scores, labels, views, queries, boxes, nullptr, counts}, workspace, workspace_bytes))
+    return DOD_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   if (!(iou_threshold >= 0.0f)) hipLaunchKernelGGL(dv_kernel<0>, dim3(B), dim3(DET_THREADS), 0, s, a);
   else if (K <= 512) hipLaunchKernelGGL(dv_kernel<512>, dim3(B), dim3(DET_THREADS), 0, s, a);
@@ -323,26 +305,17 @@ extern "C" int dod_detect_views(const float* det, int B, int V, int Q, int C, co
   return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
 }
 
-extern "C" size_t dod_fuse_views_workspace_bytes(int V, int Q, int C, int K) { return dod_detect_views_workspace_bytes(V, Q, C, K); }
-
 extern "C" int dod_fuse_views(const float* det, int B, int V, int Q, int C, const int32_t* view_offsets, const int32_t* view_rects,
                               const uint8_t* view_flips, const float* sizes, int first_class, float threshold, int K,
                               float iou_threshold, int class_agnostic, int clamp, float edge_margin, int conf, float* scores,
                               int32_t* labels, int32_t* views, int32_t* queries, float* boxes, int32_t* members, int32_t* counts,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  if (!view_offsets || !sizes || !scores || !labels || !views || !queries || !boxes || !members || !counts) return DOD_ERR_INVALID;
-  if (B < 1 || !dv_shape_ok(V, Q, C, K) || first_class < 0 || first_class >= C) return DOD_ERR_INVALID;
-  if (V > 0 && (!det || !view_rects || !view_flips)) return DOD_ERR_INVALID;
-  if (conf != 0 && conf != 1) return DOD_ERR_INVALID;
-  if (((uintptr_t)boxes & 15) != 0) return DOD_ERR_INVALID;      // rows are stored as float4
-  if (!workspace || workspace_bytes < dod_fuse_views_workspace_bytes(V, Q, C, K)) return DOD_ERR_INVALID;
   DvArgs a;
-  a.det = det; a.voffs = view_offsets; a.rects = view_rects; a.flips = view_flips; a.sizes = sizes;
-  a.keys = (unsigned*)workspace; a.cut = (unsigned char*)workspace + dv_keys_bytes(V, Q, C);
-  a.scores = scores; a.labels = labels; a.views = views; a.queries = queries; a.boxes = boxes; a.counts = counts;
-  a.V = V; a.Q = Q; a.C = C; a.first_class = first_class; a.K = K;
-  a.threshold = threshold; a.iou = iou_threshold; a.margin = edge_margin;
-  a.metric = 0; a.agnostic = class_agnostic; a.clamp = clamp;
-  hipLaunchKernelGGL(fv_kernel, dim3(B), dim3(DET_THREADS), 0, (hipStream_t)stream, a, members, conf);
+  if (!members || (conf != 0 && conf != 1)) return DOD_ERR_INVALID;
+  if (!dv_prepare(a, det, B, V, Q, C, view_offsets, view_rects, view_flips, sizes, first_class, threshold, K, iou_threshold, 0,
+                  class_agnostic, clamp, edge_margin, DetOut{scores, labels, views, queries, boxes, members, counts}, workspace, workspace_bytes))
+    return DOD_ERR_INVALID;
+  hipLaunchKernelGGL(fv_kernel, dim3(B), dim3(DET_THREADS), 0, (hipStream_t)stream, a, conf);
   return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
 }
+

@@ -14,6 +14,11 @@ typedef unsigned short bf16_t;   // storage type of bf16 in memory
 
 #define DOD_WAVE 64
 
+namespace dod {
+// the one rounding of every workspace carve: the parts of a workspace start 256 bytes apart
+inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+}
+
 // Tuning switches (tile overrides, A/B schedules, in-kernel time stamps, the register-only MFMA probes) exist only in -DDINODET_TUNING builds
 // (`python -m dinov2_od_amd._build --tuning` -> lib/libdinodet_tuning.so, which tools/ load through DINODET_LIB).  The release library reads
 // the few OPERATIONAL variables INTEGRATION.md lists and nothing else: no environment variable can change which kernel runs or what it computes.

@@ -122,7 +122,6 @@ inline bool is_h2(const dod_handle* h) { return h->cfg.precision == DOD_PREC_FP1
 // operand dtype of everything that is not an fp8 GEMM: bf16 in both the bf16 and the fp8 mode
 inline bool is_bf16(const dod_handle* h) { return h->cfg.precision == DOD_PREC_BF16 || is_fp8(h); }
 inline size_t esz(const dod_handle* h) { return is_x3(h) ? 6 : (is_bf16(h) ? 2 : 4); }   // x3: [hi | hi | lo] bf16 per element
-inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 // norm1 / norm2 can be folded into the QKV / MLP-in GEMMs (bf16 and the compensated modes; the strict fp32 and the fp8 schedule keep the
 // LayerNorm kernel).  The ONE predicate behind the workspace's statistics buffers, BLayer::fold and the forward's choice of schedule.
 inline bool ln_foldable(const dod_handle* h) { return !is_fp8(h) && (is_bf16(h) || is_x3(h)) && h->cfg.hidden % 32 == 0; }

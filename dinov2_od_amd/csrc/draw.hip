@@ -15,7 +15,9 @@
 //      table and the font from global memory.
 //   4. the painted rows go back through LDS and leave in aligned dword stores, first and last bytes of a row alone.
 // A tile no row touches has an empty list: steps 2 and 4 are then a straight copy or convert.
-// The box arithmetic must round once per operation: this file is compiled with -ffp-contract=off (_build.EXTRA).
+// The box conversion (dod_detect's) and `x * 255 + 0.5` of the fp32 -> byte rule must round once per operation: no multiply-add is
+// contracted anywhere in this file.
+#pragma clang fp contract(off)
 #include "dod_common.h"
 #include "../../include/dinodet.h"
 

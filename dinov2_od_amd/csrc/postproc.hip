@@ -82,13 +82,11 @@ __global__ __launch_bounds__(256) void pp_emit_kernel(const float* __restrict__ 
   }
 }
 
-static inline size_t pp_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" size_t dod_postprocess_workspace_bytes(int B, int Q, int C) {
   (void)Q;
   if (B <= 0 || C <= 1) return 0;
   const size_t runs = (size_t)B * (C - 1);
-  return pp_align(runs * sizeof(unsigned)) + pp_align(runs * sizeof(unsigned long long));
+  return dod::align_up(runs * sizeof(unsigned)) + dod::align_up(runs * sizeof(unsigned long long));
 }
 
 extern "C" int dod_postprocess(const float* det, int B, int Q, int C, const int64_t* image_ids, float threshold,
@@ -100,7 +98,7 @@ extern "C" int dod_postprocess(const float* det, int B, int Q, int C, const int6
   hipStream_t s = (hipStream_t)stream;
   const int runs = B * (C - 1);
   unsigned* counts = (unsigned*)workspace;
-  unsigned long long* offsets = (unsigned long long*)((char*)workspace + pp_align((size_t)runs * sizeof(unsigned)));
+  unsigned long long* offsets = (unsigned long long*)((char*)workspace + dod::align_up((size_t)runs * sizeof(unsigned)));
   const int blocks = (runs + 255) / 256;
   hipLaunchKernelGGL(pp_count_kernel, dim3(blocks), dim3(256), 0, s, det, B, Q, C, threshold, counts);
   hipLaunchKernelGGL(pp_scan_kernel, dim3(1), dim3(1024), 0, s, counts, runs, offsets, (long long*)count);

@@ -69,6 +69,40 @@ def _sizes_rows(sizes, B):
     return t
 
 
+def _check_det(det, num_classes, rows="B"):
+    """det [rows, Q, C+4] against num_classes -> (rows, Q, C).  The device is not looked at: the callers check it last, so that every
+    argument is checked whether or not a GPU is present"""
+    if not (isinstance(det, torch.Tensor) and det.dtype == torch.float32 and det.dim() == 3):
+        raise ValueError(f"det must be a CUDA fp32 tensor [{rows}, Q, C+4]")
+    n, Q, W = det.shape
+    Cn = int(num_classes)
+    if W != Cn + 4 or Cn < 1:
+        raise ValueError(f"det has {W} columns, expected num_classes + 4 = {Cn + 4}")
+    return n, Q, Cn
+
+
+def _check_top_k(Cn, top_k, nms_iou, skip_background, max_k_nms):
+    """-> (first_class, K, iou_threshold as the C entry points take it: -1 without NMS); max_k_nms: the entry point's K limit with NMS"""
+    first = 1 if skip_background else 0
+    if first >= Cn:
+        raise ValueError("skip_background leaves no class (num_classes == 1)")
+    nms = nms_iou is not None
+    if nms and not float(nms_iou) >= 0.0:
+        raise ValueError(f"nms_iou must be None or >= 0, got {nms_iou}")
+    K, kmax = int(top_k), max_k_nms if nms else MAX_TOP_K
+    if not 1 <= K <= kmax:
+        raise ValueError(f"top_k must be in 1..{kmax}{' with NMS' if kmax < MAX_TOP_K else ''}, got {K}")
+    return first, K, float(nms_iou) if nms else -1.0
+
+
+def _alloc(cls, B, K, dev, extra=0):
+    """cls(scores, labels, boxes, queries, counts, then `extra` more [B, K] int32 tensors) uninitialised on dev"""
+    def i32():
+        return torch.empty(B, K, dtype=torch.int32, device=dev)
+    return cls(torch.empty(B, K, dtype=torch.float32, device=dev), i32(), torch.empty(B, K, 4, dtype=torch.float32, device=dev), i32(),
+               torch.empty(B, dtype=torch.int32, device=dev), *(i32() for _ in range(extra)))
+
+
 def detect_packed(det, num_classes, sizes=None, top_k=100, threshold=-1.0, nms_iou=None, class_agnostic=False, clamp=True,
                   skip_background=True):
     """det: packed detections [B, Q, C+4] fp32 on the GPU.  Per image the `top_k` highest-logit (query, class) pairs -- of those with
@@ -77,23 +111,10 @@ def detect_packed(det, num_classes, sizes=None, top_k=100, threshold=-1.0, nms_i
     nms_iou (>= 0) greedy NMS, per class unless class_agnostic, removes later boxes whose IoU with a survivor exceeds it.
     Returns Detections(scores [B,K] f32, labels [B,K] i32, boxes [B,K,4] f32, queries [B,K] i32, counts [B] i32) of CUDA tensors; rows
     at and beyond counts[b] are padding (score 0, label -1, query -1, box 0).  One launch on the current stream, no host sync."""
-    if not (isinstance(det, torch.Tensor) and det.dtype == torch.float32 and det.dim() == 3):
-        raise ValueError("det must be a CUDA fp32 tensor [B, Q, C+4]")
-    B, Q, W = det.shape
-    Cn, K = int(num_classes), int(top_k)
-    if W != Cn + 4 or Cn < 1:
-        raise ValueError(f"det has {W} columns, expected num_classes + 4 = {Cn + 4}")
+    B, Q, Cn = _check_det(det, num_classes)
     if B < 1 or Q < 1 or Q * Cn > (1 << 20):
         raise ValueError(f"need at least one image and one query and at most 2^20 (query, class) pairs per image, got B={B} Q={Q} C={Cn}")
-    first = 1 if skip_background else 0
-    if first >= Cn:
-        raise ValueError("skip_background leaves no class (num_classes == 1)")
-    nms = nms_iou is not None
-    if nms and not float(nms_iou) >= 0.0:
-        raise ValueError(f"nms_iou must be None or >= 0, got {nms_iou}")
-    kmax = MAX_TOP_K_NMS if nms else MAX_TOP_K
-    if not 1 <= K <= kmax:
-        raise ValueError(f"top_k must be in 1..{kmax}{' with NMS' if nms else ''}, got {K}")
+    first, K, iou = _check_top_k(Cn, top_k, nms_iou, skip_background, MAX_TOP_K_NMS)
     st = _sizes_rows(sizes, B)
     if not det.is_cuda:                                       # last: every argument is checked whether or not a GPU is present
         raise ValueError("det must be a CUDA fp32 tensor [B, Q, C+4] (there is no CPU fallback)")
@@ -103,10 +124,8 @@ def detect_packed(det, num_classes, sizes=None, top_k=100, threshold=-1.0, nms_i
     if st is not None:
         st = st.to(device=dev, dtype=torch.float32).contiguous()
     ws = torch.empty(L.dod_detect_workspace_bytes(B, Q, Cn, K), dtype=torch.uint8, device=dev)
-    out = Detections(torch.empty(B, K, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
-                     torch.empty(B, K, 4, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
-                     torch.empty(B, dtype=torch.int32, device=dev))
-    nat.check(L.dod_detect(nat.ptr(det), B, Q, Cn, first, nat.ptr(st), float(threshold), K, float(nms_iou) if nms else -1.0,
+    out = _alloc(Detections, B, K, dev)
+    nat.check(L.dod_detect(nat.ptr(det), B, Q, Cn, first, nat.ptr(st), float(threshold), K, iou,
                            int(bool(class_agnostic)), int(bool(clamp)), nat.ptr(out.scores), nat.ptr(out.labels), nat.ptr(out.queries),
                            nat.ptr(out.boxes), nat.ptr(out.counts), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
     return out

@@ -61,6 +61,20 @@ def _out_size(size):
     return (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
 
 
+def _tmp_layout(rows, out_w, jitter_w=None):
+    """the temporary of the two-pass resize as (byte offsets int64 [n], total bytes): per output the horizontal pass's `rows` rows of
+    out_w RGB pixels and, with jitter, the jittered crop of jitter_w pixels a row behind them"""
+    tsz = rows.astype(np.int64) * (out_w + (0 if jitter_w is None else jitter_w.astype(np.int64))) * 3
+    return np.concatenate([[0], np.cumsum(tsz)[:-1]]).astype(np.int64), int(tsz.sum())
+
+
+def _out_buffer(n, out_h, out_w, as_uint8, dev):
+    """the batch every entry point of the input pipeline returns: the bytes [n, height, width, 3] or float32 [n, 3, height, width]"""
+    if as_uint8:
+        return torch.empty(n, out_h, out_w, 3, dtype=torch.uint8, device=dev)
+    return torch.empty(n, 3, out_h, out_w, dtype=torch.float32, device=dev)
+
+
 def preprocess_batch(images, size=(224, 224), device="cuda", as_uint8=False):
     """images: sequence of uint8 RGB images [H_i, W_i, 3] (numpy arrays, torch tensors or PIL images); size: (height, width)
     as torchvision's Resize takes it.  Returns float32 [B, 3, height, width] on `device` -- or, with as_uint8, the resampled
@@ -71,18 +85,13 @@ def preprocess_batch(images, size=(224, 224), device="cuda", as_uint8=False):
     B = len(arrs)
     dev = torch.device(device)
     src, src_offs, hs, ws = _stage(arrs, dev)
-    tsz = hs.astype(np.int64) * out_w * 3
-    tmp_offs = np.concatenate([[0], np.cumsum(tsz)[:-1]]).astype(np.int64)
+    tmp_offs, tmp_bytes = _tmp_layout(hs, out_w)
     meta = [torch.from_numpy(x).to(dev) for x in (src_offs, hs, ws, tmp_offs)]
-    tmp = torch.empty(int(tsz.sum()), dtype=torch.uint8, device=dev)
-    if as_uint8:
-        out = torch.empty(B, out_h, out_w, 3, dtype=torch.uint8, device=dev)
-        nat.check(nat.lib().dod_preprocess_u8(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), B, int(hs.max()), int(ws.max()),
-                                              out_h, out_w, nat.ptr(tmp), nat.ptr(meta[3]), nat.ptr(out), nat.stream_ptr()))
-        return out
-    out = torch.empty(B, 3, out_h, out_w, dtype=torch.float32, device=dev)
-    nat.check(nat.lib().dod_preprocess(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), B, int(hs.max()), int(ws.max()),
-                                       out_h, out_w, nat.ptr(tmp), nat.ptr(meta[3]), nat.ptr(out), nat.stream_ptr()))
+    tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
+    out = _out_buffer(B, out_h, out_w, as_uint8, dev)
+    fn = nat.lib().dod_preprocess_u8 if as_uint8 else nat.lib().dod_preprocess
+    nat.check(fn(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), B, int(hs.max()), int(ws.max()), out_h, out_w, nat.ptr(tmp),
+                 nat.ptr(meta[3]), nat.ptr(out), nat.stream_ptr()))
     return out
 
 

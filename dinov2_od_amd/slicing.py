@@ -23,7 +23,7 @@ import torch
 from . import _native as nat
 from . import augment as _aug
 from . import preprocess as _pre
-from .postprocess import Detections, MAX_TOP_K, _sizes_rows
+from .postprocess import Detections, MAX_TOP_K, _alloc, _check_det, _check_top_k, _sizes_rows
 
 MAX_CANDIDATES = 1 << 20                 # include/dinodet.h dod_detect_views: (views of one image) * Q * C
 NMS_METRICS = {"iou": 0, "ios": 1}       # intersection over union / over the smaller box
@@ -133,19 +133,11 @@ def _extract(arrs, plan, plan_dev, size, dev):
     if offsets.shape != (B + 1,) or offsets[0] != 0 or offsets[-1] != V or (np.diff(offsets) < 0).any():
         raise ValueError(f"plan: offsets must run from 0 to the {V} views in {B} non-decreasing steps, got {offsets.tolist()}")
     owner = np.repeat(np.arange(B), np.diff(offsets))
-    out = torch.empty(V, out_h, out_w, 3, dtype=torch.uint8, device=dev)
     if V == 0:
-        return out
-    crops, _, _ = _aug._check_params([arrs[b].shape[:2] for b in owner], rects, plan.flips, None, out_h, out_w)
+        return _pre._out_buffer(0, out_h, out_w, True, dev)
+    crops, flips, _ = _aug._check_params([arrs[b].shape[:2] for b in owner], rects, plan.flips, None, out_h, out_w)
     src, src_offs, hs, ws = _pre._stage(arrs, dev)          # every source image once; its views share the offset
-    tsz = crops[:, 3].astype(np.int64) * out_w * 3
-    tmp_offs = np.concatenate([[0], np.cumsum(tsz)[:-1]]).astype(np.int64)
-    meta = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (src_offs[owner], hs[owner], ws[owner], tmp_offs)]
-    tmp = torch.empty(int(tsz.sum()), dtype=torch.uint8, device=dev)
-    nat.check(nat.lib().dod_preprocess_aug_u8(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), V, nat.ptr(plan_dev.rects),
-                                              nat.ptr(plan_dev.flips), None, None, int(crops[:, 3].max()), int(crops[:, 2].max()), out_h, out_w,
-                                              nat.ptr(tmp), nat.ptr(meta[3]), nat.ptr(out), nat.stream_ptr()))
-    return out
+    return _aug._launch_aug(src, src_offs[owner], hs[owner], ws[owner], crops, flips, None, out_h, out_w, True, (plan_dev.rects, plan_dev.flips))
 
 
 def extract_views(images, plan, size=(224, 224), device="cuda"):
@@ -171,12 +163,7 @@ def detect_views_packed(det, num_classes, plan, sizes, top_k=100, threshold=0.05
     agree than could have; "max" keeps the founder's score.  Fused scores are not thresholded again.  Returns FusedDetections:
     SlicedDetections plus members [B, K] i32.
     One launch on the current stream, no host sync."""
-    if not (isinstance(det, torch.Tensor) and det.dtype == torch.float32 and det.dim() == 3):
-        raise ValueError("det must be a CUDA fp32 tensor [V, Q, C+4]")
-    V, Q, Wd = det.shape
-    Cn, K = int(num_classes), int(top_k)
-    if Wd != Cn + 4 or Cn < 1:
-        raise ValueError(f"det has {Wd} columns, expected num_classes + 4 = {Cn + 4}")
+    V, Q, Cn = _check_det(det, num_classes, "V")
     B = int(plan.offsets.shape[0]) - 1
     if B < 1 or Q < 1 or Q * Cn > MAX_CANDIDATES:
         raise ValueError(f"need at least one image and one query and at most 2^20 (query, class) pairs, got B={B} Q={Q} C={Cn}")
@@ -188,12 +175,7 @@ def detect_views_packed(det, num_classes, plan, sizes, top_k=100, threshold=0.05
             raise ValueError(f"plan: offsets must run from 0 to the {V} views without decreasing, got {off.tolist()}")
         if int(np.diff(off).max()) * Q * Cn > MAX_CANDIDATES:
             raise ValueError(f"an image has {int(np.diff(off).max())} views: more than {MAX_CANDIDATES} candidates with Q={Q} C={Cn}")
-    first = 1 if skip_background else 0
-    if first >= Cn:
-        raise ValueError("skip_background leaves no class (num_classes == 1)")
-    nms = nms_iou is not None
-    if nms and not float(nms_iou) >= 0.0:
-        raise ValueError(f"nms_iou must be None or >= 0, got {nms_iou}")
+    first, K, iou = _check_top_k(Cn, top_k, nms_iou, skip_background, MAX_TOP_K)
     if nms_metric not in NMS_METRICS:
         raise ValueError(f"nms_metric must be one of {sorted(NMS_METRICS)}, got {nms_metric!r}")
     if merge not in MERGES:
@@ -202,12 +184,10 @@ def detect_views_packed(det, num_classes, plan, sizes, top_k=100, threshold=0.05
     if fuse:
         if fuse_conf not in FUSE_CONFS:
             raise ValueError(f"fuse_conf must be one of {sorted(FUSE_CONFS)}, got {fuse_conf!r}")
-        if not nms:
+        if nms_iou is None:
             raise ValueError("merge='fuse' needs nms_iou: it is the IoU above which a candidate joins a cluster")
         if nms_metric != "iou":
             raise ValueError(f"merge='fuse' matches by IoU only, got nms_metric={nms_metric!r}")
-    if not 1 <= K <= MAX_TOP_K:
-        raise ValueError(f"top_k must be in 1..{MAX_TOP_K}, got {K}")
     st = _sizes_rows(sizes, B)
     if st is None:
         raise ValueError("sizes: the source images' (height, width) are needed to place the views")
@@ -219,25 +199,17 @@ def detect_views_packed(det, num_classes, plan, sizes, top_k=100, threshold=0.05
     pd = plan_to_device(plan, dev)
     st = st.to(device=dev, dtype=torch.float32).contiguous()
     ws = torch.empty(L.dod_detect_views_workspace_bytes(V, Q, Cn, K), dtype=torch.uint8, device=dev)     # dod_fuse_views' is the same
+    # the two entry points share their arguments up to the IoU threshold and from the class-agnostic flag to the boxes
+    head = (nat.ptr(det) if V else None, B, V, Q, Cn, nat.ptr(pd.offsets), nat.ptr(pd.rects) if V else None, nat.ptr(pd.flips) if V else None,
+            nat.ptr(st), first, float(threshold), K, iou)
+    flags = (int(bool(class_agnostic)), int(bool(clamp)), float(edge_margin))
+    out = _alloc(FusedDetections, B, K, dev, 2) if fuse else _alloc(SlicedDetections, B, K, dev, 1)
+    rows = (nat.ptr(out.scores), nat.ptr(out.labels), nat.ptr(out.views), nat.ptr(out.queries), nat.ptr(out.boxes))
+    tail = (nat.ptr(out.counts), nat.ptr(ws), ws.numel(), nat.stream_ptr())
     if fuse:
-        out = FusedDetections(torch.empty(B, K, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
-                              torch.empty(B, K, 4, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
-                              torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
-                              torch.empty(B, K, dtype=torch.int32, device=dev))
-        nat.check(L.dod_fuse_views(nat.ptr(det) if V else None, B, V, Q, Cn, nat.ptr(pd.offsets), nat.ptr(pd.rects) if V else None,
-                                   nat.ptr(pd.flips) if V else None, nat.ptr(st), first, float(threshold), K, float(nms_iou),
-                                   int(bool(class_agnostic)), int(bool(clamp)), float(edge_margin), FUSE_CONFS[fuse_conf], nat.ptr(out.scores),
-                                   nat.ptr(out.labels), nat.ptr(out.views), nat.ptr(out.queries), nat.ptr(out.boxes), nat.ptr(out.members),
-                                   nat.ptr(out.counts), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
-        return out
-    out = SlicedDetections(torch.empty(B, K, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
-                           torch.empty(B, K, 4, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev),
-                           torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev))
-    nat.check(L.dod_detect_views(nat.ptr(det) if V else None, B, V, Q, Cn, nat.ptr(pd.offsets), nat.ptr(pd.rects) if V else None,
-                                 nat.ptr(pd.flips) if V else None, nat.ptr(st), first, float(threshold), K, float(nms_iou) if nms else -1.0,
-                                 NMS_METRICS[nms_metric], int(bool(class_agnostic)), int(bool(clamp)), float(edge_margin), nat.ptr(out.scores),
-                                 nat.ptr(out.labels), nat.ptr(out.views), nat.ptr(out.queries), nat.ptr(out.boxes), nat.ptr(out.counts),
-                                 nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+        nat.check(L.dod_fuse_views(*head, *flags, FUSE_CONFS[fuse_conf], *rows, nat.ptr(out.members), *tail))
+    else:
+        nat.check(L.dod_detect_views(*head, NMS_METRICS[nms_metric], *flags, *rows, *tail))
     return out
 
 

@@ -49,11 +49,14 @@ def size_rows(sizes, B):
     return np.broadcast_to(s.reshape(-1, 2), (B, 2)).copy()
 
 
-def select(logits_flat, C, K, first_class, threshold):
-    """flat indices q*C + c of the first K candidates of one image, in order"""
+def select(logits_flat, C, K, first_class, threshold, row_ok=None):
+    """flat indices r*C + c of the first K candidates of one image, in order (r = q for dod_detect, v*Q + q for dod_detect_views);
+    row_ok [rows]: None or the edge filter's verdict on every row"""
     x = np.ascontiguousarray(logits_flat, dtype=np.float32)
     idx = np.arange(x.size)
     cand = (idx % C >= first_class) & ~np.isnan(x)
+    if row_ok is not None:
+        cand &= row_ok[idx // C]
     if not threshold < 0:
         cand &= sigmoid32(x) > F(threshold)
     ci = idx[cand]
@@ -73,8 +76,9 @@ def boxes_of(rows, hw, clamp):
     return np.stack([x1, y1, x2, y2], axis=1).astype(np.float32)
 
 
-def nms_keep(boxes, labels, iou, class_agnostic):
-    """greedy NMS over boxes in their order -> boolean keep mask"""
+def nms_keep(boxes, labels, iou, class_agnostic, metric=0):
+    """greedy NMS over boxes in their order -> boolean keep mask; metric 0 = IoU, 1 = intersection over the smaller box (the nms_metric
+    codes of dod_detect_views)"""
     n = len(boxes)
     keep = np.ones(n, bool)
     z = F(0.0)
@@ -86,8 +90,12 @@ def nms_keep(boxes, labels, iou, class_agnostic):
         iw = _max(z, _min(boxes[i, 2], r[:, 2]) - _max(boxes[i, 0], r[:, 0]))
         ih = _max(z, _min(boxes[i, 3], r[:, 3]) - _max(boxes[i, 1], r[:, 1]))
         inter = (iw * ih).astype(np.float32)
-        union = ((area[i] + area[i + 1:]).astype(np.float32) - inter).astype(np.float32)
-        sup = inter > (F(iou) * union).astype(np.float32)
+        if metric == 0:
+            ref = ((area[i] + area[i + 1:]).astype(np.float32) - inter).astype(np.float32)
+        else:
+            assert metric == 1
+            ref = _min(np.full(n - i - 1, area[i], np.float32), area[i + 1:])
+        sup = inter > (F(iou) * ref).astype(np.float32)
         if not class_agnostic:
             sup &= labels[i + 1:] == labels[i]
         keep[i + 1:] &= ~sup

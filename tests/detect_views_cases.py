@@ -14,7 +14,7 @@ from dinov2_od_amd.slicing import NMS_METRICS
 from tests import detect_cases as dc
 
 F = np.float32
-IOU, IOS = NMS_METRICS["iou"], NMS_METRICS["ios"]      # the nms_metric codes the Python layer passes: 0 and 1
+assert (NMS_METRICS["iou"], NMS_METRICS["ios"]) == (0, 1)      # the nms_metric codes the Python layer passes are the ones dc.nms_keep takes
 
 
 def view_boxes(rows, rect, flip):
@@ -52,43 +52,6 @@ def edge_cut(boxes, rect, margin, hw):
     return cut
 
 
-def select(logits_flat, C, K, first_class, threshold, row_ok):
-    """flat indices r*C + c (r = v*Q + q) of the first K candidates of one image, in order; row_ok [rows]: the edge filter's verdict"""
-    x = np.ascontiguousarray(logits_flat, dtype=np.float32)
-    idx = np.arange(x.size)
-    cand = (idx % C >= first_class) & ~np.isnan(x) & row_ok[idx // C]
-    if not threshold < 0:
-        cand &= dc.sigmoid32(x) > F(threshold)
-    ci = idx[cand]
-    order = np.lexsort((ci, ~dc.key_image(x[ci])))
-    return ci[order[:K]]
-
-
-def nms_keep(boxes, labels, iou, class_agnostic, metric):
-    """greedy NMS over boxes in their order -> boolean keep mask; metric 0 = IoU, 1 = intersection over the smaller box"""
-    n = len(boxes)
-    keep = np.ones(n, bool)
-    z = F(0.0)
-    area = (dc._max(z, boxes[:, 2] - boxes[:, 0]) * dc._max(z, boxes[:, 3] - boxes[:, 1])).astype(np.float32)
-    for i in range(n):
-        if not keep[i]:
-            continue
-        r = boxes[i + 1:]
-        iw = dc._max(z, dc._min(boxes[i, 2], r[:, 2]) - dc._max(boxes[i, 0], r[:, 0]))
-        ih = dc._max(z, dc._min(boxes[i, 3], r[:, 3]) - dc._max(boxes[i, 1], r[:, 1]))
-        inter = (iw * ih).astype(np.float32)
-        if metric == IOU:
-            ref = ((area[i] + area[i + 1:]).astype(np.float32) - inter).astype(np.float32)
-        else:
-            assert metric == IOS
-            ref = dc._min(np.full(n - i - 1, area[i], np.float32), area[i + 1:])
-        sup = inter > (F(iou) * ref).astype(np.float32)
-        if not class_agnostic:
-            sup &= labels[i + 1:] == labels[i]
-        keep[i + 1:] &= ~sup
-    return keep
-
-
 def detect_views_ref(det, C, K, offsets, rects, flips, sizes, first_class=1, threshold=-1.0, iou=None, metric=0, class_agnostic=False,
                      clamp=True, edge_margin=0.0):
     """the whole call: {"scores" [B,K] f32, "labels", "views", "queries" [B,K] i32, "boxes" [B,K,4] f32, "counts" [B] i32,
@@ -110,7 +73,7 @@ def detect_views_ref(det, C, K, offsets, rects, flips, sizes, first_class=1, thr
         cut = np.concatenate([edge_cut(raw[(v - v0) * Q:(v - v0 + 1) * Q], rects[v], edge_margin, hw[b]) for v in range(v0, v1)])
         out["rows"][b], out["cut"][b] = nv * Q, int(cut.sum())
         logits = det[v0:v1, :, :C].reshape(-1)
-        sel = select(logits, C, K, first_class, threshold, ~cut)
+        sel = dc.select(logits, C, K, first_class, threshold, ~cut)
         r, lab = sel // C, sel % C
         vi, q = r // Q, r % Q
         bx = raw[r]
@@ -120,7 +83,7 @@ def detect_views_ref(det, C, K, offsets, rects, flips, sizes, first_class=1, thr
         sc = dc.sigmoid32(logits[sel])
         out["selected"][b] = len(sel)
         if iou is not None:
-            keep = nms_keep(bx, lab, iou, class_agnostic, metric)
+            keep = dc.nms_keep(bx, lab, iou, class_agnostic, metric)
             vi, q, lab, bx, sc = vi[keep], q[keep], lab[keep], bx[keep], sc[keep]
         n = len(q)
         out["counts"][b] = n

@@ -8,10 +8,11 @@ import torch
 from dinov2_od_amd import _native as nat, synth
 from tests import cases
 from tests import detect_cases as dc
+from tests import guard_rows as gr
+from tests.guard_rows import same as _same
 
 pytestmark = pytest.mark.gpu
-GUARD = 8                       # rows in front of and behind every output
-SENT_F, SENT_I = -77.25, -777
+OUTS = ("scores", "labels", "queries", "boxes", "counts")
 
 
 @pytest.fixture(scope="module")
@@ -22,35 +23,22 @@ def pp():
     return postprocess
 
 
-def _guarded(rows, width, dtype, sentinel):
-    raw = torch.full((rows + 2 * GUARD, width), sentinel, dtype=dtype, device="cuda")
-    return raw, raw[GUARD:GUARD + rows]
-
-
 def _run(det, C, K, first_class=1, sizes=None, threshold=-1.0, iou=None, class_agnostic=False, clamp=True, stream=None):
     """dod_detect through the C ABI into guarded outputs -> dict of numpy arrays shaped like detect_cases.detect_ref's"""
     L = nat.lib()
     d = det if isinstance(det, torch.Tensor) else torch.from_numpy(det).cuda()
     B, Q, _ = d.shape
-    bufs = {"scores": _guarded(B * K, 1, torch.float32, SENT_F), "labels": _guarded(B * K, 1, torch.int32, SENT_I),
-            "queries": _guarded(B * K, 1, torch.int32, SENT_I), "boxes": _guarded(B * K, 4, torch.float32, SENT_F),
-            "counts": _guarded(B, 1, torch.int32, SENT_I)}
+    bufs = gr.buffers(B, K, OUTS)
     st = None if sizes is None else torch.from_numpy(dc.size_rows(sizes, B)).cuda()
     ws = torch.empty(L.dod_detect_workspace_bytes(B, Q, C, K), dtype=torch.uint8, device="cuda")
     assert ws.numel() > 0
     s = torch.cuda.current_stream() if stream is None else stream
     with torch.cuda.stream(s):
         nat.check(L.dod_detect(nat.ptr(d), B, Q, C, first_class, nat.ptr(st), float(threshold), K, -1.0 if iou is None else float(iou),
-                               int(class_agnostic), int(clamp), *(nat.ptr(bufs[k][1]) for k in ("scores", "labels", "queries", "boxes", "counts")),
-                               nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+                               int(class_agnostic), int(clamp), *(nat.ptr(bufs[k][1]) for k in OUTS), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
     s.synchronize()
-    out = {}
-    for k, (raw, view) in bufs.items():
-        sent = SENT_F if raw.dtype == torch.float32 else SENT_I
-        assert bool((raw[:GUARD] == sent).all()) and bool((raw[GUARD + view.shape[0]:] == sent).all()), f"guard rows of {k} written"
-        out[k] = view.cpu().numpy()
-    return {"scores": out["scores"].reshape(B, K), "labels": out["labels"].reshape(B, K), "queries": out["queries"].reshape(B, K),
-            "boxes": out["boxes"].reshape(B, K, 4), "counts": out["counts"].reshape(B)}
+    gr.untouched(bufs)
+    return gr.shaped(bufs, B, K)
 
 
 def _check(got, want):
@@ -65,10 +53,6 @@ def _check(got, want):
     pad = np.arange(K)[None, :] >= want["counts"][:, None]
     assert np.all(got["scores"][pad] == 0.0) and np.all(got["labels"][pad] == -1) and np.all(got["queries"][pad] == -1)
     assert not got["boxes"][pad].view(np.uint32).any()
-
-
-def _same(a, b):
-    return all(np.array_equal(a[k].view(np.uint32) if a[k].dtype == np.float32 else a[k], b[k].view(np.uint32) if b[k].dtype == np.float32 else b[k]) for k in a)
 
 
 TOPK_SHAPES = [(1, 1, 2, 1), (3, 7, 5, 4), (2, 113, 19, 100), (2, 100, 91, 100), (2, 300, 91, 300), (1, 300, 91, 1024), (65, 9, 3, 5)]

@@ -13,10 +13,10 @@ from dinov2_od_amd import _native as nat
 from tests import cases
 from tests import detect_cases as dc
 from tests import detect_views_cases as dv
+from tests import guard_rows as gr
+from tests.guard_rows import same as _same, untouched as _untouched
 
 pytestmark = pytest.mark.gpu
-GUARD = 8                       # rows in front of and behind every output
-SENT_F, SENT_I = -77.25, -777
 OUTS = ("scores", "labels", "views", "queries", "boxes", "counts")
 INVALID = 1                     # DOD_ERR_INVALID (include/dinodet.h)
 
@@ -29,24 +29,6 @@ def sl():
     return slicing
 
 
-def _guarded(rows, width, dtype, sentinel):
-    raw = torch.full((rows + 2 * GUARD, width), sentinel, dtype=dtype, device="cuda")
-    return raw, raw[GUARD:GUARD + rows]
-
-
-def _buffers(B, K):
-    return {"scores": _guarded(B * K, 1, torch.float32, SENT_F), "labels": _guarded(B * K, 1, torch.int32, SENT_I),
-            "views": _guarded(B * K, 1, torch.int32, SENT_I), "queries": _guarded(B * K, 1, torch.int32, SENT_I),
-            "boxes": _guarded(B * K, 4, torch.float32, SENT_F), "counts": _guarded(B, 1, torch.int32, SENT_I)}
-
-
-def _untouched(bufs, inside=False):
-    for k, (raw, view) in bufs.items():
-        sent = SENT_F if raw.dtype == torch.float32 else SENT_I
-        part = raw if inside else torch.cat([raw[:GUARD], raw[GUARD + view.shape[0]:]])
-        assert bool((part == sent).all()), f"{'outputs' if inside else 'guard rows'} of {k} written"
-
-
 def _run(case, C, K, first_class=1, threshold=-1.0, iou=None, metric=0, class_agnostic=False, clamp=True, margin=0.0, stream=None):
     """dod_detect_views through the C ABI into guarded outputs -> dict of numpy arrays shaped like detect_views_ref's"""
     det, offsets, rects, flips, sizes = case
@@ -54,7 +36,7 @@ def _run(case, C, K, first_class=1, threshold=-1.0, iou=None, metric=0, class_ag
     B, (V, Q, _) = len(offsets) - 1, det.shape
     d = det if isinstance(det, torch.Tensor) else torch.from_numpy(det).cuda()
     dev = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (offsets, rects.reshape(-1, 4), flips, dc.size_rows(sizes, B))]
-    bufs = _buffers(B, K)
+    bufs = gr.buffers(B, K, OUTS)
     ws = torch.empty(L.dod_detect_views_workspace_bytes(V, Q, C, K), dtype=torch.uint8, device="cuda")
     assert ws.numel() > 0
     s = torch.cuda.current_stream() if stream is None else stream
@@ -65,9 +47,7 @@ def _run(case, C, K, first_class=1, threshold=-1.0, iou=None, metric=0, class_ag
                                      *(nat.ptr(bufs[k][1]) for k in OUTS), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
     s.synchronize()
     _untouched(bufs)
-    out = {k: view.cpu().numpy() for k, (raw, view) in bufs.items()}
-    return {"scores": out["scores"].reshape(B, K), "labels": out["labels"].reshape(B, K), "views": out["views"].reshape(B, K),
-            "queries": out["queries"].reshape(B, K), "boxes": out["boxes"].reshape(B, K, 4), "counts": out["counts"].reshape(B)}
+    return gr.shaped(bufs, B, K)
 
 
 def _ref(case, C, K, first_class=1, threshold=-1.0, iou=None, metric=0, class_agnostic=False, clamp=True, margin=0.0):
@@ -93,10 +73,6 @@ def _check(got, want, nan_boxes=False):
     pad = np.arange(K)[None, :] >= want["counts"][:, None]
     assert np.all(got["scores"][pad] == 0.0) and np.all(got["labels"][pad] == -1) and np.all(got["views"][pad] == -1) and np.all(got["queries"][pad] == -1)
     assert not got["boxes"][pad].view(np.uint32).any()
-
-
-def _same(a, b):
-    return all(np.array_equal(a[k].view(np.uint32) if a[k].dtype == np.float32 else a[k], b[k].view(np.uint32) if b[k].dtype == np.float32 else b[k]) for k in a)
 
 
 @functools.lru_cache(maxsize=None)
@@ -130,6 +106,35 @@ def test_shapes_match_restatement(sl, counts, Q, C, K, nms):
         _check(got, want)
         if nms is None:
             assert np.array_equal(want["counts"], [min(K, n * Q * (C - first)) for n in counts])
+
+
+@pytest.mark.parametrize("clamp", [True, False])
+@pytest.mark.parametrize("iou,agnostic", [(None, False), (0.5, False), (0.5, True)])
+@pytest.mark.parametrize("B,Q,C,K", [(3, 9, 5, 4), (2, 7, 3, 64)])         # the second: fewer pairs than K, the pass without a select
+def test_one_unflipped_full_view_per_image_is_dod_detect(sl, B, Q, C, K, iou, agnostic, clamp):
+    """the kernels' statement of tests/test_detect_views_cpu.py's test of this name: both entry points end in the same tail
+    (det_finish, csrc/detect_select.h), so with rect = (0, 0, W, H) and no flip counts, labels, queries and the bits of boxes and scores
+    are dod_detect's, views is 0 in every valid row and -1 in the padding"""
+    L = nat.lib()
+    H, W = 37, 53
+    det = dc.random_det(48, B, Q, C)
+    case = (det, dv.offsets_of([1] * B), np.asarray([(0, 0, W, H)] * B, np.int32), np.zeros(B, np.uint8), [(float(H), float(W))] * B)
+    got = _run(case, C, K, 1, -1.0, iou, 0, agnostic, clamp)
+    names = ("scores", "labels", "queries", "boxes", "counts")
+    bufs = gr.buffers(B, K, names)
+    d, st = torch.from_numpy(det).cuda(), torch.from_numpy(dc.size_rows((H, W), B)).cuda()
+    ws = torch.empty(L.dod_detect_workspace_bytes(B, Q, C, K), dtype=torch.uint8, device="cuda")
+    nat.check(L.dod_detect(nat.ptr(d), B, Q, C, 1, nat.ptr(st), -1.0, K, -1.0 if iou is None else float(iou), int(agnostic), int(clamp),
+                           *(nat.ptr(bufs[k][1]) for k in names), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+    torch.cuda.synchronize()
+    _untouched(bufs)
+    want = gr.shaped(bufs, B, K)
+    for k in names:
+        assert _same({k: want[k]}, {k: got[k]}), k
+    n = got["counts"]
+    assert n.min() > 0 and (iou is not None or np.all(n == min(K, Q * (C - 1))))
+    valid = np.arange(K)[None, :] < n[:, None]
+    assert np.all(got["views"][valid] == 0) and np.all(got["views"][~valid] == -1)
 
 
 @pytest.mark.parametrize("counts,Q,C,K", [((1, 5, 2), 7, 5, 4), ((13, 13), 100, 91, 300), ((3, 2), 40, 7, 33)])
@@ -267,7 +272,7 @@ def test_invalid_arguments_return_invalid_and_write_nothing(sl):
     det, offsets, rects, flips, sizes = _case(46, counts, Q, C)
     B, V = len(counts), int(sum(counts))
     t = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (det, offsets, rects, flips, dc.size_rows(sizes, B))]
-    bufs = _buffers(B, K)
+    bufs = gr.buffers(B, K, OUTS)
     ws = torch.empty(L.dod_detect_views_workspace_bytes(V, Q, C, K), dtype=torch.uint8, device="cuda")
     good = dict(det=nat.ptr(t[0]), B=B, V=V, Q=Q, C=C, offs=nat.ptr(t[1]), rects=nat.ptr(t[2]), flips=nat.ptr(t[3]), sizes=nat.ptr(t[4]), first=1,
                 thr=-1.0, K=K, iou=0.5, metric=0, agn=0, clamp=1, margin=0.0, ws=nat.ptr(ws), wsb=ws.numel())

@@ -22,10 +22,9 @@ from tests import cases
 from tests import detect_cases as dc
 from tests import detect_views_cases as dv
 from tests import fuse_views_cases as fv
+from tests.guard_rows import buffers as _buffers, same as _same, shaped as _shaped, untouched as _untouched
 
 pytestmark = pytest.mark.gpu
-GUARD = 8
-SENT_F, SENT_I = -77.25, -777
 OUTS = ("scores", "labels", "views", "queries", "boxes", "members", "counts")
 BASE = ("scores", "labels", "views", "queries", "boxes", "counts")
 INVALID = 1                     # DOD_ERR_INVALID (include/dinodet.h)
@@ -37,28 +36,6 @@ def sl():
         pytest.fail("GPU tests need a GPU")
     from dinov2_od_amd import slicing
     return slicing
-
-
-def _guarded(rows, width, dtype, sentinel):
-    raw = torch.full((rows + 2 * GUARD, width), sentinel, dtype=dtype, device="cuda")
-    return raw, raw[GUARD:GUARD + rows]
-
-
-def _buffers(B, K, names):
-    shape = {"boxes": (B * K, 4, torch.float32, SENT_F), "scores": (B * K, 1, torch.float32, SENT_F), "counts": (B, 1, torch.int32, SENT_I)}
-    return {k: _guarded(*shape.get(k, (B * K, 1, torch.int32, SENT_I))) for k in names}
-
-
-def _untouched(bufs, inside=False):
-    for k, (raw, view) in bufs.items():
-        sent = SENT_F if raw.dtype == torch.float32 else SENT_I
-        part = raw if inside else torch.cat([raw[:GUARD], raw[GUARD + view.shape[0]:]])
-        assert bool((part == sent).all()), f"{'outputs' if inside else 'guard rows'} of {k} written"
-
-
-def _shaped(bufs, B, K):
-    out = {k: view.cpu().numpy() for k, (raw, view) in bufs.items()}
-    return {k: v.reshape(B) if k == "counts" else v.reshape(B, K, 4) if k == "boxes" else v.reshape(B, K) for k, v in out.items()}
 
 
 def _device(case):
@@ -128,10 +105,6 @@ def _check(case, C, K, first_class=1, threshold=-1.0, iou=0.5, class_agnostic=Fa
     assert np.all(got["queries"][pad] == -1) and not got["members"][pad].any() and not got["boxes"][pad].view(np.uint32).any()
     assert np.all(got["members"][~pad] >= 1)
     return got, want
-
-
-def _same(a, b):
-    return all(np.array_equal(a[k].view(np.uint32) if a[k].dtype == np.float32 else a[k], b[k].view(np.uint32) if b[k].dtype == np.float32 else b[k]) for k in a)
 
 
 @functools.lru_cache(maxsize=None)
