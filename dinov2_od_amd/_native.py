@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("DINODET_LIB") or os.path.join(_HERE, "lib", "libdinod
 DOD_F32, DOD_BF16 = 0, 1
 PREC = {"fp32": 0, "bf16": 1, "fp8": 2, "bf16x3": 3, "fp16x2": 4}
 ACT = {"none": 0, "relu": 1, "gelu": 2, "sigmoid": 3, "swiglu_pairs": 4}
+LN_FORM = {"f32": 0, "bf16": 1, "f32_bf16": 2, "pair": 3, "h2": 4, "fp8": 5, "fp8_mx": 6, "f32_s3": 7}      # enum DOD_LN_*
 PW = {"gelu_bwd": 0, "swiglu_bwd": 1, "relu_drop_bwd": 2, "dropout_add": 3, "sigmoid_bwd4": 4}      # enum dod_pointwise_op
 
 
@@ -144,6 +145,10 @@ SYMBOLS = {
     "dod_op_split_h2": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "dod_op_linear_h2": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "dod_op_layernorm": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, _I, _P]),
+    "dod_op_layernorm_form": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P]),
+    "dod_op_swiglu": (_I, [_P, _P, _I, _I, _I, _P]),
+    "dod_op_split3": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "dod_op_deform_sample_ex": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dod_op_linear_ln": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, C.POINTER(DodLnFold), _P]),
     "dod_op_rowstats": (_I, [_P, _I, _I, _F, _P, _I, _P, _P]),
     "dod_op_ln_finalize": (_I, [_P, _I, _I, _F, _P, _P]),

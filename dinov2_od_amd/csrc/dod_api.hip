@@ -474,6 +474,45 @@ int dod_op_layernorm(const float* x, const float* add, const float* gamma, const
   if (!x || !gamma || !beta || !out) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
   return rejected(nullptr, launch_layernorm(x, add, gamma, beta, eps, rows, D, ln_out(out_dtype == DOD_F32 ? (float*)out : nullptr, out_dtype == DOD_BF16 ? (bf16_t*)out : nullptr), (hipStream_t)stream), "dod_op_layernorm rows=%d D=%d", rows, D);
 }
+// every output form of launch_layernorm, as the forward schedules fill LnOut
+int dod_op_layernorm_form(const float* x, const float* add, const float* gamma, const float* beta, float eps, int rows, int D, int form, void* out, void* out2,
+                          void* stream) {
+  if (!x || !gamma || !beta || !out) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
+  if (form < DOD_LN_F32 || form > DOD_LN_F32_S3) return fail(nullptr, DOD_ERR_INVALID, "dod_op_layernorm_form: unknown form %d", form);
+  const bool two = form == DOD_LN_F32_BF16 || form == DOD_LN_FP8 || form == DOD_LN_FP8_MX || form == DOD_LN_F32_S3;
+  if (two && !out2) return fail(nullptr, DOD_ERR_INVALID, "null buffer (form %d writes out2)", form);
+  if (!two && out2) return fail(nullptr, DOD_ERR_INVALID, "dod_op_layernorm_form: form %d has no second output, out2 must be NULL", form);
+  if (rows <= 0 || D <= 0) return fail(nullptr, DOD_ERR_INVALID, "dod_op_layernorm_form: rows=%d D=%d must be positive", rows, D);
+  if (D % 4 != 0 || D > 2048) return fail(nullptr, DOD_ERR_INVALID, "dod_op_layernorm_form: D=%d must be a multiple of 4 and at most 2048", D);
+  if (form == DOD_LN_H2 && D % 32 != 0) return fail(nullptr, DOD_ERR_INVALID, "dod_op_layernorm_form: H2 rows need D %% 32 == 0 (D=%d)", D);
+  if (form == DOD_LN_FP8_MX && D % 64 != 0) return fail(nullptr, DOD_ERR_INVALID, "dod_op_layernorm_form: block-scaled rows need D %% 64 == 0 (D=%d)", D);
+  LnOut o;
+  switch (form) {
+    case DOD_LN_F32: o.f32 = (float*)out; break;
+    case DOD_LN_BF16: o.bf16 = (bf16_t*)out; break;
+    case DOD_LN_F32_BF16: o.f32 = (float*)out; o.bf16 = (bf16_t*)out2; break;
+    case DOD_LN_PAIR: case DOD_LN_H2: o.split = (bf16_t*)out; break;
+    case DOD_LN_FP8: o.fp8 = (unsigned char*)out; o.scale = (float*)out2; break;
+    case DOD_LN_FP8_MX: o.fp8 = (unsigned char*)out; o.bs = (unsigned char*)out2; break;
+    default: o.f32 = (float*)out; o.a3 = (bf16_t*)out2; break;
+  }
+  return rejected(nullptr, launch_layernorm(x, add, gamma, beta, eps, rows, D, o, (hipStream_t)stream, form == DOD_LN_H2 ? 1 : 0), "dod_op_layernorm_form rows=%d D=%d form=%d", rows, D, form);
+}
+int dod_op_swiglu(const void* x, void* out, int dtype, int rows, int Fh, void* stream) {
+  if (!x || !out) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
+  if (dtype != DOD_F32 && dtype != DOD_BF16) return fail(nullptr, DOD_ERR_INVALID, "dod_op_swiglu: dtype must be DOD_F32 or DOD_BF16");
+  if (rows <= 0 || Fh <= 0) return fail(nullptr, DOD_ERR_INVALID, "dod_op_swiglu: rows=%d Fh=%d must be positive", rows, Fh);
+  const bool bf = dtype == DOD_BF16;
+  return rejected(nullptr, launch_swiglu(bf ? nullptr : (const float*)x, bf ? (const bf16_t*)x : nullptr, rows, Fh, bf ? nullptr : (float*)out, bf ? (bf16_t*)out : nullptr, (hipStream_t)stream),
+                  "dod_op_swiglu rows=%d Fh=%d", rows, Fh);
+}
+int dod_op_split3(const float* x, int ld, int rows, int cols, int weight_order, void* out, void* stream) {
+  if (!x || !out) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
+  if (rows <= 0 || cols <= 0) return fail(nullptr, DOD_ERR_INVALID, "dod_op_split3: rows=%d cols=%d must be positive", rows, cols);
+  if (ld < cols) return fail(nullptr, DOD_ERR_INVALID, "dod_op_split3: pitch %d is less than cols=%d", ld, cols);
+  if (weight_order != 0 && weight_order != 1) return fail(nullptr, DOD_ERR_INVALID, "dod_op_split3: weight_order must be 0 or 1");
+  return rejected(nullptr, launch_split3(x, ld, (bf16_t*)out, rows, cols, weight_order, (hipStream_t)stream), "dod_op_split3 rows=%d cols=%d", rows, cols);
+}
 int dod_op_attention_bf16(const void* qkv, void* ctx, int B, int N, int heads, float scale, void* stream) {
   if (!qkv || !ctx) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
   return rejected(nullptr, launch_attn_bf16((const bf16_t*)qkv, (bf16_t*)ctx, B, N, heads, scale, (hipStream_t)stream), "dod_op_attention_bf16");
@@ -495,6 +534,18 @@ int dod_op_deform_sample(const float* proj, int ldp, const float* values, int B,
   if (!proj || !values || !out) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
   if (hh * ww != N) return fail(nullptr, DOD_ERR_INVALID, "Cannot reshape input of size %d into a %dx%d feature map", N, hh, ww);
   return rejected(nullptr, launch_deform_sample(proj, ldp, values, B, Q, N, Hd, P, dh, hh, ww, out, (hipStream_t)stream), "dod_op_deform_sample");
+}
+// the decoder's own launch: projections shared by all images (layer 0) and / or the fused [hi | hi | lo] operand copy
+int dod_op_deform_sample_ex(const float* proj, int ldp, int proj_shared, const float* values, int B, int Q, int N, int Hd, int P, int dh, int hh, int ww, float* out,
+                            void* out3, void* stream) {
+  if (!proj || !values || !out) return fail(nullptr, DOD_ERR_INVALID, "null buffer");
+  if (B <= 0 || Q <= 0 || N <= 0 || Hd <= 0 || hh <= 0 || ww <= 0) return fail(nullptr, DOD_ERR_INVALID, "dod_op_deform_sample_ex: B=%d Q=%d N=%d Hd=%d h=%d w=%d must be positive", B, Q, N, Hd, hh, ww);
+  if (P < 1 || P > 8) return fail(nullptr, DOD_ERR_INVALID, "dod_op_deform_sample_ex: 1..8 sampling points (got %d)", P);
+  if (dh < 1 || dh > 128) return fail(nullptr, DOD_ERR_INVALID, "dod_op_deform_sample_ex: head_dim 1..128 (got %d)", dh);
+  if ((long long)hh * ww != N) return fail(nullptr, DOD_ERR_INVALID, "Cannot reshape input of size %d into a %dx%d feature map", N, hh, ww);
+  if (ldp < 2 + 3LL * Hd * P) return fail(nullptr, DOD_ERR_INVALID, "dod_op_deform_sample_ex: pitch %d is less than 2 + 3*Hd*P = %lld", ldp, 2 + 3LL * Hd * P);
+  if ((long long)B * Q * Hd > 0x7fffffffLL) return fail(nullptr, DOD_ERR_INVALID, "dod_op_deform_sample_ex: B*Q*Hd is more items than one launch holds");
+  return rejected(nullptr, launch_deform_sample(proj, ldp, values, B, Q, N, Hd, P, dh, hh, ww, out, (hipStream_t)stream, proj_shared ? 1 : 0, (bf16_t*)out3), "dod_op_deform_sample_ex");
 }
 int dod_op_pos_resize(const float* pos_in, int G, int gh, int gw, int D, float* pos_out, void* stream) {
   if (!pos_in || !pos_out) return fail(nullptr, DOD_ERR_INVALID, "null buffer");

@@ -257,6 +257,24 @@ int dod_op_ln_finalize(const void* part, int rows, int D, float eps, void* stats
 /* out = LayerNorm(x + add) ; add may be NULL */
 int dod_op_layernorm(const float* x, const float* add, const float* gamma, const float* beta, float eps,
                      int rows, int D, void* out, int out_dtype, void* stream);
+/* The same LayerNorm in every output form the forward schedules launch (D % 4 == 0, D <= 2048).  `form` says what out / out2 are:
+ *   DOD_LN_F32       out fp32 [rows, D]                                          out2 NULL
+ *   DOD_LN_BF16      out bf16 [rows, D]                                          out2 NULL
+ *   DOD_LN_F32_BF16  out fp32 [rows, D]                                          out2 bf16 [rows, D], the rounding of out
+ *   DOD_LN_PAIR      out bf16 [rows, 2 D] = [hi | lo], as dod_op_split_pair      out2 NULL
+ *   DOD_LN_H2        out H2 operand rows of 4 D bytes, as dod_op_split_h2 (D % 32 == 0)        out2 NULL
+ *   DOD_LN_FP8       out e4m3 [rows, D], value = q * scale                       out2 fp32 scale [rows] = amax / 448 (1.0 for a zero row)
+ *   DOD_LN_FP8_MX    out e4m3 [rows, D] (D % 64 == 0)                            out2 e8m0 bytes [rows][2][D / 64], as dod_op_quant_mx_fp8
+ *   DOD_LN_F32_S3    out fp32 [rows, D]                                          out2 bf16 [rows, 3 D] = [hi | hi | lo], the split of out */
+enum { DOD_LN_F32 = 0, DOD_LN_BF16 = 1, DOD_LN_F32_BF16 = 2, DOD_LN_PAIR = 3, DOD_LN_H2 = 4, DOD_LN_FP8 = 5, DOD_LN_FP8_MX = 6, DOD_LN_F32_S3 = 7 };
+int dod_op_layernorm_form(const float* x, const float* add, const float* gamma, const float* beta, float eps,
+                          int rows, int D, int form, void* out, void* out2, void* stream);
+/* SwiGLU gate of [rows, 2 Fh] rows whose halves are chunked, not interleaved: out[r][c] = silu(x[r][c]) * x[r][Fh + c].  dtype DOD_F32 or
+ * DOD_BF16 is the type of x and of out alike. */
+int dod_op_swiglu(const void* x, void* out, int dtype, int rows, int Fh, void* stream);
+/* x [rows, cols] fp32 at pitch ld -> bf16 [rows, 3 cols]: hi = bf16(x), lo = bf16(x - hi); weight_order 0: the activation operand
+ * [hi | hi | lo], 1: the weight operand [hi | lo | hi] */
+int dod_op_split3(const float* x, int ld, int rows, int cols, int weight_order, void* out, void* stream);
 /* qkv [B*N, 3*heads*64] bf16 -> ctx [B*N, heads*64] bf16 */
 int dod_op_attention_bf16(const void* qkv, void* ctx, int B, int N, int heads, float scale, void* stream);
 /* The same attention with the fp8 mode's epilogue: the context leaves block-scaled, ctx_q8 [B*N, D] e4m3 bytes (D = heads*64; a head's 64
@@ -269,6 +287,11 @@ int dod_op_attention_f32(const float* q, const float* k, const float* v, float* 
 /* proj [B*Q, ldp] = [ref logits(2) | offsets(Hd*P*2) | weight logits(Hd*P)], values [B*N, Hd*dh] -> out [B*Q, Hd*dh] */
 int dod_op_deform_sample(const float* proj, int ldp, const float* values, int B, int Q, int N, int Hd, int P,
                          int dh, int h, int w, float* out, void* stream);
+/* The same gather as the decoder launches it: proj_shared != 0: proj has Q rows only, shared by every image (layer 0, whose queries do not
+ * depend on the image); out3 != NULL: out is written a second time as the bf16 operand [B*Q, 3*Hd*dh] = [hi | hi | lo] of the output
+ * projection.  1 <= P <= 8, dh <= 128, h*w == N, ldp >= 2 + 3*Hd*P. */
+int dod_op_deform_sample_ex(const float* proj, int ldp, int proj_shared, const float* values, int B, int Q, int N, int Hd, int P,
+                            int dh, int h, int w, float* out, void* out3, void* stream);
 /* pos_in [G*G+1, D] -> pos_out [gh*gw+1, D] */
 int dod_op_pos_resize(const float* pos_in, int G, int gh, int gw, int D, float* pos_out, void* stream);
 /* img [B,3,H,W] -> cols [B*(H/p)*(W/p), Kp] of out_dtype */

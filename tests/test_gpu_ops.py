@@ -1,8 +1,15 @@
-"""`-m gpu`: every HIP kernel of the inference path, called through the C ABI's operator entry points,
-against the CPU oracle / a plain fp32 torch statement of the same op, on seeded inputs (the training
-step's adjoint kernels: tests/test_gpu_train_ops.py, against float64).  Tolerances are written
-next to each comparison: fp32 kernels 1e-5-level (summation order only); bf16 kernels are
-compared with the SAME bf16-rounded operands evaluated in fp32 on the CPU."""
+"""`-m gpu`: the HIP kernels of the inference path that dod_op_linear, dod_op_gemm_f32x, dod_op_layernorm, dod_op_attention_*,
+dod_op_deform_sample, dod_op_pos_resize and dod_op_im2col reach, against the CPU oracle / a plain fp32 torch statement of the same op, on seeded inputs, under
+tensor-wide bounds (max |a - b| / max |b|).  Tolerances are written next to each comparison: fp32 kernels 1e-5-level (summation
+order only); bf16 kernels are compared with the SAME bf16-rounded operands evaluated in fp32 on the CPU.
+
+What this file does NOT reach, and where it is tested per element against float64: the training step's adjoint kernels
+(tests/test_gpu_train_ops.py); every attention form and output format (tests/test_gpu_attention.py); the inference GEMM forms and the
+fused patch embedding (tests/test_gpu_gemm_edges.py); and the row and gather kernels -- test_layernorm here runs dod_op_layernorm's
+fp32 and bf16 forms at D = 128, 384, 768, 1536 (four of layernorm_kernel's nine dispatch arms, two of its seven output forms) and
+test_deform_sample_matches_oracle the gather with per-image projections at the projection width and without the fused operand copy; the other
+arms and forms, rowstats_kernel over the same sweep, the shared-projection / out3 gather, swiglu_kernel and split3_kernel are
+tests/test_gpu_rowops.py's."""
 import math
 
 import numpy as np

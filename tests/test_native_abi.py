@@ -253,6 +253,60 @@ def test_attention_epilogue_operators_validate_arguments(lib):
     assert mx(p, p, p, 1 << 16, 1, 1 << 16, 0.125, None) == 1 and h2(p, p, 1 << 16, 1, 1 << 16, 0.125, None) == 1      # B * heads past an int
 
 
+def test_row_and_gather_operators_validate_arguments(lib):
+    """dod_op_layernorm_form / dod_op_deform_sample_ex / dod_op_swiglu / dod_op_split3: a null pointer, a non-positive size or a shape the
+    launcher does not take is DOD_ERR_INVALID with a message before any launch (no GPU here: a launch would be DOD_ERR_HIP)."""
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p)
+    err = lambda: lib.dod_last_error(None)
+    F = nat.LN_FORM
+    two = {"f32_bf16", "fp8", "fp8_mx", "f32_s3"}
+
+    def ln(form="f32", rows=5, D=64, null=None, out2="auto"):
+        a = [p, p, p, p, 1e-6, rows, D, F[form] if isinstance(form, str) else form, p, (p if form in two else None) if out2 == "auto" else out2, None]
+        if null is not None:
+            a[null] = None
+        return lib.dod_op_layernorm_form(*a)
+    for form in F:
+        for i in (0, 2, 3, 8):                                  # x, gamma, beta, out (add may be NULL)
+            assert ln(form, null=i) == 1 and b"null" in err(), (form, i)
+        assert ln(form, D=2052) == 1 and b"2048" in err(), form
+        assert ln(form, D=66) == 1 and b"multiple of 4" in err(), form
+        assert ln(form, rows=0) == 1 and ln(form, rows=-3) == 1 and ln(form, D=0) == 1 and b"positive" in err(), form
+        if form in two:
+            assert ln(form, out2=None) == 1 and b"null" in err(), form
+        else:
+            assert ln(form, out2=p) == 1 and b"out2 must be NULL" in err(), form
+    assert ln("h2", D=48) == 1 and b"32" in err() and ln("h2", D=2044) == 1
+    assert ln("fp8_mx", D=96) == 1 and b"64" in err() and ln("fp8_mx", D=32) == 1 and ln("fp8_mx", D=2016) == 1
+    assert ln(-1) == 1 and ln(8) == 1 and b"unknown form" in err()
+
+    def dfm(ldp=20, shared=0, B=3, Q=5, N=26, Hd=3, P=2, dh=32, hh=2, ww=13, null=None):
+        a = [p, ldp, shared, p, B, Q, N, Hd, P, dh, hh, ww, p, None, None]
+        if null is not None:
+            a[null] = None
+        return lib.dod_op_deform_sample_ex(*a)
+    for i in (0, 3, 12):                                        # proj, values, out (out3 may be NULL)
+        assert dfm(null=i) == 1 and b"null" in err(), i
+    assert dfm(P=9, ldp=64) == 1 and b"points" in err() and dfm(P=0) == 1
+    assert dfm(dh=129) == 1 and b"head_dim" in err() and dfm(dh=0) == 1
+    assert dfm(hh=5, ww=5) == 1 and b"feature map" in err()
+    assert dfm(ldp=19) == 1 and b"pitch" in err()
+    for kw in (dict(B=0), dict(Q=-1), dict(Hd=0), dict(N=0, hh=0, ww=13), dict(N=0, hh=13, ww=0)):
+        assert dfm(**kw) == 1 and b"positive" in err(), kw
+    assert dfm(B=1 << 15, Q=1 << 15, Hd=3, shared=1) == 1 and b"items" in err()
+
+    sw = lib.dod_op_swiglu
+    assert sw(None, p, 0, 3, 5, None) == 1 and b"null" in err() and sw(p, None, 1, 3, 5, None) == 1 and b"null" in err()
+    assert sw(p, p, 2, 3, 5, None) == 1 and b"dtype" in err()
+    assert sw(p, p, 0, 0, 5, None) == 1 and sw(p, p, 1, 3, -1, None) == 1 and b"positive" in err()
+    s3 = lib.dod_op_split3
+    assert s3(None, 8, 2, 8, 0, p, None) == 1 and b"null" in err() and s3(p, 8, 2, 8, 0, None, None) == 1 and b"null" in err()
+    assert s3(p, 7, 2, 8, 0, p, None) == 1 and b"pitch" in err()
+    assert s3(p, 8, 0, 8, 0, p, None) == 1 and s3(p, 8, 2, 0, 1, p, None) == 1 and b"positive" in err()
+    assert s3(p, 8, 2, 8, 2, p, None) == 1 and b"weight_order" in err()
+
+
 def test_create_validates_arguments(lib):
     bb, dc = cases.cfg1(25)
     h = C.c_void_p()
