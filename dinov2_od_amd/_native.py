@@ -183,6 +183,8 @@ SYMBOLS = {
     "dod_coco_eval_append_host": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P, _I64, _P]),
     "dod_coco_eval_evaluate": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P, _P, _P, _P, _P, _P]),
     "dod_coco_eval_matches": (_I, [_P, _SZ, _I64, _I, _I, _I64, _I64, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "dod_coco_eval_append_detections": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P]),
+    "dod_coco_eval_confusion": (_I, [_P, _SZ, _I64, _I, _I, _I64, C.c_double, C.c_double, _P, _P]),
     "dod_op_sort_pairs_workspace_bytes": (_SZ, [_I64]),
     "dod_op_sort_pairs_u64": (_I, [_P, _P, _P, _P, _I64, _I, _I, _P, _SZ, _P]),
     "dod_set_criterion_workspace_bytes": (_SZ, [_I, _I, _I]),

@@ -6,12 +6,16 @@ useCats = 1.  The device code restates COCOeval operation for operation in doubl
 the arrays pycocotools builds, bit for bit, and the 12 `stats` their means.
 
     compute_coco_metrics(results, annotation_file)   the reference's function: same signature, same six keys
-    COCOEvaluator(annotations, device)               .add_records / .add_packed / .evaluate / .reset
+    COCOEvaluator(annotations, device)               .add_records / .add_packed / .add_detections / .evaluate / .confusion_matrix / .reset
     validate_coco(model, dataloader, device, annotations)   forward -> add_packed per batch (no host sync) -> one evaluate
+    validate_coco(..., detect=dict(...) | sliced=dict(...), category_ids=table)   model.detect / detect_sliced -> add_detections
+    per_category_metrics(result, annotations)        AP / AP50 / AR100 of every category from evaluate()'s arrays (host only)
 
 The evaluator compares what it is given: the reference emits normalised boxes and class indices as `category_id`
-(utils.py:225-233), and neither is "fixed" here.  One deviation from pycocotools: an empty result list evaluates (AP = AR = 0
-where ground truth exists) instead of raising.
+(utils.py:225-233), and neither is "fixed" in `add_packed` or in `validate_coco` without `detect=` / `sliced=`.  `add_detections`
+takes what `model.detect` and `detect_sliced` return -- pixel xyxy boxes in each image's own size, a label per row -- and maps the
+labels through `category_ids`, which is what a real COCO annotation file (pixel boxes, COCO category ids) is scored against.
+One deviation from pycocotools: an empty result list evaluates (AP = AR = 0 where ground truth exists) instead of raising.
 
 The host part of this module (annotation loading and grouping, input checks) is plain numpy and runs without a GPU; the
 evaluation itself has no CPU fallback.
@@ -31,6 +35,9 @@ AREA_RANGES = ((0.0, 1e10), (0.0, 1024.0), (1024.0, 9216.0), (9216.0, 1e10))
 MAX_DETS = (1, 10, 100)
 MAX_GT_PER_GROUP = 1024
 MAX_DETECTIONS = 1 << 24
+MAX_CONFUSION_CATEGORIES = 2048          # include/dinodet.h dod_coco_eval_confusion
+MAX_GT_PER_IMAGE = 1024                  #   non-crowd ground truths of one image, all categories
+MAX_APPEND_IMAGES = 1 << 16              # include/dinodet.h dod_coco_eval_append_detections: images of one call
 METRIC_KEYS = ("AP", "AP50", "AP75", "APs", "APm", "APl")
 
 # struct dod_coco_det: one detection with the doubles a results list holds
@@ -51,6 +58,11 @@ class Annotations:
     @property
     def num_groups(self):
         return int(np.unique(self.gt_group).size)
+
+    def gt_per_image(self):
+        """non-crowd ground truths of every image, all categories together [I]: what the confusion matrix matches against"""
+        I = self.image_ids.size
+        return np.bincount((self.gt_group % I)[self.gt_iscrowd == 0], minlength=I).astype(np.int64)
 
 
 def _index_of(sorted_ids, ids):
@@ -123,6 +135,70 @@ def to_coco_dets(records, ann):
     return out
 
 
+def _id_list(ids, n, name):
+    """ids (a sequence or an integer tensor) -> a tuple of Python ints, or the tensor itself when it is on a GPU (reading it would
+    synchronise); ValueError unless it is one-dimensional with n entries (n None: at least one)"""
+    import torch
+    if isinstance(ids, torch.Tensor):
+        if ids.dim() != 1 or ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+            raise ValueError(f"{name} must be a one-dimensional integer tensor or a sequence of ints")
+        out, size = (ids if ids.is_cuda else tuple(int(v) for v in ids.tolist())), ids.numel()
+    else:
+        try:
+            out = tuple(int(v) for v in ids)
+        except TypeError:
+            raise ValueError(f"{name} must be a one-dimensional integer tensor or a sequence of ints") from None
+        size = len(out)
+    if size < 1 or (n is not None and size != n):
+        raise ValueError(f"{name} must have {'at least one entry' if n is None else f'one entry per image ({n})'}, got {size}")
+    return out
+
+
+def _ids_on(ids, device):
+    """what _id_list returned -> an int64 tensor on device, without a host synchronisation"""
+    import torch
+    if isinstance(ids, tuple):
+        return torch.tensor(ids, dtype=torch.int64).to(device, non_blocking=True)
+    return ids.to(device=device, dtype=torch.int64).contiguous()
+
+
+def check_detections(result, image_ids, category_ids=None):
+    """The argument checks of COCOEvaluator.add_detections, the device looked at last so that every argument is checked whether or not
+    a GPU is present.  -> ((scores, labels, boxes, counts), image ids, category table or None), the last two as _id_list returns them"""
+    import torch
+    try:
+        t = (result.scores, result.labels, result.boxes, result.counts)
+    except AttributeError:
+        raise ValueError("result must be a postprocess.Detections (scores, labels, boxes, queries, counts)") from None
+    scores, labels, boxes, counts = t
+    if not all(isinstance(v, torch.Tensor) for v in t):
+        raise ValueError("result must hold tensors")
+    if scores.dim() != 2 or scores.dtype != torch.float32 or scores.shape[0] < 1 or scores.shape[1] < 1:
+        raise ValueError("result.scores must be fp32 [B, Kd] with B >= 1 and Kd >= 1")
+    B, Kd = scores.shape
+    if B > MAX_APPEND_IMAGES:
+        raise ValueError(f"at most {MAX_APPEND_IMAGES} images per call, got {B}")
+    if tuple(labels.shape) != (B, Kd) or labels.dtype != torch.int32:
+        raise ValueError(f"result.labels must be int32 [{B}, {Kd}]")
+    if tuple(boxes.shape) != (B, Kd, 4) or boxes.dtype != torch.float32:
+        raise ValueError(f"result.boxes must be fp32 [{B}, {Kd}, 4]")
+    if tuple(counts.shape) != (B,) or counts.dtype != torch.int32:
+        raise ValueError(f"result.counts must be int32 [{B}]")
+    ids = _id_list(image_ids, B, "image_ids")
+    table = None if category_ids is None else _id_list(category_ids, None, "category_ids")
+    if not all(v.is_cuda for v in t) or len({v.device for v in t}) != 1:
+        raise ValueError("result must hold CUDA tensors of one device (there is no CPU fallback)")
+    return t, ids, table
+
+
+def check_confusion_limits(n_categories, max_gt_per_image):
+    """ValueError beyond what dod_coco_eval_confusion takes (include/dinodet.h)"""
+    if n_categories > MAX_CONFUSION_CATEGORIES:
+        raise ValueError(f"the confusion matrix takes at most {MAX_CONFUSION_CATEGORIES} categories, the annotations have {n_categories}")
+    if max_gt_per_image > MAX_GT_PER_IMAGE:
+        raise ValueError(f"the confusion matrix takes at most {MAX_GT_PER_IMAGE} non-crowd ground truths per image, one image has {max_gt_per_image}")
+
+
 class COCOEvaluator:
     """Holds the grouped ground truth and the appended detections in one device workspace (sized for `max_detections`)."""
 
@@ -137,6 +213,8 @@ class COCOEvaluator:
         a = self.ann
         self.I, self.K, self.G = int(a.image_ids.size), int(a.category_ids.size), int(a.gt_group.size)
         self.max_detections = int(max_detections)
+        self.max_gt_per_image = int(a.gt_per_image().max())      # what confusion_matrix checks against its limit
+        self._catmap = None
         L = nat.lib()
         nbytes = L.dod_coco_eval_workspace_bytes(self.max_detections, self.I, self.K, self.G)
         if nbytes == 0:
@@ -190,6 +268,48 @@ class COCOEvaluator:
                                         nat.ptr(ws), ws.numel(), nat.stream_ptr()))
             self._call(L.dod_coco_eval_append, nat.ptr(out), nat.ptr(count), cap)
 
+    def add_detections(self, result, image_ids, category_ids=None):
+        """result: a postprocess.Detections (so slicing.SlicedDetections / FusedDetections too) of CUDA tensors -- scores [B, Kd]
+        fp32, labels [B, Kd] int32, boxes [B, Kd, 4] fp32 pixel xyxy, counts [B] int32 -- as model.detect / detect_sliced return it;
+        image_ids: a sequence or tensor of B ids; category_ids: the table label -> annotation category id (a sequence or tensor,
+        kept on the device per evaluator), None = the label is the id.  Appends rows 0 .. counts[b]-1 of every image, images in
+        order, as xywh double records on the device (dod_coco_eval_append_detections): no host synchronisation."""
+        import torch
+        (scores, labels, boxes, counts), ids, table = check_detections(result, image_ids, category_ids)
+        B, Kd = scores.shape
+        if scores.device != self.device:
+            raise ValueError(f"result is on {scores.device}, the evaluator on {self.device}")
+        with torch.cuda.device(self.device):
+            ids_t = _ids_on(ids, self.device)
+            map_t = None if table is None else self._category_map(table)
+            scores, labels, boxes, counts = (t.contiguous() for t in (scores, labels, boxes, counts))
+            self._call(nat.lib().dod_coco_eval_append_detections, nat.ptr(boxes), nat.ptr(scores), nat.ptr(labels), nat.ptr(counts), B, Kd,
+                       nat.ptr(ids_t), nat.ptr(map_t), 0 if map_t is None else map_t.numel())
+
+    def _category_map(self, table):
+        """the label -> category id table on the evaluator's device.  A host table is uploaded once and kept until another one comes (a
+        validation loop passes the same one every batch); a tensor that is on a GPU already is the caller's own cache"""
+        if not isinstance(table, tuple):
+            return _ids_on(table, self.device)
+        if self._catmap is None or self._catmap[0] != table:
+            self._catmap = (table, _ids_on(table, self.device))
+        return self._catmap[1]
+
+    def confusion_matrix(self, score_threshold=0.25, iou_threshold=0.5):
+        """int64 numpy [K+1, K+1]: matrix[p][g] counts (predicted category index p, ground-truth category index g) pairs over the
+        appended detections with score >= score_threshold, greedily matched in score order to the non-crowd ground truths of
+        their image at IoU >= iou_threshold across categories (include/dinodet.h dod_coco_eval_confusion); index K is
+        "background": matrix[p][K] unmatched detections, matrix[K][g] missed ground truths.  Indices follow `ann.category_ids`."""
+        import torch
+        score_threshold, iou_threshold = float(score_threshold), float(iou_threshold)
+        if score_threshold != score_threshold or iou_threshold != iou_threshold:
+            raise ValueError("score_threshold and iou_threshold must not be NaN")
+        check_confusion_limits(self.K, self.max_gt_per_image)
+        with torch.cuda.device(self.device):
+            m = torch.empty((self.K + 1, self.K + 1), dtype=torch.int64, device=self.device)
+            self._call(nat.lib().dod_coco_eval_confusion, score_threshold, iou_threshold, nat.ptr(m))
+            return m.cpu().numpy()
+
     def evaluate(self):
         """{'stats': the 12 COCOeval.stats, 'precision': [10,101,K,4,3], 'recall': [10,K,4,3]} (numpy float64)"""
         import torch
@@ -230,6 +350,24 @@ def metrics_from_stats(stats):
     return {k: float(stats[i]) for i, k in enumerate(METRIC_KEYS)}
 
 
+def per_category_metrics(result, annotations):
+    """result: what COCOEvaluator.evaluate() returned; annotations: as for load_annotations.  -> {category id: {'AP', 'AP50',
+    'AR100'}}: COCOeval.summarize's rule restricted to one category -- the mean over the entries > -1 of precision[:, :, k, 0, 2]
+    (AP), precision[0, :, k, 0, 2] (AP50) and recall[:, k, 0, 2] (AR100), area range 'all' and maxDets 100; -1 when there are none.
+    Host only."""
+    ann = load_annotations(annotations)
+    prec, rec = np.asarray(result["precision"]), np.asarray(result["recall"])
+    K = int(ann.category_ids.size)
+    if prec.shape != (len(IOU_THRS), len(REC_THRS), K, 4, 3) or rec.shape != (len(IOU_THRS), K, 4, 3):
+        raise ValueError(f"precision / recall are not the arrays of an evaluation over these {K} categories")
+
+    def mean(s):
+        s = s[s > -1]
+        return -1.0 if s.size == 0 else float(np.mean(s))
+    return {int(c): {"AP": mean(prec[:, :, k, 0, 2]), "AP50": mean(prec[0, :, k, 0, 2]), "AR100": mean(rec[:, k, 0, 2])}
+            for k, c in enumerate(ann.category_ids)}
+
+
 def compute_coco_metrics(results, annotation_file):
     """Drop-in for dino_detector.utils.compute_coco_metrics (utils.py:243-276): results = the list evaluate_coco returns,
     annotation_file = the COCO ground-truth json.  Returns {'AP', 'AP50', 'AP75', 'APs', 'APm', 'APl'} as Python floats."""
@@ -238,11 +376,41 @@ def compute_coco_metrics(results, annotation_file):
     return metrics_from_stats(ev.evaluate()["stats"])
 
 
-def validate_coco(model, dataloader, device, annotations, threshold=0.05, max_detections=1 << 20):
+def validate_coco(model, dataloader, device, annotations, threshold=0.05, max_detections=1 << 20, *, detect=None, sliced=None,
+                  category_ids=None):
     """evaluate_coco + compute_coco_metrics without the host in between: forward -> add_packed per batch -> one evaluate.
-    Returns the six metrics plus 'stats' (all 12)."""
+    Returns the six metrics plus 'stats' (all 12).  That scores the reference's records: normalised boxes, the class index as id.
+    detect=dict(top_k=..., threshold=..., nms_iou=..., ...): model.detect(images, sizes=every target's 'orig_size' (height, width),
+    the input's own (H, W) where a target has none, **detect) -> add_detections per batch instead: pixel boxes, labels mapped through
+    category_ids (None = the label is the id), which is what a COCO annotation file holds.  sliced=dict(...): the loader yields
+    lists of raw uint8 [H_i, W_i, 3] images and model.detect_sliced(images, **sliced) runs instead.  These two also return
+    evaluate()'s 'precision' and 'recall'.  `threshold` is add_packed's and is not read by them."""
     import torch
+    if detect is not None and sliced is not None:
+        raise ValueError("detect= and sliced= exclude each other")
+    if detect is None and sliced is None and category_ids is not None:
+        raise ValueError("category_ids maps the labels of detect= / sliced=; without either the class index is the id")
+    for name, kw in (("detect", detect), ("sliced", sliced)):
+        if kw is not None and not isinstance(kw, dict):
+            raise ValueError(f"{name}= takes a dict of keyword arguments")
+    if detect is not None and "sizes" in detect:
+        raise ValueError("detect= takes no 'sizes': they come from every target's 'orig_size'")
+    if category_ids is not None:
+        category_ids = _id_list(category_ids, None, "category_ids")
     ev = COCOEvaluator(annotations, device, max_detections)
+    if detect is not None or sliced is not None:
+        for images, targets in dataloader:
+            ids = [i if t.get("image_id", None) is None else int(t["image_id"]) for i, t in enumerate(targets)]
+            if sliced is not None:
+                res = model.detect_sliced(images, **sliced)
+            else:
+                images = images.to(device)
+                own = (int(images.shape[-2]), int(images.shape[-1]))
+                sizes = [[float(v) for v in torch.as_tensor(t["orig_size"]).reshape(2).tolist()] if "orig_size" in t else own for t in targets]
+                res = model.detect(images, sizes=sizes, **detect)
+            ev.add_detections(res, ids, category_ids)
+        out = ev.evaluate()
+        return dict(metrics_from_stats(out["stats"]), **out)      # with 'precision' and 'recall': per_category_metrics reads them
     model.eval()
     with torch.no_grad():
         for images, targets in dataloader:

@@ -15,6 +15,12 @@
 //   accumulate  detections re-ordered by (category, score descending), stable on (image, rank); one thread per (category, area,
 //             maxDet, threshold) runs the integer cumulative sums forward (searchsorted positions) and backward (running maximum).
 //   summarize one workgroup per statistic, a fixed-order tree sum.
+//   append_detections  the fixed-shape output of dod_detect*: one workgroup per image sums the clamped counts of the images before it
+//             (the exclusive scan, as a block reduction) and writes its rows behind them; one more workgroup advances the count.
+//   confusion detections ordered by (image index, score descending, input order) with the same two sorts; one workgroup of four waves
+//             per image holds the image's non-crowd ground truths of all categories in LDS (<= 1024), walks the candidates serially
+//             and takes, lanes parallel over the ground truths, the arg-max IoU under a total order (IoU, then the later ground
+//             truth), so the reduction's shape cannot change the answer.  Counts go to the matrix by integer atomics.
 // No atomics on results, no float atomics anywhere: two evaluations of the same input are bit-identical.
 #pragma clang fp contract(off)
 #include "dod_internal.h"
@@ -35,14 +41,22 @@ constexpr int kMaxIds = 1 << 24;                  // images, categories
 constexpr int kTile = 2048;                       // keys per sort workgroup
 constexpr int kMagic = 0x0c0c0e7a;
 constexpr u64 kBits40 = ((u64)1 << 40) - 1;
+constexpr int kMaxAppendImages = 1 << 16;         // images of one append_detections call (every workgroup sums the counts before it)
+constexpr int kCfThreads = 256;                   // confusion: four waves per image
+constexpr int kCfMaxGt = 1024;                    // non-crowd ground truths per image
+constexpr int kCfSlots = kCfMaxGt / kCfThreads;   // ground truths a lane owns: g = tid + kCfThreads * slot
+constexpr int kCfMaxK = 2048;
+constexpr int kErrImage = 1, kErrScore = 2, kErrTruncated = 4, kErrLabel = 8;
 
 struct Hdr {
   i64 count;            // detections appended so far (may exceed max_dets: then evaluate refuses)
   u64 score_or;         // OR of the scores' bit patterns: its trailing zero digits are skipped by the score sorts
-  int err;              // 1 image id not in the annotations, 2 non-finite score, 4 a source buffer was truncated
+  int err;              // 1 image id not in the annotations, 2 non-finite score, 4 a source buffer was truncated, 8 a label outside its map
   int ng;               // ground-truth groups
   int magic;
   int nbig;             // ground-truth groups of more than 64
+  int max_img_gt;       // the most non-crowd ground truths one image has (all categories)
+  int reserved;
 };
 
 struct CocoDet { i64 image_id; i64 category_id; double bbox[4]; double score; };      // == dod_coco_det
@@ -54,7 +68,7 @@ __device__ __constant__ double c_area_hi[kA] = {1e10, 1024.0, 9216.0, 1e10};
 // ------------------------------------------------------------------------------------------------ workspace layout
 struct Lay {
   size_t hdr, img_ids, cat_ids, iou_thr, rec_thr, gbox, garea, gcrowd, gkey, gstart, catg, npig, dets, keyA, keyB, valA, valB, hist,
-      sidx, rank, catk, dm, dig, prec, rec, stats, total;
+      sidx, rank, catk, dm, dig, prec, rec, stats, istart, ilist, icat, total;
   int nb;
 };
 
@@ -90,6 +104,9 @@ Lay layout(i64 cap, int I, int K, i64 G) {
   L.prec = take((size_t)kT * kR * K * kA * kM * 8);
   L.rec = take((size_t)kT * K * kA * kM * 8);
   L.stats = take(12 * 8);
+  L.istart = take(((size_t)I + 1) * 4);      // per image: its non-crowd ground truths of all categories, (category index, file) order
+  L.ilist = take(g * 4);                     //   their positions in gbox
+  L.icat = take(g * 4);                      //   their category indices
   L.total = o;
   return L;
 }
@@ -234,6 +251,77 @@ __global__ void ce_bump_kernel(Hdr* hdr, const i64* __restrict__ src_count, i64 
 }
 
 __global__ void ce_reset_kernel(Hdr* hdr) { hdr->count = 0; hdr->score_or = 0; hdr->err = 0; }
+
+struct DetSrc {      // the fixed-shape output of dod_detect / dod_detect_views / dod_fuse_views
+  const float* boxes;        // [B, Kd, 4] xyxy
+  const float* scores;       // [B, Kd]
+  const int* labels;         // [B, Kd]
+  const int* counts;         // [B]
+  const i64* image_ids;      // [B]
+  const i64* map;            // [n_map] or null
+  int B, Kd, n_map;
+};
+
+__device__ __forceinline__ i64 clamped_count(int c, int Kd) { return c < 0 ? 0 : c > Kd ? Kd : c; }
+
+// sum of v over the workgroup (blockDim.x == 256), in every thread; integers, so the order is free
+__device__ __forceinline__ i64 block_sum_256(i64 v, i64* part) {
+  const int tid = threadIdx.x;
+  part[tid] = v;
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if (tid < d) part[tid] += part[tid + d];
+    __syncthreads();
+  }
+  return part[0];
+}
+
+// workgroup b: rows 0 .. counts[b]-1 of image b go behind the evaluator's records and the rows of the images before b
+__global__ __launch_bounds__(256) void ce_append_det_kernel(DetSrc p, Hdr* hdr, CocoDet* __restrict__ dets, i64 cap) {
+  __shared__ i64 part[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  i64 before = 0;
+  for (int j = tid; j < b; j += 256) before += clamped_count(p.counts[j], p.Kd);
+  before = block_sum_256(before, part);
+  const i64 have = hdr->count, base = have + before;
+  const int cnt = (int)clamped_count(p.counts[b], p.Kd);
+  const i64 img = p.image_ids[b];
+  bool bad = false;
+  for (int r = tid; r < cnt; r += 256) {
+    const size_t row = (size_t)b * p.Kd + r;
+    const int lab = p.labels[row];
+    i64 cat = lab;
+    if (p.map) {
+      if (lab < 0 || lab >= p.n_map) bad = true; else cat = p.map[lab];
+    }
+    if (have < 0 || base + r >= cap) continue;
+    const float* bx = p.boxes + row * 4;
+    const double x1 = (double)bx[0], y1 = (double)bx[1], x2 = (double)bx[2], y2 = (double)bx[3];
+    CocoDet d;
+    d.image_id = img; d.category_id = cat;
+    d.bbox[0] = x1; d.bbox[1] = y1; d.bbox[2] = x2 - x1; d.bbox[3] = y2 - y1;
+    d.score = (double)p.scores[row];
+    dets[base + r] = d;
+  }
+  if (bad) atomicOr(&hdr->err, kErrLabel);
+}
+
+__global__ __launch_bounds__(256) void ce_bump_det_kernel(Hdr* hdr, const int* __restrict__ counts, int B, int Kd) {
+  __shared__ i64 part[256];
+  i64 sum = 0, odd = 0;
+  for (int j = threadIdx.x; j < B; j += 256) {
+    const int c = counts[j];
+    sum += clamped_count(c, Kd);
+    odd += c < 0 || c > Kd;
+  }
+  sum = block_sum_256(sum, part);
+  __syncthreads();
+  odd = block_sum_256(odd, part);
+  if (threadIdx.x == 0) {
+    if (odd) hdr->err |= kErrTruncated;
+    hdr->count += sum;
+  }
+}
 
 // score keys with the input index as payload; checks image ids and scores
 __global__ __launch_bounds__(256) void ce_key_kernel(const CocoDet* __restrict__ dets, i64 n, const i64* __restrict__ img_ids, int I,
@@ -390,6 +478,108 @@ __global__ __launch_bounds__(DOD_WAVE) void ce_match_kernel(MatchArgs p) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------ confusion matrix
+// image key of the detection at each score-sorted position: the image index of a candidate (known category, score >= threshold), I for
+// the rest (an unknown image id was refused before this runs)
+__global__ __launch_bounds__(256) void ce_ikey_kernel(const CocoDet* __restrict__ dets, const unsigned* __restrict__ val, i64 n,
+                                                      const i64* __restrict__ img_ids, int I, const i64* __restrict__ cat_ids, int K,
+                                                      double score_thr, u64* __restrict__ key) {
+  const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const CocoDet* d = dets + val[j];
+  const int ii = find_id(img_ids, I, d->image_id), kk = find_id(cat_ids, K, d->category_id);
+  key[j] = ii >= 0 && kk >= 0 && d->score >= score_thr ? (u64)ii : (u64)I;
+}
+
+struct ConfArgs {
+  const CocoDet* dets;
+  const u64* skey;           // image keys, sorted
+  const unsigned* sval;      // input positions in (image, score descending, input order) order
+  i64 n;
+  const i64* cat_ids;
+  int K;
+  const int* istart;
+  const int* ilist;
+  const int* icat;
+  const double* gbox;
+  double thr;                // min(iou_threshold, 1 - 1e-10)
+  u64* matrix;               // [K+1, K+1]
+};
+
+// (v, g) beats (bv, bg): a higher IoU, or the same IoU at a later ground truth; g < 0 is "none".  A total order on distinct g, so any
+// reduction tree finds the same maximum.
+__device__ __forceinline__ bool cf_better(double v, int g, double bv, int bg) { return g >= 0 && (bg < 0 || v > bv || (v == bv && g > bg)); }
+
+// One workgroup per image.  Lane tid owns the ground truths tid + 256 * slot and keeps their taken bits in a register; the candidates
+// come 256 at a time through LDS and are matched one after the other: a wave-level butterfly, then the four waves' winners through LDS
+// (two alternating rows, so one barrier per candidate is enough).
+__global__ __launch_bounds__(kCfThreads) void ce_confusion_kernel(ConfArgs p) {
+  __shared__ double gb[kCfMaxGt][4];
+  __shared__ int gk[kCfMaxGt];
+  __shared__ double cb[kCfThreads][4];
+  __shared__ int ck[kCfThreads];
+  __shared__ double wv[2][kCfThreads / DOD_WAVE];
+  __shared__ int wg[2][kCfThreads / DOD_WAVE];
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & (DOD_WAVE - 1), wave = tid / DOD_WAVE;
+  const int g0 = p.istart[img];
+  int G = p.istart[img + 1] - g0;
+  if (G > kCfMaxGt) G = kCfMaxGt;                          // the host refuses such an image before the launch
+  for (int g = tid; g < G; g += kCfThreads) {
+    const size_t at = (size_t)p.ilist[g0 + g] * 4;
+    for (int c = 0; c < 4; ++c) gb[g][c] = p.gbox[at + c];
+    gk[g] = p.icat[g0 + g];
+  }
+  const i64 d0 = lower_bound_u64(p.skey, p.n, (u64)img), d1 = lower_bound_u64(p.skey, p.n, (u64)img + 1);
+  const size_t W = (size_t)p.K + 1;
+  unsigned taken = 0;
+  for (i64 c0 = d0; c0 < d1; c0 += kCfThreads) {
+    const int m = d1 - c0 < kCfThreads ? (int)(d1 - c0) : kCfThreads;
+    __syncthreads();                                       // the ground truths are staged; the chunk before this one is used up
+    if (tid < m) {
+      const CocoDet* r = p.dets + p.sval[c0 + tid];
+      for (int c = 0; c < 4; ++c) cb[tid][c] = r->bbox[c];
+      ck[tid] = find_id(p.cat_ids, p.K, r->category_id);
+    }
+    __syncthreads();
+    if (G == 0) {                                          // nothing to match: every candidate is left over
+      if (tid < m && ck[tid] >= 0) atomicAdd(&p.matrix[(size_t)ck[tid] * W + p.K], (u64)1);
+      continue;
+    }
+    for (int d = 0; d < m; ++d) {
+      double bv = 0.0;
+      int bg = -1;
+#pragma unroll
+      for (int s = 0; s < kCfSlots; ++s) {
+        const int g = tid + s * kCfThreads;
+        if (g < G && !((taken >> s) & 1u)) {
+          const double v = bb_iou(cb[d], gb[g], false);
+          if (v >= p.thr && cf_better(v, g, bv, bg)) { bv = v; bg = g; }
+        }
+      }
+#pragma unroll
+      for (int o = DOD_WAVE / 2; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(bv, o, DOD_WAVE);
+        const int og = __shfl_xor(bg, o, DOD_WAVE);
+        if (cf_better(ov, og, bv, bg)) { bv = ov; bg = og; }
+      }
+      const int row = d & 1;
+      if (lane == 0) { wv[row][wave] = bv; wg[row][wave] = bg; }
+      __syncthreads();
+      bv = wv[row][0]; bg = wg[row][0];
+#pragma unroll
+      for (int w = 1; w < kCfThreads / DOD_WAVE; ++w)
+        if (cf_better(wv[row][w], wg[row][w], bv, bg)) { bv = wv[row][w]; bg = wg[row][w]; }
+      if (bg >= 0 && (bg & (kCfThreads - 1)) == tid) taken |= 1u << (bg / kCfThreads);
+      if (tid == 0 && ck[d] >= 0) atomicAdd(&p.matrix[(size_t)ck[d] * W + (bg >= 0 ? gk[bg] : p.K)], (u64)1);
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < kCfSlots; ++s) {                     // the ground truths nothing took
+    const int g = tid + s * kCfThreads;
+    if (g < G && !((taken >> s) & 1u)) atomicAdd(&p.matrix[(size_t)p.K * W + gk[g]], (u64)1);
+  }
+}
+
 __global__ __launch_bounds__(256) void ce_gather_score_kernel(const CocoDet* __restrict__ dets, const int* __restrict__ sidx, i64 n,
                                                               u64* __restrict__ key, unsigned* __restrict__ val) {
   const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -495,6 +685,24 @@ int check_ws(const void* ws, size_t bytes, i64 cap, int I, int K, i64 G, Lay* L)
   return DOD_OK;
 }
 
+// what evaluate and confusion refuse from the header alone, before any launch
+int check_appended(const char* who, const Hdr& h, i64 max_dets) {
+  if (h.magic != kMagic) return fail(nullptr, DOD_ERR_STATE, "%s: dod_coco_eval_set_gt has not run on this workspace", who);
+  if (h.err & kErrTruncated)
+    return fail(nullptr, DOD_ERR_INVALID, "%s: an appended record buffer was truncated (its count exceeds its capacity)", who);
+  if (h.err & kErrLabel) return fail(nullptr, DOD_ERR_INVALID, "%s: an appended detection's label is outside its category map", who);
+  if (h.count < 0 || h.count > max_dets)
+    return fail(nullptr, DOD_ERR_INVALID, "%s: %lld detections were appended, max_dets is %lld", who, (long long)h.count, (long long)max_dets);
+  return DOD_OK;
+}
+
+// ... and from the flags ce_key_kernel leaves
+int check_keyed(const char* who, const Hdr& h) {
+  if (h.err & kErrImage) return fail(nullptr, DOD_ERR_INVALID, "%s: a detection's image id is not in the annotations", who);
+  if (h.err & kErrScore) return fail(nullptr, DOD_ERR_INVALID, "%s: a detection's score is not finite", who);
+  return DOD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -551,9 +759,29 @@ int dod_coco_eval_set_gt(void* ws, size_t ws_bytes, int64_t max_dets, int I, int
   gstart.push_back((int)G);
   for (int g = 0; g < ng; ++g) ++catg[(size_t)(gkey[g] / (u64)I) + 1];
   for (int k = 0; k < K; ++k) catg[k + 1] += catg[k];
+  // per image: its non-crowd ground truths of all categories; ascending position = (category index, file) order
+  std::vector<int> istart((size_t)I + 1, 0), ilist, icat;
+  for (i64 g = 0; g < G; ++g)
+    if (!gt_iscrowd[g]) ++istart[(size_t)(gt_group[g] % I) + 1];
+  int max_img_gt = 0;
+  for (int i = 0; i < I; ++i) {
+    if (istart[i + 1] > max_img_gt) max_img_gt = istart[i + 1];
+    istart[i + 1] += istart[i];
+  }
+  ilist.resize((size_t)istart[I]);
+  icat.resize((size_t)istart[I]);
+  {
+    std::vector<int> fill(istart.begin(), istart.end() - 1);
+    for (i64 g = 0; g < G; ++g) {
+      if (gt_iscrowd[g]) continue;
+      const int at = fill[(size_t)(gt_group[g] % I)]++;
+      ilist[at] = (int)g;
+      icat[at] = (int)(gt_group[g] / I);
+    }
+  }
   if (int rc = check_ws(ws, ws_bytes, max_dets, I, K, G, &L)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  Hdr h = {0, 0, 0, ng, kMagic, nbig};
+  Hdr h = {0, 0, 0, ng, kMagic, nbig, max_img_gt, 0};
 #define CE_UP(off, src, bytes) \
   if ((bytes) > 0) HIPCHK(nullptr, hipMemcpyAsync((char*)ws + (off), (src), (bytes), hipMemcpyHostToDevice, s))
   CE_UP(L.hdr, &h, sizeof h);
@@ -567,6 +795,9 @@ int dod_coco_eval_set_gt(void* ws, size_t ws_bytes, int64_t max_dets, int I, int
   CE_UP(L.gkey, gkey.data(), (size_t)ng * 8);
   CE_UP(L.gstart, gstart.data(), ((size_t)ng + 1) * 4);
   CE_UP(L.catg, catg.data(), ((size_t)K + 1) * 4);
+  CE_UP(L.istart, istart.data(), ((size_t)I + 1) * 4);
+  CE_UP(L.ilist, ilist.data(), ilist.size() * 4);
+  CE_UP(L.icat, icat.data(), icat.size() * 4);
 #undef CE_UP
   HIPCHK(nullptr, hipStreamSynchronize(s));               // the host vectors above go out of scope
   return DOD_OK;
@@ -613,6 +844,68 @@ int dod_coco_eval_append_host(void* ws, size_t ws_bytes, int64_t max_dets, int I
   return DOD_OK;
 }
 
+int dod_coco_eval_append_detections(void* ws, size_t ws_bytes, int64_t max_dets, int I, int K, int64_t G, const float* boxes,
+                                    const float* scores, const int32_t* labels, const int32_t* counts, int B, int Kd,
+                                    const int64_t* image_ids, const int64_t* category_map, int n_map, void* stream) {
+  Lay L;
+  if (!boxes || !scores || !labels || !counts || !image_ids)
+    return fail(nullptr, DOD_ERR_INVALID, "coco_eval_append_detections: null boxes / scores / labels / counts / image_ids");
+  if (B < 1 || B > kMaxAppendImages || Kd < 1)
+    return fail(nullptr, DOD_ERR_INVALID, "coco_eval_append_detections: need 1 <= B <= %d images and Kd >= 1 rows, got B=%d Kd=%d", kMaxAppendImages, B, Kd);
+  if (category_map && n_map < 1) return fail(nullptr, DOD_ERR_INVALID, "coco_eval_append_detections: a category map of %d entries", n_map);
+  if (int rc = check_ws(ws, ws_bytes, max_dets, I, K, G, &L)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const DetSrc src = {boxes, scores, labels, counts, (const i64*)image_ids, (const i64*)category_map, B, Kd, category_map ? n_map : 0};
+  hipLaunchKernelGGL(ce_append_det_kernel, dim3(B), dim3(256), 0, s, src, at<Hdr>(ws, L.hdr), at<CocoDet>(ws, L.dets), (i64)max_dets);
+  hipLaunchKernelGGL(ce_bump_det_kernel, dim3(1), dim3(256), 0, s, at<Hdr>(ws, L.hdr), counts, B, Kd);
+  return hipGetLastError() == hipSuccess ? DOD_OK : fail(nullptr, DOD_ERR_HIP, "coco_eval_append_detections: launch failed");
+}
+
+int dod_coco_eval_confusion(void* ws, size_t ws_bytes, int64_t max_dets, int I, int K, int64_t G, double score_threshold,
+                            double iou_threshold, int64_t* matrix, void* stream) {
+  Lay L;
+  if (!matrix) return fail(nullptr, DOD_ERR_INVALID, "coco_eval_confusion: null matrix");
+  if (score_threshold != score_threshold || iou_threshold != iou_threshold)
+    return fail(nullptr, DOD_ERR_INVALID, "coco_eval_confusion: a threshold is NaN");
+  if (int rc = check_ws(ws, ws_bytes, max_dets, I, K, G, &L)) return rc;
+  if (K > kCfMaxK) return fail(nullptr, DOD_ERR_INVALID, "coco_eval_confusion: %d categories, at most %d", K, kCfMaxK);
+  hipStream_t s = (hipStream_t)stream;
+  Hdr* hdr = at<Hdr>(ws, L.hdr);
+  Hdr h;
+  HIPCHK(nullptr, hipMemcpyAsync(&h, hdr, sizeof h, hipMemcpyDeviceToHost, s));
+  HIPCHK(nullptr, hipStreamSynchronize(s));
+  if (int rc = check_appended("coco_eval_confusion", h, max_dets)) return rc;
+  if (h.max_img_gt > kCfMaxGt)
+    return fail(nullptr, DOD_ERR_INVALID, "coco_eval_confusion: an image has %d non-crowd ground truths, at most %d", h.max_img_gt, kCfMaxGt);
+  const i64 n = h.count;
+  const CocoDet* dets = at<CocoDet>(ws, L.dets);
+  u64* k[2] = {at<u64>(ws, L.keyA), at<u64>(ws, L.keyB)};
+  unsigned* v[2] = {at<unsigned>(ws, L.valA), at<unsigned>(ws, L.valB)};
+  unsigned* hist = at<unsigned>(ws, L.hist);
+  const i64* img_ids = at<i64>(ws, L.img_ids);
+  const i64* cat_ids = at<i64>(ws, L.cat_ids);
+  const int nblk = (int)((n + 255) / 256);
+  int cur = 0;
+  if (n > 0) {      // (image index, score descending, input order): evaluate's score sort, then a stable sort on the image key
+    hipLaunchKernelGGL(ce_key_kernel, dim3(nblk), dim3(256), 0, s, dets, n, img_ids, I, k[0], v[0], hdr);
+    HIPCHK(nullptr, hipMemcpyAsync(&h, hdr, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPCHK(nullptr, hipStreamSynchronize(s));
+    if (int rc = check_keyed("coco_eval_confusion", h)) return rc;
+    const int score_b0 = h.score_or ? (__builtin_ctzll(h.score_or) / 8) * 8 : 56;
+    cur = sort_pairs(k, v, n, score_b0, 64, hist, s);
+    hipLaunchKernelGGL(ce_ikey_kernel, dim3(nblk), dim3(256), 0, s, dets, v[cur], n, img_ids, I, cat_ids, K, score_threshold, k[cur]);
+    u64* k2[2] = {k[cur], k[cur ^ 1]};
+    unsigned* v2[2] = {v[cur], v[cur ^ 1]};
+    cur ^= sort_pairs(k2, v2, n, 0, bits_for((u64)I), hist, s);
+  }
+  const size_t cells = ((size_t)K + 1) * ((size_t)K + 1);
+  HIPCHK(nullptr, hipMemsetAsync(matrix, 0, cells * 8, s));
+  const ConfArgs a = {dets, k[cur], v[cur], n, cat_ids, K, at<int>(ws, L.istart), at<int>(ws, L.ilist), at<int>(ws, L.icat),
+                      at<double>(ws, L.gbox), iou_threshold < 1 - 1e-10 ? iou_threshold : 1 - 1e-10, (u64*)matrix};
+  hipLaunchKernelGGL(ce_confusion_kernel, dim3(I), dim3(kCfThreads), 0, s, a);
+  return hipGetLastError() == hipSuccess ? DOD_OK : fail(nullptr, DOD_ERR_HIP, "coco_eval_confusion: launch failed");
+}
+
 int dod_coco_eval_evaluate(void* ws, size_t ws_bytes, int64_t max_dets, int I, int K, int64_t G, double* stats, double* precision,
                            double* recall, int64_t* n_dets, int32_t* n_groups, void* stream) {
   Lay L;
@@ -623,10 +916,7 @@ int dod_coco_eval_evaluate(void* ws, size_t ws_bytes, int64_t max_dets, int I, i
   Hdr h;
   HIPCHK(nullptr, hipMemcpyAsync(&h, hdr, sizeof h, hipMemcpyDeviceToHost, s));
   HIPCHK(nullptr, hipStreamSynchronize(s));
-  if (h.magic != kMagic) return fail(nullptr, DOD_ERR_STATE, "coco_eval_evaluate: dod_coco_eval_set_gt has not run on this workspace");
-  if (h.err & 4) return fail(nullptr, DOD_ERR_INVALID, "coco_eval_evaluate: an appended record buffer was truncated (its count exceeds its capacity)");
-  if (h.count < 0 || h.count > max_dets)
-    return fail(nullptr, DOD_ERR_INVALID, "coco_eval_evaluate: %lld detections were appended, max_dets is %lld", (long long)h.count, (long long)max_dets);
+  if (int rc = check_appended("coco_eval_evaluate", h, max_dets)) return rc;
   const i64 n = h.count;
   const CocoDet* dets = at<CocoDet>(ws, L.dets);
   u64* k[2] = {at<u64>(ws, L.keyA), at<u64>(ws, L.keyB)};
@@ -647,8 +937,7 @@ int dod_coco_eval_evaluate(void* ws, size_t ws_bytes, int64_t max_dets, int I, i
     hipLaunchKernelGGL(ce_key_kernel, dim3(nblk), dim3(256), 0, s, dets, n, img_ids, I, k[0], v[0], hdr);
     HIPCHK(nullptr, hipMemcpyAsync(&h, hdr, sizeof h, hipMemcpyDeviceToHost, s));
     HIPCHK(nullptr, hipStreamSynchronize(s));
-    if (h.err & 1) return fail(nullptr, DOD_ERR_INVALID, "coco_eval_evaluate: a detection's image id is not in the annotations");
-    if (h.err & 2) return fail(nullptr, DOD_ERR_INVALID, "coco_eval_evaluate: a detection's score is not finite");
+    if (int rc = check_keyed("coco_eval_evaluate", h)) return rc;
     score_b0 = h.score_or ? (__builtin_ctzll(h.score_or) / 8) * 8 : 56;      // digits in which every score agrees sort nothing
     cur = sort_pairs(k, v, n, score_b0, 64, hist, s);
     hipLaunchKernelGGL(ce_gkey_kernel, dim3(nblk), dim3(256), 0, s, dets, v[cur], n, img_ids, I, cat_ids, K, k[cur]);

@@ -636,12 +636,40 @@ int dod_match_assign(const float* cost, const int32_t* gt_offsets, int B, int Q,
  *                        [10,K,4,3] or NULL; n_dets / n_groups: HOST out or NULL (detections held, ground-truth groups).
  *                        Synchronises (it reads the detection count and returns the statistics).  DOD_ERR_INVALID: more than
  *                        max_dets detections were appended or a source buffer was truncated; a detection's image id is not
- *                        in image_ids; a score is not finite.  Detections of a category the annotations lack are not
+ *                        in image_ids; a score is not finite; a label of dod_coco_eval_append_detections was outside its
+ *                        category map.  Detections of a category the annotations lack are not
  *                        evaluated (COCOeval's catIds come from the ground truth).
  * dod_coco_eval_matches  after evaluate, copies out (DEVICE, each may be NULL) per sorted detection position [n_dets]: the
  *                        input index, the rank in its (image, category) group, and bit a*10+t of matched / ignored for area
  *                        range a and IoU threshold t (meaningful for rank < 100); per ground-truth group [n_groups]: its key
- *                        and the non-ignored ground truths per area range [n_groups, 4]. */
+ *                        and the non-ignored ground truths per area range [n_groups, 4].
+ * dod_coco_eval_append_detections  what dod_detect / dod_detect_views / dod_fuse_views write (all DEVICE): boxes [B,Kd,4] pixel
+ *                        xyxy, scores [B,Kd], labels [B,Kd], counts [B]; image_ids [B] int64; category_map [n_map] int64 or NULL.
+ *                        Rows 0 .. counts[b]-1 of every image are appended in (image ascending, row ascending) order -- the order
+ *                        of the host list built the same way, which the stable score sort keeps for ties -- as records with
+ *                        x = (double)x1, y = (double)y1, w = (double)x2 - (double)x1, h = (double)y2 - (double)y1, the score widened,
+ *                        category_id = category_map[label] (the label itself without a map).  Rows at and beyond counts[b] are
+ *                        never read.  Two launches on `stream` (every image's workgroup sums the counts before it; one
+ *                        workgroup advances the count), no host synchronisation, no float atomics.  Records past max_dets are
+ *                        not written and the count still grows, so evaluate refuses.  A counts[b] outside [0, Kd] contributes
+ *                        clamp(counts[b], 0, Kd) rows and evaluate / confusion report the truncated source; a label outside
+ *                        [0, n_map) with a map makes them report DOD_ERR_INVALID with a message of its own (reset clears both).
+ *                        DOD_ERR_INVALID before any launch: a NULL boxes / scores / labels / counts / image_ids, B < 1 or
+ *                        B > 65536, Kd < 1, n_map < 1 with a map.
+ * dod_coco_eval_confusion  matrix: DEVICE int64 [K+1, K+1], overwritten; matrix[p][g] counts (predicted category index p,
+ *                        ground-truth category index g) pairs at one operating point, index K standing for "background".  Per
+ *                        image of the annotations the candidates are its appended detections of a category the annotations
+ *                        hold with score >= score_threshold, in evaluate's stable (score descending, append order) order; the
+ *                        ground truths are its non-crowd ones of ALL categories in (category index, file) order.  Each
+ *                        candidate in turn takes, among the ground truths not yet taken, the one of the highest IoU (bbIou's
+ *                        non-crowd form, double) that is >= min(iou_threshold, 1 - 1e-10), the LATER one on a tie (a NaN IoU
+ *                        matches nothing): evaluateImg's greedy loop without ignore flags, across classes.  A match adds 1 to
+ *                        matrix[pred][gt], a candidate left over to matrix[pred][K], a ground truth left over to
+ *                        matrix[K][gt]; other detections and crowd ground truths appear nowhere.  Needs no evaluate before it and
+ *                        leaves a later evaluate's results (and dod_coco_eval_matches' after an earlier one) as they are.
+ *                        Synchronises (the count, then the input flags); integer atomics only.  DOD_ERR_INVALID: evaluate's
+ *                        input errors; K > 2048; an image with more than 1024 non-crowd ground truths; a NaN threshold; a NULL
+ *                        matrix. */
 typedef struct dod_coco_det {
   int64_t image_id;
   int64_t category_id;
@@ -662,6 +690,11 @@ int dod_coco_eval_evaluate(void* workspace, size_t workspace_bytes, int64_t max_
 int dod_coco_eval_matches(const void* workspace, size_t workspace_bytes, int64_t max_dets, int n_images, int n_categories, int64_t n_gt,
                           int64_t n_dets, int32_t* det_index, int32_t* det_rank, uint64_t* matched, uint64_t* ignored, int32_t n_groups,
                           uint64_t* group_keys, int32_t* npig, void* stream);
+int dod_coco_eval_append_detections(void* workspace, size_t workspace_bytes, int64_t max_dets, int n_images, int n_categories, int64_t n_gt,
+                                    const float* boxes, const float* scores, const int32_t* labels, const int32_t* counts, int B, int Kd,
+                                    const int64_t* image_ids, const int64_t* category_map, int n_map, void* stream);
+int dod_coco_eval_confusion(void* workspace, size_t workspace_bytes, int64_t max_dets, int n_images, int n_categories, int64_t n_gt,
+                            double score_threshold, double iou_threshold, int64_t* matrix, void* stream);
 
 /* Stable LSD radix sort (8-bit digits) of n <= 2^24 (64-bit key, 32-bit payload) pairs on key bits [begin_bit, end_bit), both
  * multiples of 8: equal keys keep their input order.  Sorts (keys, vals) in place; keys_alt / vals_alt [n] are scratch.
@@ -976,6 +1009,8 @@ const char* dod_version(void);
  * and the drawing entry (dod_draw_detections with its two new structs, which no earlier entry reads) and the merge of sliced
  * inference (dod_detect_views*) and its fusing form (dod_fuse_views*) and the composed canvases (dod_preprocess_compose,
  * dod_preprocess_compose_u8).
+ * dod_coco_eval_append_detections and dod_coco_eval_confusion joined revision 6 the same way; the evaluator's workspace grew with them (the
+ * per-image ground-truth lists), which a caller learns from dod_coco_eval_workspace_bytes as before.
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);

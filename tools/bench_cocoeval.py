@@ -6,8 +6,12 @@ image thresholded at 0.05 (the records dod_postprocess would emit, built here in
   dicts      the path it replaces in front of pycocotools: records -> one Python dict per detection -> json dump -> json load
   restate    tests/cocoeval_ref.py (pycocotools' loops in numpy, the yardstick) on the first --ref-images images, and the device
              on the same subset, whose precision / recall must equal the restatement's bit for bit (--ref-images 0 skips it)
+  --detections  instead of the legs above: COCOEvaluator.add_detections of a detect() result of 64 x 300 rows (hipEvent pairs, the
+             evaluator reset outside them) against the host route detections_to_list -> one dict per row -> add_records (wall clock,
+             once); and confusion_matrix(0.25, 0.5) on the whole scene, with the numpy restatement of tests/eval_detections_cases.py
+             on the first --ref-images images, which the device must equal cell for cell
 One JSON line on stdout.
-    python tools/bench_cocoeval.py [--steps 10] [--warmup 2] [--images 5000] [--ref-images 250] [--host-only]
+    python tools/bench_cocoeval.py [--steps 10] [--warmup 2] [--images 5000] [--ref-images 250] [--host-only] [--detections]
 --host-only: the dicts and restate legs without a GPU."""
 import argparse
 import json
@@ -82,6 +86,70 @@ def _device_evaluate(ds, rec, steps, warmup):
     return out, dict(_stats(ms), upload_records_s=round(upload, 4), workspace_mb=round(ev._ws.numel() / 2 ** 20, 1))
 
 
+def _timed(fn, steps, warmup, before=None):
+    """hipEvent pairs around fn() after a warm-up; before() runs outside the timed region"""
+    import torch
+    ms = []
+    for i in range(warmup + steps):
+        if before is not None:
+            before()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        fn()
+        e.record()
+        e.synchronize()
+        if i >= warmup:
+            ms.append(s.elapsed_time(e))
+    return _stats(ms)
+
+
+def _detections_leg(ds, rec, steps, warmup, ref_images, B=64, Kd=300):
+    """add_detections of a [B, Kd] detect() result against detections_to_list -> dicts -> add_records, and confusion_matrix on the
+    whole scene against the numpy restatement (tests/eval_detections_cases.py) on the first ref_images images, which must agree"""
+    import torch
+    from dinov2_od_amd import cocoeval as ce
+    from dinov2_od_amd.postprocess import Detections, detections_to_list
+    from tests import eval_detections_cases as edc
+    rng = np.random.default_rng(1)
+    ids = [im["id"] for im in ds["images"][:B]]
+    xy, wh = rng.uniform(0, 500, (B, Kd, 2)), rng.uniform(4, 140, (B, Kd, 2))
+    res = Detections(torch.from_numpy(rng.uniform(0.05, 1, (B, Kd)).astype(np.float32)).cuda(), torch.from_numpy(rng.integers(0, 80, (B, Kd)).astype(np.int32)).cuda(),
+                     torch.from_numpy(np.concatenate([xy, xy + wh], -1).astype(np.float32)).cuda(), torch.full((B, Kd), -1, dtype=torch.int32).cuda(),
+                     torch.full((B,), Kd, dtype=torch.int32).cuda())
+    table = list(range(1, 81))
+    ev = ce.COCOEvaluator(ds, max_detections=B * Kd)
+    leg = {"rows": B * Kd, "add_detections": _timed(lambda: ev.add_detections(res, ids, table), steps, warmup, before=ev.reset)}
+
+    def host_route():
+        records = []
+        for i, one in zip(ids, detections_to_list(res)):
+            for box, score, label in zip(one["boxes"].cpu().numpy().tolist(), one["scores"].cpu().numpy().tolist(), one["labels"].cpu().numpy().tolist()):
+                records.append({"image_id": i, "category_id": table[label], "bbox": [box[0], box[1], box[2] - box[0], box[3] - box[1]], "score": score})
+        ev.add_records(records)
+    ev.reset()
+    t0 = time.perf_counter()
+    host_route()
+    torch.cuda.synchronize()
+    leg["list_dicts_add_records_s"] = round(time.perf_counter() - t0, 4)
+    full = ce.COCOEvaluator(ds, max_detections=max(1, rec.size))
+    full.add_records(rec)
+    leg["confusion_matrix"] = dict(_timed(lambda: full.confusion_matrix(0.25, 0.5), steps, warmup), detections=int(rec.size),
+                                   max_gt_per_image=full.max_gt_per_image)
+    if ref_images > 0:
+        sds, srec = _subset(ds, rec, ref_images)
+        sd = records_to_coco(srec)
+        t0 = time.perf_counter()
+        want = edc.confusion_ref(sds, sd, 0.25, 0.5)
+        leg["restatement"] = {"images": ref_images, "detections": int(srec.size), "confusion_ref_s": round(time.perf_counter() - t0, 2)}
+        sub = ce.COCOEvaluator(sds, max_detections=max(1, srec.size))
+        sub.add_records(srec)
+        leg["restatement"]["confusion_matrix"] = _timed(lambda: sub.confusion_matrix(0.25, 0.5), steps, warmup)
+        same = bool(np.array_equal(sub.confusion_matrix(0.25, 0.5), want))
+        leg["restatement"]["equal"] = same
+        assert same, leg
+    return leg
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -89,11 +157,20 @@ def main():
     ap.add_argument("--images", type=int, default=5000)
     ap.add_argument("--ref-images", type=int, default=250)
     ap.add_argument("--host-only", action="store_true")
+    ap.add_argument("--detections", action="store_true")
     a = ap.parse_args()
     t0 = time.perf_counter()
     ds, rec = make_scene(a.images)
     out = {"tool": "bench_cocoeval", "images": a.images, "categories": 80, "ground_truths": len(ds["annotations"]), "detections": int(rec.size),
            "scene_build_s": round(time.perf_counter() - t0, 2), "host_only": a.host_only}
+    if a.detections:                                          # this leg alone: the evaluate legs are the default run's
+        if a.host_only:
+            raise SystemExit("--detections times device calls: it cannot run --host-only")
+        import torch
+        out["device"] = torch.cuda.get_device_name(0)
+        out["detections_leg"] = _detections_leg(ds, rec, a.steps, a.warmup, a.ref_images)
+        print(json.dumps(out))
+        return
     if not a.host_only:
         import torch
         out["device"] = torch.cuda.get_device_name(0)
