@@ -578,6 +578,38 @@ int dod_preprocess_compose_u8(const uint8_t* src, const int64_t* src_offs, const
                               const uint8_t* fills, int fill_per_canvas, int max_crop_h, int max_crop_w, int max_dw, int out_h,
                               int out_w, uint8_t* tmp, const int64_t* tmp_offs, uint8_t* out_hwc, void* stream);
 
+/* Geometric warp (random affine, perspective; Python mirror: dinov2_od_amd/augment.py warp_batch): per image b
+ *   Image.transform((out_w, out_h), PERSPECTIVE, coeffs[b], BILINEAR, fillcolor=fill)  ->  ToTensor
+ * Pillow-exact (src/libImaging/Geometry.c, generic transform + bilinear filter).  An affine is the 8 coefficients with a6 = a7 = 0: the
+ * bytes are those of Image.AFFINE.  For output pixel (x, y), a source of W x H RGB bytes p and coefficients a[0..7], all in double,
+ * one rounding per operation, no FMA contraction:
+ *   xin = x + 0.5;  yin = y + 0.5
+ *   den = a6*xin + a7*yin + 1
+ *   sx  = (a0*xin + a1*yin + a2) / den          (left to right; the division is skipped when a6 == 0 and a7 == 0: den is exactly 1)
+ *   sy  = (a3*xin + a4*yin + a5) / den
+ *   outside  <=>  not (sx >= 0.0 and sx < W and sy >= 0.0 and sy < H)     -> the pixel is the fill colour (a NaN coordinate too)
+ *   sx -= 0.5; sy -= 0.5;  ix = floor(sx); iy = floor(sy);  dx = sx - ix;  dy = sy - iy
+ *   x0 = clamp(ix, 0, W-1);  x1 = clamp(ix+1, 0, W-1);  r0 = clamp(iy, 0, H-1)
+ *   per channel:  v1 = p[r0][x0] + (p[r0][x1] - p[r0][x0]) * dx
+ *                 v2 = (0 <= iy+1 < H) ? p[iy+1][x0] + (p[iy+1][x1] - p[iy+1][x0]) * dx : v1
+ *                 byte = (uint8) (v1 + (v2 - v1) * dy)        (truncation; the value is always within [0, 255])
+ * There is no blending with the fill at the border: a pixel is either the fill or a sample with edge clamping.
+ *   src, src_offs, heights, widths: B ragged uint8 HWC sources, as in dod_preprocess (the uniform [B, h, w, 3] output of
+ *           dod_preprocess_aug_u8 / dod_preprocess_compose_u8 is src_offs[b] = b * h * w * 3).  An image with heights[b] < 1 or
+ *           widths[b] < 1 is all fill.
+ *   coeffs  double [B, 8].  Any value is safe: the coordinates become integers only after the inside test has passed.
+ *   fills   uint8 [B, 3] when fill_per_image is non-zero, else uint8 [3].
+ * One launch, no workspace, no atomics, no host synchronisation; every element of out is written exactly once and nothing else is.
+ * All pointers are device pointers.  DOD_ERR_INVALID when a pointer is missing, B <= 0, B > 65535, out_h <= 0 or out_w <= 0 (or
+ * out_h > 524 280: past one launch). */
+int dod_preprocess_warp(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
+                        const double* coeffs, const uint8_t* fills, int fill_per_image, int out_h, int out_w, float* out, void* stream);
+
+/* as dod_preprocess_warp, stopping before ToTensor: out_hwc = uint8 [B, out_h, out_w, 3], the input of dod_forward_u8 */
+int dod_preprocess_warp_u8(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
+                           const double* coeffs, const uint8_t* fills, int fill_per_image, int out_h, int out_w, uint8_t* out_hwc,
+                           void* stream);
+
 /* ---- Hungarian-matcher cost matrices on device -------------------------------------
  * Replaces the per-image cost computation of HungarianMatcher.forward, dino_detector/matching.py:79-98 (focal class
  * cost :80-86, L1 box cost :89, GIoU cost :92-95 with utils.py:124-164, weighted sum :98) for the whole batch.
@@ -1010,7 +1042,8 @@ const char* dod_version(void);
  * inference (dod_detect_views*) and its fusing form (dod_fuse_views*) and the composed canvases (dod_preprocess_compose,
  * dod_preprocess_compose_u8).
  * dod_coco_eval_append_detections and dod_coco_eval_confusion joined revision 6 the same way; the evaluator's workspace grew with them (the
- * per-image ground-truth lists), which a caller learns from dod_coco_eval_workspace_bytes as before.
+ * per-image ground-truth lists), which a caller learns from dod_coco_eval_workspace_bytes as before.  The geometric warp
+ * (dod_preprocess_warp, dod_preprocess_warp_u8) joined revision 6 by name as well.
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);
