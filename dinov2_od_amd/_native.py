@@ -175,6 +175,10 @@ SYMBOLS = {
     "dod_preprocess_compose_u8": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dod_preprocess_warp": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P]),
     "dod_preprocess_warp_u8": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P]),
+    "dod_jpeg_entropy_host": (_I, [_P, _I64, _P, _I, _I, _P, _I, _P, _I64, _P]),
+    "dod_jpeg_entropy_device": (_I, [_P, _I64, _P, _I, _P, _I, _P, _I, _P, _I64, _P, _P]),
+    "dod_jpeg_idct": (_I, [_P, _I64, _P, _I, _P, _I, _P, _P]),
+    "dod_jpeg_color": (_I, [_P, _P, _I, _I64, _P, _P]),
     "dod_match_cost": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P]),
     "dod_match_assign_workspace_bytes": (_SZ, [_I, _I, _I]),
     "dod_match_assign": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _SZ, _P]),

@@ -107,15 +107,15 @@ def augment_batch(images, targets, crops, flips, jitter=None, size=(224, 224), d
     on `device`, or with as_uint8 the uint8 [B, height, width, 3] bytes for `model.forward_packed_u8`.  Anything wrong with the
     parameters raises ValueError before anything is copied or launched."""
     out_h, out_w = _pre._out_size(size)
-    arrs = _pre._as_arrays(images)
-    B = len(arrs)
-    shapes = [a.shape[:2] for a in arrs]
+    srcs = _pre._sources(images)
+    B = len(srcs)
+    shapes = srcs.shapes
     crops, flips, jitter = _check_params(shapes, crops, flips, jitter, out_h, out_w)
     if targets is not None and len(targets) != B:
         raise ValueError(f"targets: expected {B} dicts, got {len(targets)}")
     if jitter is not None and (jitter == 1.0).all():
         jitter = None                                   # the geometric-only kernel
-    src, src_offs, hs, ws = _pre._stage(arrs, torch.device(device))
+    src, src_offs, hs, ws = srcs.stage(torch.device(device))
     out = _launch_aug(src, src_offs, hs, ws, crops, flips, jitter, out_h, out_w, as_uint8)
     new_targets = transform_targets(targets, shapes, crops, flips, (out_h, out_w), min_visibility) if targets is not None else None
     return out, new_targets
@@ -286,21 +286,21 @@ def compose_batch(images, targets, pieces, size, fill=(124, 116, 104), device="c
     `model.forward_packed_u8`; the targets as `compose_targets` documents them.  Only the sources some piece names are staged, each
     once.  Anything wrong with the arguments raises ValueError before anything is copied or launched."""
     out_h, out_w = _pre._out_size(size)
-    arrs = _pre._as_arrays(images)
-    shapes = [a.shape[:2] for a in arrs]
+    srcs = _pre._sources(images)
+    shapes = srcs.shapes
     pieces = [list(c) for c in pieces]
     rows, offs, jitter = _check_pieces(shapes, pieces, out_h, out_w)
     fill, per_canvas = _check_fill(fill, len(pieces))
-    if targets is not None and len(targets) != len(arrs):
-        raise ValueError(f"targets: expected {len(arrs)} dicts (one per source), got {len(targets)}")
+    if targets is not None and len(targets) != len(srcs):
+        raise ValueError(f"targets: expected {len(srcs)} dicts (one per source), got {len(targets)}")
     if jitter is not None and (jitter == 1.0).all():
         jitter = None                                   # the geometric-only kernels
     used = np.unique(rows[:, 0])
-    remap = np.full(len(arrs), -1, dtype=np.int32)
+    remap = np.full(len(srcs), -1, dtype=np.int32)
     remap[used] = np.arange(len(used), dtype=np.int32)
     staged = rows.copy()
     staged[:, 0] = remap[rows[:, 0]]
-    src, src_offs, hs, ws = _pre._stage([arrs[i] for i in used], torch.device(device))
+    src, src_offs, hs, ws = srcs.stage(torch.device(device), used)
     out = _launch_compose(src, src_offs, hs, ws, staged, offs, jitter, fill, per_canvas, out_h, out_w, as_uint8)
     new_targets = compose_targets(targets, shapes, pieces, (out_h, out_w), min_visibility) if targets is not None else None
     return out, new_targets
@@ -539,9 +539,9 @@ def warp_batch(images_u8, targets, coeffs, size, fill=(124, 116, 104), device="c
         B, h, w = (int(v) for v in images_u8.shape[:3])
         shapes = [(h, w)] * B
     else:
-        arrs = _pre._as_arrays(images_u8)
-        B = len(arrs)
-        shapes = [a.shape[:2] for a in arrs]
+        srcs = _pre._sources(images_u8)
+        B = len(srcs)
+        shapes = srcs.shapes
     coeffs = _check_coeffs(coeffs, shapes, out_h, out_w)
     fill, per_image = _check_fill(fill, B)
     if targets is not None and len(targets) != B:
@@ -551,7 +551,7 @@ def warp_batch(images_u8, targets, coeffs, size, fill=(124, 116, 104), device="c
         src_offs = np.arange(B, dtype=np.int64) * (h * w * 3)
         hs, ws = np.full(B, h, dtype=np.int32), np.full(B, w, dtype=np.int32)
     else:
-        src, src_offs, hs, ws = _pre._stage(arrs, torch.device(device))
+        src, src_offs, hs, ws = srcs.stage(torch.device(device))
     out = _launch_warp(src, src_offs, hs, ws, coeffs, fill, per_image, out_h, out_w, as_uint8)
     new_targets = warp_targets(targets, shapes, coeffs, (out_h, out_w), min_visibility) if targets is not None else None
     return out, new_targets
@@ -844,8 +844,8 @@ class TrainAugment:
         return [mosaic[n] if kind[n, 0] < self.mosaic_prob else zoom[n] if kind[n, 1] < self.zoom_out_prob else plain[n] for n in range(B)]
 
     def __call__(self, images, targets=None):
-        arrs = _pre._as_arrays(images)
-        shapes = [a.shape[:2] for a in arrs]
+        arrs = _pre._sources(images)
+        shapes = arrs.shapes
         warp = self.affine_prob > 0.0 or self.perspective_prob > 0.0
         as_uint8 = self.as_uint8 or warp                    # the warp reads the bytes
         if self.mosaic_prob == 0.0 and self.zoom_out_prob == 0.0:

@@ -25,6 +25,13 @@ def _staging(nbytes):
     return _STAGE
 
 
+def _staging_sent():
+    """after the last async copy out of the staging buffer has been queued: `_staging` waits for this event before the next refill"""
+    global _STAGE_BUSY
+    _STAGE_BUSY = torch.cuda.Event()
+    _STAGE_BUSY.record()
+
+
 def _as_arrays(images):
     """the batch as contiguous uint8 [H, W, 3] numpy arrays"""
     arrs = []
@@ -51,10 +58,61 @@ def _stage(arrs, dev):
     for a, o in zip(arrs, src_offs):
         sv[o:o + a.size] = a.reshape(-1)
     src = stage[:total].to(dev, non_blocking=True)
-    global _STAGE_BUSY
-    _STAGE_BUSY = torch.cuda.Event()
-    _STAGE_BUSY.record()
+    _staging_sent()
     return src, src_offs, hs, ws
+
+
+class Staged:
+    """A batch of ragged uint8 RGB sources that already sits on the device in `_stage`'s layout: `src` (uint8, the images' HWC bytes
+    back to back) with `src_offs` (int64), `heights` and `widths` (int32) on the host.  Every entry point that takes `images`
+    takes one of these instead and then copies nothing: `jpeg.decode_jpeg_batch` returns one (`DecodedBatch`)."""
+
+    def __init__(self, src, src_offs, heights, widths):
+        self.src = src
+        self.src_offs = np.ascontiguousarray(src_offs, dtype=np.int64)
+        self.heights = np.ascontiguousarray(heights, dtype=np.int32)
+        self.widths = np.ascontiguousarray(widths, dtype=np.int32)
+
+    def __len__(self):
+        return len(self.heights)
+
+    @property
+    def shapes(self):
+        return [(int(h), int(w)) for h, w in zip(self.heights, self.widths)]
+
+    def stage(self, dev, used=None):
+        """(src, src_offs, heights, widths) of the images `used` (all of them by default), as `_stage` returns them"""
+        d = torch.device(dev)
+        if d.type == "cuda" and d.index is None:
+            d = torch.device("cuda", torch.cuda.current_device())      # a bare "cuda" is where the caller's metadata will go
+        if d != self.src.device:
+            raise ValueError(f"the batch was decoded on {self.src.device}, not on {dev}")
+        if used is None:
+            return self.src, self.src_offs, self.heights, self.widths
+        return self.src, self.src_offs[used], self.heights[used], self.widths[used]
+
+
+class _HostImages:
+    """the same two questions -- shapes, stage -- for images that are still on the host"""
+
+    def __init__(self, images):
+        self.arrs = _as_arrays(images)
+
+    def __len__(self):
+        return len(self.arrs)
+
+    @property
+    def shapes(self):
+        return [a.shape[:2] for a in self.arrs]
+
+    def stage(self, dev, used=None):
+        return _stage(self.arrs if used is None else [self.arrs[i] for i in used], dev)
+
+
+def _sources(images):
+    """what an entry point does with its `images` argument: a `Staged` batch (or what an outer entry point already opened) passes
+    through, anything else is validated as host images"""
+    return images if isinstance(images, (Staged, _HostImages)) else _HostImages(images)
 
 
 def _out_size(size):
@@ -76,15 +134,15 @@ def _out_buffer(n, out_h, out_w, as_uint8, dev):
 
 
 def preprocess_batch(images, size=(224, 224), device="cuda", as_uint8=False):
-    """images: sequence of uint8 RGB images [H_i, W_i, 3] (numpy arrays, torch tensors or PIL images); size: (height, width)
-    as torchvision's Resize takes it.  Returns float32 [B, 3, height, width] on `device` -- or, with as_uint8, the resampled
+    """images: sequence of uint8 RGB images [H_i, W_i, 3] (numpy arrays, torch tensors or PIL images), or a `Staged` batch that is on
+    the device already (`jpeg.decode_jpeg_batch`); size: (height, width) as torchvision's Resize takes it.  Returns float32 [B, 3, height, width] on `device` -- or, with as_uint8, the resampled
     bytes uint8 [B, height, width, 3] (before ToTensor) for `model.forward_packed_u8`, whose patch-embedding kernel divides by 255
     in its load stage: the fp32 batch then never goes through HBM."""
     out_h, out_w = _out_size(size)
-    arrs = _as_arrays(images)
-    B = len(arrs)
+    srcs = _sources(images)
+    B = len(srcs)
     dev = torch.device(device)
-    src, src_offs, hs, ws = _stage(arrs, dev)
+    src, src_offs, hs, ws = srcs.stage(dev)
     tmp_offs, tmp_bytes = _tmp_layout(hs, out_w)
     meta = [torch.from_numpy(x).to(dev) for x in (src_offs, hs, ws, tmp_offs)]
     tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)

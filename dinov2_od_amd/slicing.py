@@ -129,14 +129,15 @@ def plan_to_device(plan, device):
 def _extract(arrs, plan, plan_dev, size, dev):
     out_h, out_w = _pre._out_size(size)
     offsets, rects = np.asarray(plan.offsets, dtype=np.int64), np.asarray(plan.rects)
+    shapes = arrs.shapes
     B, V = len(arrs), len(rects)
     if offsets.shape != (B + 1,) or offsets[0] != 0 or offsets[-1] != V or (np.diff(offsets) < 0).any():
         raise ValueError(f"plan: offsets must run from 0 to the {V} views in {B} non-decreasing steps, got {offsets.tolist()}")
     owner = np.repeat(np.arange(B), np.diff(offsets))
     if V == 0:
         return _pre._out_buffer(0, out_h, out_w, True, dev)
-    crops, flips, _ = _aug._check_params([arrs[b].shape[:2] for b in owner], rects, plan.flips, None, out_h, out_w)
-    src, src_offs, hs, ws = _pre._stage(arrs, dev)          # every source image once; its views share the offset
+    crops, flips, _ = _aug._check_params([shapes[b] for b in owner], rects, plan.flips, None, out_h, out_w)
+    src, src_offs, hs, ws = arrs.stage(dev)                 # every source image once; its views share the offset
     return _aug._launch_aug(src, src_offs[owner], hs[owner], ws[owner], crops, flips, None, out_h, out_w, True, (plan_dev.rects, plan_dev.flips))
 
 
@@ -144,7 +145,7 @@ def extract_views(images, plan, size=(224, 224), device="cuda"):
     """images: as `preprocess_batch` takes them; plan: plan_views' result for their shapes.  Returns uint8 [V, height, width, 3] on
     `device`, view v being Pillow's crop(rect) -> resize(size, BILINEAR) -> transpose(FLIP_LEFT_RIGHT) of its image, bit for bit: one
     dod_preprocess_aug_u8 call over all views.  Every source image is staged once; its views read it through the same offset."""
-    arrs = _pre._as_arrays(images)
+    arrs = _pre._sources(images)
     dev = torch.device(device)
     return _extract(arrs, plan, plan_to_device(plan, dev), size, dev)
 
@@ -216,8 +217,8 @@ def detect_views_packed(det, num_classes, plan, sizes, top_k=100, threshold=0.05
 def detect_sliced(model, images, size=None, tile=None, overlap=0.2, full_view=True, flip=False, max_batch=64, **kw):
     """DINOv2ObjectDetector.detect_sliced (models/detector.py); `model` is in eval mode and grad is off.  **kw goes to
     detect_views_packed: merge="fuse" (with nms_iou and fuse_conf) fuses the views' boxes instead of suppressing them."""
-    arrs = _pre._as_arrays(images)
-    shapes = [a.shape[:2] for a in arrs]
+    arrs = _pre._sources(images)
+    shapes = arrs.shapes
     size = _pre._out_size((224, 224) if size is None else size)
     tile = size if tile is None else tile
     max_batch = int(max_batch)

@@ -610,6 +610,49 @@ int dod_preprocess_warp_u8(const uint8_t* src, const int64_t* src_offs, const in
                            const double* coeffs, const uint8_t* fills, int fill_per_image, int out_h, int out_w, uint8_t* out_hwc,
                            void* stream);
 
+/* Baseline JPEG decode (Python mirror: dinov2_od_amd/jpeg.py decode_jpeg_batch; specification in numpy: tests/jpeg_cases.py): a batch
+ * of JPEG files as bytes -> the packed uint8 RGB sources (src, src_offs, heights, widths) every dod_preprocess* entry reads, bit for
+ * bit what libjpeg-turbo gives Pillow's Image.open(f).convert("RGB") (JDCT_ISLOW, fancy upsampling).  Streams taken: SOF0 / SOF1
+ * Huffman, 8 bits, one interleaved scan, 8-bit quantisation tables, 3 components YCbCr with luma 1x1 / 2x1 / 2x2 and chroma 1x1, or
+ * 1 component; with or without restart markers.  The header parse stays with the caller, who hands over tables of plain integers
+ * (layouts: dinov2_od_amd/csrc/jpeg_entropy.h, which a host compiler can include by itself):
+ *   images     int64 [B, 32], the DOD_JI_* row of every image: size, sampling, MCU counts, restart interval, the scan's byte range,
+ *              and per component its first block, blocks per row, plane offset, quantisation / DC / AC table, then the output offset
+ *              and the first work item of the colour stage (4 pixels of one row each; H * ceil(W / 4) per image)
+ *   intervals  int64 [V, 5]: image, byte begin and end, first MCU, MCU count of one restart interval
+ *   htabs      int32 [T, 802] Huffman tables: 9-bit look-up, largest code / symbol offset per length, symbols
+ *   qtabs      uint16 [Q, 64] quantisation tables in natural order
+ *   comps      int64 [C, 4] per component in coefficient order: first block, blocks per row, plane offset, quantisation table
+ *   coef       int16 [n_blocks, 64], natural order, 16-byte aligned; zero before the entropy stage (the device stage writes non-zero
+ *              coefficients only; the host entry zeroes its images' blocks itself)
+ *   planes     one uint8 plane per component, padded to whole blocks (8 * blocks_w bytes per row), offsets multiples of 8
+ *   status     int32 [B]: DOD_JPEG_F_* flags of a stream that ran out of bytes (1), used an undefined code (2), ran past a block's
+ *              end (4), lacked a restart marker (8), left whole bytes unread behind an interval's last MCU (32), or of a descriptor naming
+ *              a table or block outside its array (16)
+ * The entropy stage is one function, memory-safe on any bytes: reads stay inside the interval (zero bits and flag 1 behind it), every
+ * store is bounds-checked, an undefined code ends the interval.  What follows the flagged point keeps its zeros, so the pixels are
+ * a function of the bytes either way.
+ *   dod_jpeg_entropy_host    host code, no HIP call: decodes the whole scans of images [first, first + count) (restart markers
+ *                            handled) into host memory -- meant for pinned memory and one call per thread on disjoint image ranges.
+ *   dod_jpeg_entropy_device  one thread per restart interval; bytes / images / intervals / htabs / coef / status on the device.
+ *   dod_jpeg_idct            dequantise + jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2, 64-bit sums, int workspace, descale by 11
+ *                            and 18, + 128, range limit on the low 10 bits): every plane byte of every block written once.
+ *   dod_jpeg_color           h2v1 / h2v2 fancy upsampling (plain replication for a component no wider than 2 samples; the edge
+ *                            rows and columns of the ceil(W h / h_max) x ceil(H v / v_max) component replicated; block padding is
+ *                            never read) + jdcolor's 16-bit tables: R = Y + ((91881 Cr' + 32768) >> 16), B = Y + ((116130 Cb' +
+ *                            32768) >> 16), G = Y + ((-22554 Cb' + 32768 - 46802 Cr') >> 16), clamped; one component is replicated
+ *                            to R = G = B.  Every output byte of every image with work items is written exactly once, no atomics.
+ * One launch each on `stream`, no workspace, no host synchronisation.  DOD_ERR_INVALID before any launch for a NULL pointer, a
+ * non-positive count or a misaligned coef / qtabs / planes. */
+int dod_jpeg_entropy_host(const uint8_t* bytes, int64_t nbytes, const int64_t* images, int first, int count, const int32_t* htabs,
+                          int n_htabs, int16_t* coef, int64_t coef_blocks, int32_t* status);
+int dod_jpeg_entropy_device(const uint8_t* bytes, int64_t nbytes, const int64_t* images, int n_images, const int64_t* intervals,
+                            int n_intervals, const int32_t* htabs, int n_htabs, int16_t* coef, int64_t coef_blocks, int32_t* status,
+                            void* stream);
+int dod_jpeg_idct(const int16_t* coef, int64_t n_blocks, const int64_t* comps, int n_comps, const uint16_t* qtabs, int n_qtabs,
+                  uint8_t* planes, void* stream);
+int dod_jpeg_color(const uint8_t* planes, const int64_t* images, int n_images, int64_t n_items, uint8_t* out, void* stream);
+
 /* ---- Hungarian-matcher cost matrices on device -------------------------------------
  * Replaces the per-image cost computation of HungarianMatcher.forward, dino_detector/matching.py:79-98 (focal class
  * cost :80-86, L1 box cost :89, GIoU cost :92-95 with utils.py:124-164, weighted sum :98) for the whole batch.
@@ -1043,7 +1086,7 @@ const char* dod_version(void);
  * dod_preprocess_compose_u8).
  * dod_coco_eval_append_detections and dod_coco_eval_confusion joined revision 6 the same way; the evaluator's workspace grew with them (the
  * per-image ground-truth lists), which a caller learns from dod_coco_eval_workspace_bytes as before.  The geometric warp
- * (dod_preprocess_warp, dod_preprocess_warp_u8) joined revision 6 by name as well.
+ * (dod_preprocess_warp, dod_preprocess_warp_u8) joined revision 6 by name as well, and so did the JPEG decode (dod_jpeg_*).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 6
 int dod_abi_version(void);
