@@ -15,7 +15,8 @@
 // the tie rules are those of torch autograd on the reference formula (maximum / minimum of equal values: half to each
 // side; clamp(min=0) passes at 0; l1_loss: 0 where pred == target; (1 - p_t)**0 has no pow gradient).
 // The same row kernel serves FocalLoss (losses.py:9-68): match == NULL means "row r's target is labels[r]", pred_boxes ==
-// NULL skips the box terms, num_boxes == NULL normalises by 1, elem_loss / d_elem carry reduction='none'.
+// NULL skips the box terms, num_boxes == NULL normalises by 1, elem_loss / d_elem carry reduction='none': elem_loss is the
+// un-normalised term and d_elem its upstream gradient, neither divided by num_boxes (only the d_losses path is).
 // Layered form (deep supervision: `layers` decoder outputs against the same targets): rows r = (l*B + b)*Q + q, each layer has
 // its own ceil(B*Q / 16) workgroups, partials and finalize workgroup, so layer l's losses and gradients are bit-identical to
 // the single-layer call on that layer's slice; still two launches forward, one backward.
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(256) void crit_backward_kernel(CritArgs a, const fl
     const float* x = a.logits + r * a.ls;
     float* dx = d_logits + r * a.C;
     for (int c = lane; c < a.C; c += DOD_WAVE) {
-      const float up = d_elem ? d_elem[(long long)r * a.C + c] / nb : gce;
+      const float up = d_elem ? d_elem[(long long)r * a.C + c] : gce;      // elem_loss is un-normalised, so is its gradient
       dx[c] = up * focal_grad(x[c], c == tc, a.alpha, a.gamma);
     }
     if (lane == 0 && a.boxes && d_boxes) {

@@ -797,7 +797,9 @@ int dod_op_sort_pairs_u64(uint64_t* keys, uint32_t* vals, uint64_t* keys_alt, ui
  * un-normalised per-element focal term (FocalLoss reduction='none').  workspace: dod_set_criterion_workspace_bytes(B, Q, C)
  * bytes (DOD_ERR_STATE if smaller).  Two launches.
  * Backward (one launch, recomputed from the inputs): d_losses = fp32[3] upstream gradient of `losses` (weights and
- * accumulation arrive through it); d_elem (nullable, fp32 [B*Q, C]) replaces d_losses[0] element-wise (reduction='none').
+ * accumulation arrive through it) -- d_losses[i] / max(num_boxes, 1) reaches loss i's terms; d_elem (nullable, fp32 [B*Q, C]) is
+ * the upstream gradient of elem_loss and replaces d_losses[0] element-wise (reduction='none'): d_logits = d_elem * d(elem_loss),
+ * NOT divided by num_boxes, as elem_loss is not; with both given the boxes still take d_losses[1..2] / max(num_boxes, 1).
  * Writes dense d_logits fp32 [B*Q, C] and, when pred_boxes and d_boxes are given, dense d_boxes fp32 [B*Q, 4] (zero on
  * unmatched rows).  Tie rules are those of torch autograd on the reference formula.
  * DOD_ERR_INVALID: a NULL required pointer, non-positive B / Q / C, negative G, a row stride below C (logits) or 4 (boxes),

@@ -11,7 +11,7 @@ import torch
 
 from dinov2_od_amd import _native as nat, losses as L, synth
 from tests import aux_cases as ac
-from tests import cases, criterion_cases as cc
+from tests import cases, criterion_cases as cc, criterion_edge_cases as ce
 from tests.cases import rel_err, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -282,6 +282,10 @@ def test_layered_criterion_is_the_single_layer_call_per_layer(nl, B, Q, Cc):
         for mine, want, key in ((d_logits[l].cpu().numpy(), g64[:, :Cc], "dlogits"), (d_boxes[l].cpu().numpy(), g64[:, Cc:], "dboxes")):
             err, scale = np.abs(mine - want).max(), np.abs(want).max()
             assert err <= 1e-5 * scale, (l, key, err, scale)
+        # and element by element (tests/criterion_edge_cases.py)
+        flat = det_np[l].reshape(R, W)
+        ref64 = ce.reference(flat[:, :Cc], flat[:, Cc:], labels_np, gt_np, sm.cpu().numpy(), float(sum(counts)), 0.25, 2.0, d_losses=dl[l].cpu().numpy())
+        ce.check({"losses": got, "d_logits": d_logits[l].cpu().numpy(), "d_boxes": d_boxes[l].cpu().numpy()}, ref64, f"nl={nl} C={Cc} layer {l}")
     # the Python layer: packed slices are read in place, separate tensors go through one stacked copy -- same bits either way
     d = det[:nl * R].clone().view(nl, B, Q, W).requires_grad_(True)
     views = L.native_losses_layers([d[l, ..., :Cc] for l in range(nl)], [d[l, ..., Cc:] for l in range(nl)], labels, gt, match, nb)

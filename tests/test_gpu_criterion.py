@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from dinov2_od_amd import losses as L, synth
-from tests import cases, criterion_cases as cc
+from tests import cases, criterion_cases as cc, criterion_edge_cases as ce
 from tests.cases import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -52,6 +52,16 @@ def test_native_matches_reference_float64(g10, name):
         scale = np.abs(w64).max()
         print(f"{name} {key}: max|d| {err:.2e} (reference fp32 {err32:.2e}), max|g64| {scale:.2e}")
         assert err <= 1e-5 * scale or scale == 0 and err == 0, (key, err, scale)
+    # and element by element (tests/criterion_edge_cases.py); the criterion's weights are the upstream gradient and scale the losses
+    B, Q, C, counts, seed, alpha, gamma = cc.CASES[name]
+    det, labels, gt, offs = cc.inputs(name)
+    w = np.array([cc.WEIGHTS[k] for k in KEYS], np.float32)
+    ref = ce.reference(det.reshape(B * Q, -1)[:, :C], det.reshape(B * Q, -1)[:, C:], labels, gt, L.match_table(cc.indices_from(g10, name), counts, Q).numpy(),
+                       float(sum(counts)), alpha, gamma, d_losses=w)
+    ref["losses_bound"] = w * ref["losses_bound"] + ce.U * np.abs(w * ref["losses"])
+    ref["losses"] = w * ref["losses"]
+    r = ce.check({"losses": losses, "d_logits": gl.reshape(B * Q, C), "d_boxes": gb.reshape(B * Q, 4)}, ref, name)
+    print(f"{name} worst error / bound per element: {ce.fmt(r)}")
 
 
 def _synthetic(B, Q, C, seed):
@@ -85,6 +95,10 @@ def test_native_matches_composite_float64_at_training_shapes(B, Q, C):
         err, scale = np.abs(g32[sl] - g64[sl]).max(), np.abs(g64[sl]).max()
         print(f"B={B} Q={Q} {key}: max|d| {err:.2e}, max|g64| {scale:.2e}")
         assert err <= 1e-5 * scale, key
+    ref = ce.reference(det.reshape(B * Q, -1)[:, :C], det.reshape(B * Q, -1)[:, C:], labels, gt, match.numpy(), float(sum(counts)), 0.25, 2.0,
+                       d_losses=np.array([1.0, 5.0, 2.0], np.float32))
+    r = ce.check({"losses": gr, "d_logits": g32[..., :C].reshape(B * Q, C), "d_boxes": g32[..., C:].reshape(B * Q, 4)}, ref, f"B={B} Q={Q}")
+    print(f"B={B} Q={Q} worst error / bound per element: {ce.fmt(r)}")
 
 
 def _packed_run(det, C, labels, gt, match, nb, views, scale=1.0):
@@ -158,6 +172,14 @@ def test_focal_loss_on_the_criterion_kernel(reduction):
     (got * up.float().to(_dev())).sum().backward()
     assert rel_err(got.detach().cpu().numpy(), want.detach().numpy()) < 1e-5
     assert rel_err(xg.grad.cpu().numpy(), xc.grad.numpy()) < 1e-5
+    # element by element: row r's target is t[r]; 'none' is elem_loss / d_elem, 'mean' is num_boxes = N C, 'sum' is num_boxes = NULL
+    up32 = up.float().numpy()
+    none = reduction == "none"
+    ref = ce.reference(x.numpy(), None, t.numpy(), np.zeros((0, 4), np.float32), np.arange(300), 300.0 * 91 if reduction == "mean" else None, 0.25, 2.0,
+                       d_losses=None if none else np.array([up32, 0, 0], np.float32), d_elem=up32 if none else None)
+    mine = {"elem": got.detach().cpu().numpy()} if none else {"losses": np.array([float(got.detach()), 0.0, 0.0])}
+    r = ce.check(dict(mine, d_logits=xg.grad.cpu().numpy()), ref, f"FocalLoss {reduction}")
+    print(f"FocalLoss {reduction} worst error / bound per element: {ce.fmt(r)}")
     with pytest.raises(RuntimeError):
         L.FocalLoss()(xg, torch.full((300,), 91, device=_dev()))
 
