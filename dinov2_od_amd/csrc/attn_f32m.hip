@@ -11,6 +11,7 @@
 //                                              each half -- the contraction order over keys is free, so no shuffle is needed
 // 128 MFMAs x 64 cycles per tile and wave: MFMA-bound (fp32 MFMA peak 157 TFLOP/s); softmax statistics per lane (= per query).
 #include "dod_common.h"
+#include "operand_rows.h"
 
 #define FM_KV 64
 #define FM_LDK 97     // K^T rows [d][key]: odd pitch -> conflict-free transposing ds_write_b32; the two lane halves (d, d+1) land 33 banks apart
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32m_kernel(AttnF32 a) {
             make_float4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
     if (a.o3) {          // the same values as the bf16x3 operand [hi | hi | lo] of the next query-side linear
       const int Dm = a.heads * DH;
-      bf16_t* o3 = a.o3 + ((size_t)b * a.Lq + q) * 3 * Dm + h * DH;
+      bf16_t* o3 = a.o3 + ((size_t)b * a.Lq + q) * 3 * Dm;
 #pragma unroll
       for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -148,14 +149,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32m_kernel(AttnF32 a) {
           // subtraction as an fma and split a different number than split3 of the stored output does)
           float y0 = o[db][4 * g] * inv, y1 = o[db][4 * g + 1] * inv, y2 = o[db][4 * g + 2] * inv, y3 = o[db][4 * g + 3] * inv;
           asm volatile("" : "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3));
-          uint2 hi, lo;
-          hi.x = pack2bf(y0, y1); hi.y = pack2bf(y2, y3);
-          lo.x = pack2bf(y0 - __uint_as_float(hi.x << 16), y1 - __uint_as_float(hi.x & 0xffff0000u));
-          lo.y = pack2bf(y2 - __uint_as_float(hi.y << 16), y3 - __uint_as_float(hi.y & 0xffff0000u));
-          bf16_t* d = o3 + db * 32 + 8 * g + 4 * lh;
-          *reinterpret_cast<uint2*>(d) = hi;
-          *reinterpret_cast<uint2*>(d + Dm) = hi;
-          *reinterpret_cast<uint2*>(d + 2 * Dm) = lo;
+          row_store_s3x4(o3, h * DH + db * 32 + 8 * g + 4 * lh, Dm, make_float4(y0, y1, y2, y3));
         }
     }
   }

@@ -10,6 +10,7 @@
 // K/V tiles of 64 keys (four planes: Kh, Kl, Vh, Vl = 32 KiB) stream by LDS-DMA into TWO slots (64 KiB, two workgroups
 // per CU): tile t+1 is in flight while tile t is computed; same swizzles, query-on-lane products, tr-reads for V^T.
 #include "dod_common.h"
+#include "operand_rows.h"
 
 #define X3_WAVES 4
 #define X3_KV 64
@@ -99,14 +100,7 @@ __device__ __forceinline__ void x3_tile(const char* st, const bf16x8 (&qh)[4], c
     const f32x16& pp = s[s4 >> 1];
     const int u = (s4 & 1) * 8;
     uint4 hi, lo;
-    hi.x = pack2bf(pp[u + 0], pp[u + 1]);
-    hi.y = pack2bf(pp[u + 2], pp[u + 3]);
-    hi.z = pack2bf(pp[u + 4], pp[u + 5]);
-    hi.w = pack2bf(pp[u + 6], pp[u + 7]);
-    lo.x = pack2bf(pp[u + 0] - __uint_as_float(hi.x << 16), pp[u + 1] - __uint_as_float(hi.x & 0xffff0000u));
-    lo.y = pack2bf(pp[u + 2] - __uint_as_float(hi.y << 16), pp[u + 3] - __uint_as_float(hi.y & 0xffff0000u));
-    lo.z = pack2bf(pp[u + 4] - __uint_as_float(hi.z << 16), pp[u + 5] - __uint_as_float(hi.z & 0xffff0000u));
-    lo.w = pack2bf(pp[u + 6] - __uint_as_float(hi.w << 16), pp[u + 7] - __uint_as_float(hi.w & 0xffff0000u));
+    bf16_split8(make_float4(pp[u + 0], pp[u + 1], pp[u + 2], pp[u + 3]), make_float4(pp[u + 4], pp[u + 5], pp[u + 6], pp[u + 7]), hi, lo);
     ph[s4] = __builtin_bit_cast(bf16x8, hi);
     pl[s4] = __builtin_bit_cast(bf16x8, lo);
   }
@@ -221,37 +215,18 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(const bf16_t* __restric
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = 1.0f / l_tot;
   const int q = q0 + lr;
-  if (active && q < N && ctx_h2) {       // H2 operand rows for the out-proj of the fp16x2 mode (dod_common.h)
-    char* row = reinterpret_cast<char*>(ctx3) + ((size_t)b * N + q) * 4 * D;
+  bf16_t* row = ctx3 + ((size_t)b * N + q) * 2 * D;      // pair layout, pitch 2*D; ctx_h2: H2 operand rows for the out-proj of the fp16x2 mode (4*D bytes)
+  auto quad = [&](int db, int g) { return make_float4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv); };
+  if (active && q < N && ctx_h2) {
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 v = make_float4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
-        uint2 f16; unsigned hi8, lo8;
-        h2_quad(v, 1.0f, f16, hi8, lo8);
-        const int c = h * 64 + db * 32 + 8 * g + 4 * lh;
-        *reinterpret_cast<uint2*>(row + 2 * c) = f16;
-        char* p8 = row + h2_off8(D, c);
-        *reinterpret_cast<unsigned*>(p8) = hi8;
-        *reinterpret_cast<unsigned*>(p8 + 16) = lo8;
-      }
+      for (int g = 0; g < 4; ++g) row_store_h2x4(row, D, h * 64 + db * 32 + 8 * g + 4 * lh, quad(db, g));
   } else if (active && q < N) {
-    bf16_t* op = ctx3 + ((size_t)b * N + q) * 2 * D + h * 64;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float v0 = o[db][4 * g] * inv, v1 = o[db][4 * g + 1] * inv, v2 = o[db][4 * g + 2] * inv, v3 = o[db][4 * g + 3] * inv;
-        uint2 hi, lo;
-        hi.x = pack2bf(v0, v1);
-        hi.y = pack2bf(v2, v3);
-        lo.x = pack2bf(v0 - __uint_as_float(hi.x << 16), v1 - __uint_as_float(hi.x & 0xffff0000u));
-        lo.y = pack2bf(v2 - __uint_as_float(hi.y << 16), v3 - __uint_as_float(hi.y & 0xffff0000u));
-        bf16_t* p = op + db * 32 + 8 * g + 4 * lh;
-        *reinterpret_cast<uint2*>(p) = hi;
-        *reinterpret_cast<uint2*>(p + D) = lo;
-      }
+      for (int g = 0; g < 4; ++g) row_store_pair4(row, h * 64 + db * 32 + 8 * g + 4 * lh, D, quad(db, g));
   }
 }
 

@@ -11,6 +11,7 @@
 // proj row layout (one small fused GEMM): [ref logit x, ref logit y | Hd*P*2 offsets | Hd*P weight logits].
 // One wave per (b, q, head); lanes run along the head's dh value columns (coalesced row reads of V).
 #include "dod_common.h"
+#include "operand_rows.h"
 
 #define DF_MAXP 8
 
@@ -75,9 +76,9 @@ __global__ __launch_bounds__(256) void deform_sample_kernel(const float* __restr
   if (d0ok) op[lane] = acc0;
   if (d1ok) op[lane + 64] = acc1;
   if (out3) {        // the same values as the bf16x3 operand [hi | hi | lo] of the output projection (K17)
-    bf16_t* o3 = out3 + (size_t)bq * 3 * Dd + hd * dh;
-    if (d0ok) { const bf16_t hi = f2bf(acc0); o3[lane] = hi; o3[Dd + lane] = hi; o3[2 * Dd + lane] = f2bf(acc0 - bf2f(hi)); }
-    if (d1ok) { const bf16_t hi = f2bf(acc1); o3[lane + 64] = hi; o3[Dd + lane + 64] = hi; o3[2 * Dd + lane + 64] = f2bf(acc1 - bf2f(hi)); }
+    bf16_t* o3 = out3 + (size_t)bq * 3 * Dd;
+    if (d0ok) row_store_s3x1(o3, hd * dh + lane, Dd, acc0);
+    if (d1ok) row_store_s3x1(o3, hd * dh + lane + 64, Dd, acc1);
   }
 }
 

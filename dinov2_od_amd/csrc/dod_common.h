@@ -106,21 +106,10 @@ __device__ __forceinline__ size_t mx_scale_off(int K, int bi) { return (size_t)(
 //     the per-CU global->LDS path, which -- not the MFMAs -- paces this kernel).  The activations keep their e4m3(h) bytes: that
 //     conversion turns |h| > 464 into NaN (no saturating form exists), so it needs the producer's clamp.
 // Values are clamped to the fp16 / e4m3 finite ranges (|x| <= 65504; beyond it the mode degrades, it does not overflow).
+// The writers of both row forms: operand_rows.h.
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 __device__ __forceinline__ float clampf_(float v, float lim) { return __builtin_fminf(__builtin_fmaxf(v, -lim), lim); }
-// four values -> fp16 (2 dwords), e4m3 of the fp16 value times 2^ehi and of the remainder times 2^(ehi + 11) (one dword each)
-__device__ __forceinline__ void h2_quad(float4 v, float shi, uint2& f16, unsigned& hi8, unsigned& lo8) {
-  v.x = clampf_(v.x, 65504.f); v.y = clampf_(v.y, 65504.f); v.z = clampf_(v.z, 65504.f); v.w = clampf_(v.w, 65504.f);
-  const f16x2 p0 = {(_Float16)v.x, (_Float16)v.y}, p1 = {(_Float16)v.z, (_Float16)v.w};
-  f16.x = __builtin_bit_cast(unsigned, p0); f16.y = __builtin_bit_cast(unsigned, p1);
-  const float hx = (float)p0.x, hy = (float)p0.y, hz = (float)p1.x, hw = (float)p1.y;
-  const float slo = shi * 2048.0f;
-  hi8 = pack4_fp8(clampf_(hx * shi, 448.f), clampf_(hy * shi, 448.f), clampf_(hz * shi, 448.f), clampf_(hw * shi, 448.f));
-  lo8 = pack4_fp8(clampf_((v.x - hx) * slo, 448.f), clampf_((v.y - hy) * slo, 448.f), clampf_((v.z - hz) * slo, 448.f), clampf_((v.w - hw) * slo, 448.f));
-}
-// byte offset of the e4m3(h) bytes of column c (c % 4 == 0) inside an H2 activation row of K elements; the remainder bytes follow 16 bytes on
-__device__ __forceinline__ size_t h2_off8(int K, int c) { return (size_t)2 * K + (size_t)(c >> 4) * 32 + (c & 15); }
 
 // exact-erf GELU (HF ACT2FN["gelu"], modeling_dinov2.py:288-296)
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }

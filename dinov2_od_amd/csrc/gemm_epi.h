@@ -1,6 +1,7 @@
 // Shared GEMM epilogue (bf16 and fp8 MFMA kernels): accumulators -> LDS tile -> whole-row HBM stores.
 #pragma once
 #include "dod_common.h"
+#include "operand_rows.h"
 
 // 64-byte LDS rows read by 32-row MFMA lane groups: 16-B chunk ^= (row >> 2) & 3 (conflict-free ds_read_b128)
 __device__ __forceinline__ int swz64(int row, int chunk) { return chunk ^ ((row >> 2) & 3); }
@@ -166,27 +167,10 @@ __device__ __forceinline__ float half32_sum_hi(float v) {
 }
 // the new residual row in the operand format of the GEMM that reads it next (GemmEpi::ln_op; the writers of rowops.hip's LayerNorm)
 __device__ __forceinline__ void ln_store_op(const GemmEpi& e, size_t m, int n, int N, const float4& v) {
-  if (e.ln_op_kind == LNOP_H2) {
-    uint2 f16; unsigned hi8, lo8;
-    h2_quad(v, 1.0f, f16, hi8, lo8);
-    char* row = reinterpret_cast<char*>(e.ln_op) + m * (size_t)e.ln_op_ld * 2;
-    *reinterpret_cast<uint2*>(row + 2 * n) = f16;
-    char* p8 = row + h2_off8(N, n);
-    *reinterpret_cast<unsigned*>(p8) = hi8;
-    *reinterpret_cast<unsigned*>(p8 + 16) = lo8;
-    return;
-  }
-  uint2 hi;
-  hi.x = pack2bf(v.x, v.y);
-  hi.y = pack2bf(v.z, v.w);
-  bf16_t* o = reinterpret_cast<bf16_t*>(e.ln_op) + m * (size_t)e.ln_op_ld + n;
-  *reinterpret_cast<uint2*>(o) = hi;
-  if (e.ln_op_kind == LNOP_PAIR) {
-    uint2 lo;
-    lo.x = pack2bf(v.x - __uint_as_float(hi.x << 16), v.y - __uint_as_float(hi.x & 0xffff0000u));
-    lo.y = pack2bf(v.z - __uint_as_float(hi.y << 16), v.w - __uint_as_float(hi.y & 0xffff0000u));
-    *reinterpret_cast<uint2*>(o + (e.ln_op_ld >> 1)) = lo;
-  }
+  bf16_t* row = reinterpret_cast<bf16_t*>(e.ln_op) + m * (size_t)e.ln_op_ld;      // every kind: ln_op_ld 2-byte units per row
+  if (e.ln_op_kind == LNOP_H2) { row_store_h2x4(row, N, n, v); return; }
+  const uint2 hi = row_store_bf16x4(row, n, v);
+  if (e.ln_op_kind == LNOP_PAIR) row_store_pair_lo4(row, n, e.ln_op_ld >> 1, v, hi);
 }
 
 // LNF: the folded-LayerNorm producer (GemmEpi::ln_part): every lane stays in the loop (columns n >= N contribute nothing) because the row
@@ -296,48 +280,42 @@ __device__ __forceinline__ void drain_tile(const char* sm, int pitch, const Gemm
     }
     if (e.out_f32) {
       *reinterpret_cast<float4*>(e.out_f32 + orow * e.ldc + n) = v;
-    } else if (e.glu) {             // interleaved SwiGLU pairs: columns n .. n+3 = (x1, x2, x1, x2) -> two gated outputs at column n / 2
-      const float g0 = silu_mul(v.x, v.y), g1 = silu_mul(v.z, v.w);         // (H2 rows need whole quads: launchers route them to drain_tile_bf16x8)
-      const unsigned hi = pack2bf(g0, g1);
-      bf16_t* og = e.out_bf16 + orow * e.ldc + (n >> 1);
-      *reinterpret_cast<unsigned*>(og) = hi;
-      if (e.out_split < 0) *reinterpret_cast<unsigned*>(og - e.out_split) = pack2bf(g0 - __uint_as_float(hi << 16), g1 - __uint_as_float(hi & 0xffff0000u));
-    } else if (e.out_h2) {          // H2 operand row of the next GEMM (dod_common.h)
-      uint2 f16; unsigned hi8, lo8;
-      h2_quad(v, 1.0f, f16, hi8, lo8);
-      char* row = reinterpret_cast<char*>(e.out_bf16) + orow * (size_t)e.ldc * 2;
-      *reinterpret_cast<uint2*>(row + 2 * n) = f16;
-      char* p8 = row + h2_off8(N, n);
-      *reinterpret_cast<unsigned*>(p8) = hi8;
-      *reinterpret_cast<unsigned*>(p8 + 16) = lo8;
-    } else if (e.out_split > 0) {   // bf16x3 activation operand of the next GEMM: [hi | hi | lo]
-      uint2 hi, lo;
-      hi.x = pack2bf(v.x, v.y);
-      hi.y = pack2bf(v.z, v.w);
-      lo.x = pack2bf(v.x - __uint_as_float(hi.x << 16), v.y - __uint_as_float(hi.x & 0xffff0000u));
-      lo.y = pack2bf(v.z - __uint_as_float(hi.y << 16), v.w - __uint_as_float(hi.y & 0xffff0000u));
-      bf16_t* o = e.out_bf16 + orow * e.ldc + n;
-      *reinterpret_cast<uint2*>(o) = hi;
-      *reinterpret_cast<uint2*>(o + e.out_split) = hi;
-      *reinterpret_cast<uint2*>(o + 2 * (size_t)e.out_split) = lo;
-    } else if (e.out_split < 0) {   // pair layout [hi | lo] (attention input of the bf16x3 mode)
-      uint2 hi, lo;
-      hi.x = pack2bf(v.x, v.y);
-      hi.y = pack2bf(v.z, v.w);
-      lo.x = pack2bf(v.x - __uint_as_float(hi.x << 16), v.y - __uint_as_float(hi.x & 0xffff0000u));
-      lo.y = pack2bf(v.z - __uint_as_float(hi.y << 16), v.w - __uint_as_float(hi.y & 0xffff0000u));
-      bf16_t* o = e.out_bf16 + orow * e.ldc + n;
-      *reinterpret_cast<uint2*>(o) = hi;
-      *reinterpret_cast<uint2*>(o - e.out_split) = lo;
-    } else {
-      uint2 o;
-      o.x = pack2bf(v.x, v.y);
-      o.y = pack2bf(v.z, v.w);
-      *reinterpret_cast<uint2*>(e.out_bf16 + orow * e.ldc + n) = o;
+      continue;
     }
+    bf16_t* row = e.out_bf16 + orow * e.ldc;      // ldc: 2-byte units in every format (operand_rows.h)
+    if (e.glu) {                    // interleaved SwiGLU pairs: columns n .. n+3 = (x1, x2, x1, x2) -> two gated outputs at column n / 2
+      const float g0 = silu_mul(v.x, v.y), g1 = silu_mul(v.z, v.w);         // (H2 rows need whole quads: launchers route them to drain_tile_bf16x8)
+      const uint32_t hi = row_store_bf16x2(row, n >> 1, g0, g1);
+      if (e.out_split < 0) row_store_pair_lo2(row, n >> 1, -e.out_split, g0, g1, hi);
+    } else if (e.out_h2) row_store_h2x4(row, N, n, v);                          // H2 operand row of the next GEMM
+    else if (e.out_split > 0) row_store_s3x4(row, n, e.out_split, v);           // bf16x3 activation operand of the next GEMM: [hi | hi | lo]
+    else if (e.out_split < 0) row_store_pair4(row, n, -e.out_split, v);         // pair layout [hi | lo] (attention input of the bf16x3 mode)
+    else row_store_bf16x4(row, n, v);
   }
 }
 
+// The elementwise arithmetic of the bf16-row epilogues on one column quad -- the staged drain_tile_bf16x8 and the register epilogue
+// (epi_quad_bf16) run this one statement of it, so their outputs are bit-identical.  b = the bias; LN_CONS: c = the column sums, t = -mean rstd,
+// rs = rstd of the quad's row: rstd acc + (b' - mean rstd c), two packed FMAs per pair where the plain epilogue has one packed add;
+// otherwise c = the LayerScale (t, rs unused).
+template <int LN>
+__device__ __forceinline__ void epi_math4(float4& v, const float4& c, const float4& b, float t, float rs, int act) {
+  if (LN == LN_CONS) {
+    const f32x2_t t2 = (f32x2_t)(t), rs2 = (f32x2_t)(rs);
+    const f32x2_t c0 = {c.x, c.y}, c1 = {c.z, c.w}, b0 = {b.x, b.y}, b1 = {b.z, b.w}, a0 = {v.x, v.y}, a1 = {v.z, v.w};
+    const f32x2_t o0 = __builtin_elementwise_fma(a0, rs2, __builtin_elementwise_fma(t2, c0, b0));
+    const f32x2_t o1 = __builtin_elementwise_fma(a1, rs2, __builtin_elementwise_fma(t2, c1, b1));
+    v = make_float4(o0.x, o0.y, o1.x, o1.y);
+  } else {
+    v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
+  }
+  if (act == ACT_GELU) {
+    gelu_fast4(v);
+  } else if (act == ACT_RELU) {
+    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+  }
+  if (LN != LN_CONS) { v.x *= c.x; v.y *= c.y; v.z *= c.z; v.w *= c.w; }
+}
 
 // bf16 outputs without residual / row remap (QKV, fc1; plain or pair layout): EIGHT columns per lane -- one 16-byte store per lane
 // and row instead of two 8-byte ones: the store tail of a tile is bound by the number of store instructions, not by their bytes
@@ -364,79 +342,25 @@ __device__ __forceinline__ void drain_tile_bf16x8(const char* sm, int pitch, con
     if (m >= M) continue;
     float4 v = *reinterpret_cast<const float4*>(sm + row_l * pitch + c8 * 32);
     float4 u = *reinterpret_cast<const float4*>(sm + row_l * pitch + c8 * 32 + 16);
-    if (ln) {                     // rstd acc + (b' - mean rstd c): two packed FMAs per pair where the plain epilogue has one packed add
+    float t = 0.f, rs = 0.f;
+    if (ln) {
       const float2 st = *reinterpret_cast<const float2*>(sm + row_l * pitch + COLS * 4);      // stage_row_stats
-      const f32x2_t t = (f32x2_t)(-st.x * st.y), rs = (f32x2_t)(st.y);
-#define LN_PAIR_(va, vb, ca, cb, ba, bb)                                                                         \
-      { const f32x2_t c_ = {ca, cb}, b_ = {ba, bb}, a_ = {va, vb};                                                \
-        const f32x2_t o_ = __builtin_elementwise_fma(a_, rs, __builtin_elementwise_fma(t, c_, b_));               \
-        va = o_.x; vb = o_.y; }
-      LN_PAIR_(v.x, v.y, s0.x, s0.y, b0.x, b0.y) LN_PAIR_(v.z, v.w, s0.z, s0.w, b0.z, b0.w)
-      LN_PAIR_(u.x, u.y, s1.x, s1.y, b1.x, b1.y) LN_PAIR_(u.z, u.w, s1.z, s1.w, b1.z, b1.w)
-#undef LN_PAIR_
-    } else {
-      v.x += b0.x; v.y += b0.y; v.z += b0.z; v.w += b0.w;
-      u.x += b1.x; u.y += b1.y; u.z += b1.z; u.w += b1.w;
+      t = -st.x * st.y; rs = st.y;
     }
-    if (e.act == ACT_GELU) {
-      gelu_fast4(v); gelu_fast4(u);
-    } else if (e.act == ACT_RELU) {
-      v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-      u.x = fmaxf(u.x, 0.f); u.y = fmaxf(u.y, 0.f); u.z = fmaxf(u.z, 0.f); u.w = fmaxf(u.w, 0.f);
-    }
-    if (!ln) {
-      v.x *= s0.x; v.y *= s0.y; v.z *= s0.z; v.w *= s0.w;
-      u.x *= s1.x; u.y *= s1.y; u.z *= s1.z; u.w *= s1.w;
-    }
+    // ONE branch on the activation per row, not one per quad (operand_rows.h has the measurement)
+    auto both = [&](int act) { epi_math4<LN>(v, s0, b0, t, rs, act); epi_math4<LN>(u, s1, b1, t, rs, act); };
+    if (e.act == ACT_GELU) both(ACT_GELU); else if (e.act == ACT_RELU) both(ACT_RELU); else both(ACT_NONE);
+    bf16_t* row = e.out_bf16 + (size_t)m * e.ldc;      // ldc: 2-byte units in every format (operand_rows.h)
     if (e.glu) {                    // interleaved SwiGLU pairs: eight columns -> four gated outputs at column n / 2 of an N / 2-column row
       const float4 gq = make_float4(silu_mul(v.x, v.y), silu_mul(v.z, v.w), silu_mul(u.x, u.y), silu_mul(u.z, u.w));
-      const int nh = n >> 1;
-      if (e.out_h2) {               // H2 operand row (fp16x2 mode)
-        uint2 f16; unsigned hi8, lo8;
-        h2_quad(gq, 1.0f, f16, hi8, lo8);
-        char* row = reinterpret_cast<char*>(e.out_bf16) + (size_t)m * e.ldc * 2;
-        *reinterpret_cast<uint2*>(row + 2 * nh) = f16;
-        char* p8 = row + h2_off8(N >> 1, nh);
-        *reinterpret_cast<unsigned*>(p8) = hi8;
-        *reinterpret_cast<unsigned*>(p8 + 16) = lo8;
-        continue;
-      }
-      uint2 g;
-      g.x = pack2bf(gq.x, gq.y);
-      g.y = pack2bf(gq.z, gq.w);
-      bf16_t* og = e.out_bf16 + (size_t)m * e.ldc + nh;
-      *reinterpret_cast<uint2*>(og) = g;
-      if (e.out_split < 0) {        // pair layout [hi | lo] (bf16x3 mode), each half -out_split columns wide
-        uint2 lo;
-        lo.x = pack2bf(gq.x - __uint_as_float(g.x << 16), gq.y - __uint_as_float(g.x & 0xffff0000u));
-        lo.y = pack2bf(gq.z - __uint_as_float(g.y << 16), gq.w - __uint_as_float(g.y & 0xffff0000u));
-        *reinterpret_cast<uint2*>(og - e.out_split) = lo;
-      }
+      if (e.out_h2) { row_store_h2x4(row, N >> 1, n >> 1, gq); continue; }     // fp16x2 mode
+      const uint2 g = row_store_bf16x4(row, n >> 1, gq);
+      if (e.out_split < 0) row_store_pair_lo4(row, n >> 1, -e.out_split, gq, g);  // bf16x3 mode
       continue;
     }
-    if (e.out_h2) {                 // H2 operand row of the next GEMM (dod_common.h): 16 B of fp16, 8 + 8 B of e4m3
-      uint2 fa, fb; unsigned h0, l0, h1, l1;
-      h2_quad(v, 1.0f, fa, h0, l0);
-      h2_quad(u, 1.0f, fb, h1, l1);
-      char* row = reinterpret_cast<char*>(e.out_bf16) + (size_t)m * e.ldc * 2;
-      *reinterpret_cast<uint4*>(row + 2 * n) = make_uint4(fa.x, fa.y, fb.x, fb.y);
-      char* p8 = row + h2_off8(N, n);
-      *reinterpret_cast<uint2*>(p8) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(p8 + 16) = make_uint2(l0, l1);
-      continue;
-    }
-    uint4 hi;
-    hi.x = pack2bf(v.x, v.y); hi.y = pack2bf(v.z, v.w); hi.z = pack2bf(u.x, u.y); hi.w = pack2bf(u.z, u.w);
-    bf16_t* o = e.out_bf16 + (size_t)m * e.ldc + n;
-    *reinterpret_cast<uint4*>(o) = hi;
-    if (e.out_split < 0) {       // pair layout [hi | lo]
-      uint4 lo;
-      lo.x = pack2bf(v.x - __uint_as_float(hi.x << 16), v.y - __uint_as_float(hi.x & 0xffff0000u));
-      lo.y = pack2bf(v.z - __uint_as_float(hi.y << 16), v.w - __uint_as_float(hi.y & 0xffff0000u));
-      lo.z = pack2bf(u.x - __uint_as_float(hi.z << 16), u.y - __uint_as_float(hi.z & 0xffff0000u));
-      lo.w = pack2bf(u.z - __uint_as_float(hi.w << 16), u.w - __uint_as_float(hi.w & 0xffff0000u));
-      *reinterpret_cast<uint4*>(o - e.out_split) = lo;
-    }
+    if (e.out_h2) { row_store_h2x8(row, N, n, v, u); continue; }
+    const uint4 hi = row_store_bf16x8(row, n, v, u);
+    if (e.out_split < 0) row_store_pair_lo8(row, n, -e.out_split, v, u, hi);
   }
 }
 
@@ -446,28 +370,11 @@ inline bool epi_regmath_ok(const GemmEpi& e, int N) {
   return drain8_ok(e, N) && e.out_split == 0 && !e.out_h2 && !e.glu && !e.ln_part && (!e.ln_part_in || (e.ln_npart >= 1 && e.ln_npart <= 8)) &&
          (e.act == ACT_NONE || e.act == ACT_RELU || e.act == ACT_GELU);
 }
-// One accumulator quad through the arithmetic of drain_tile_bf16x8, expression for expression (the outputs are bit-identical): t = -mean rstd,
-// rs = rstd of the quad's row; c = the column sums (folded) or the LayerScale, b = the bias.
+// One accumulator quad through epi_math4, packed
 template <int LN>
-__device__ __forceinline__ uint2 epi_quad_bf16(float4 v, const float4& c, const float4& b, float t1, float rs1, int act) {
-  if (LN == LN_CONS) {
-    const f32x2_t t = (f32x2_t)(t1), rs = (f32x2_t)(rs1);
-#define LN_PAIR_(va, vb, ca, cb, ba, bb)                                                                         \
-      { const f32x2_t c_ = {ca, cb}, b_ = {ba, bb}, a_ = {va, vb};                                                \
-        const f32x2_t o_ = __builtin_elementwise_fma(a_, rs, __builtin_elementwise_fma(t, c_, b_));               \
-        va = o_.x; vb = o_.y; }
-    LN_PAIR_(v.x, v.y, c.x, c.y, b.x, b.y) LN_PAIR_(v.z, v.w, c.z, c.w, b.z, b.w)
-#undef LN_PAIR_
-  } else {
-    v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
-  }
-  if (act == ACT_GELU) {
-    gelu_fast4(v);
-  } else if (act == ACT_RELU) {
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-  }
-  if (LN != LN_CONS) { v.x *= c.x; v.y *= c.y; v.z *= c.z; v.w *= c.w; }
-  return make_uint2(pack2bf(v.x, v.y), pack2bf(v.z, v.w));
+__device__ __forceinline__ uint2 epi_quad_bf16(float4 v, const float4& c, const float4& b, float t, float rs, int act) {
+  epi_math4<LN>(v, c, b, t, rs, act);
+  return bf16_pack4(v);
 }
 // The staged bf16 tile: 512-byte rows, 8-byte slot s of row r at slot s ^ (r & 15).  A ds_write_b64 is served in four groups of 16 lanes --
 // here 16 consecutive rows at ONE column quad -- over 32 banks: the XOR puts them on 16 different slots (a row pad of 16 B leaves rows r and

@@ -123,10 +123,6 @@ __device__ __forceinline__ void f32_mainloop(const LA& la, const LW& lw, int kt0
   }
 }
 
-inline bool vec_ok(const void* p, long long ld, long long s1 = 0, long long s2 = 0) {
-  return ((uintptr_t)p & 15) == 0 && ld >= 4 && ld % 4 == 0 && s1 % 4 == 0 && s2 % 4 == 0;
-}
-
 }  // namespace
 
 // K split across workgroups (round 4).  A 64x64 tile walking K = 768 is 384 dependent v_mfma_f32_32x32x2_f32 per wave -- 24.6 k matrix-pipe cycles,
@@ -314,14 +310,7 @@ __global__ __launch_bounds__(256) void gemm_f32x_kernel(GemmF32X g) {
 
 int launch_gemm_f32x(const GemmF32X& g_, hipStream_t s) {
   GemmF32X g = g_;
-  if (g.M <= 0 || g.N <= 0 || g.K <= 0 || !g.A || !g.W || !g.C) return 1;
-  if (g.batch < 1) g.batch = 1;
-  if (g.hb < 1) g.hb = 1;
-  if (g.batch % g.hb || g.batch > 65535) return 2;
-  if (g.ksplit < 1) g.ksplit = 1;
-  if (g.ksplit > 1 && (g.act != ACT_NONE || g.scale || g.resid)) return 2;
-  const int nkt = (g.K + FBK - 1) / FBK;
-  if (g.ksplit > nkt) g.ksplit = nkt;
+  if (const int rc = f32x_normalize(g, FBK)) return rc;
   const int tiles = ((g.M + FBM - 1) / FBM) * ((g.N + FBN - 1) / FBN);
   const bool vec = vec_ok(g.A, g.lda, g.a_sb, g.a_sh) && vec_ok(g.W, g.ldw, g.w_sb, g.w_sh);
   const dim3 grid(tiles, g.batch, g.ksplit);

@@ -20,6 +20,7 @@
 // two workgroups per CU; that a second resident workgroup covers the one-stage form's barriers is the intent, its occupancy was not measured.
 // Measured per product and per step: DESIGN.md section 6b.
 #include "dod_common.h"
+#include "operand_rows.h"
 #include "gemm_f32x_epi.h"
 #include <atomic>
 
@@ -63,11 +64,6 @@ struct SplitLoad {
     v.x = oin && c < cn ? v.x : 0.f; v.y = oin && c + 1 < cn ? v.y : 0.f; v.z = oin && c + 2 < cn ? v.z : 0.f; v.w = oin && c + 3 < cn ? v.w : 0.f;
     return v;
   }
-  // (x, y) -> the dword of their bf16 heads (x in the low half) and the dword of the bf16 remainders
-  static __device__ __forceinline__ void split2(float x, float y, uint32_t& h, uint32_t& l) {
-    h = pack2bf(x, y);
-    l = pack2bf(x - bf2f((bf16_t)(h & 0xffffu)), y - bf2f((bf16_t)(h >> 16)));
-  }
   // sh / sl: the hi / lo tile's row 0 of unit u
   __device__ __forceinline__ void store(bf16_t* sh, bf16_t* sl, float4 v0, float4 v1, int k0, int u) const {
     v0 = mask(v0, k0, u, 0); v1 = mask(v1, k0, u, 1);
@@ -75,16 +71,16 @@ struct SplitLoad {
       const float x0[4] = {v0.x, v0.y, v0.z, v0.w}, x1[4] = {v1.x, v1.y, v1.z, v1.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        uint32_t h, l; split2(x0[i], x1[i], h, l);
+        uint32_t h, l; bf16_split2(x0[i], x1[i], h, l);
         *reinterpret_cast<uint32_t*>(sh + (b + i) * XLD + a) = h;      // a even: 4-byte aligned
         *reinterpret_cast<uint32_t*>(sl + (b + i) * XLD + a) = l;
       }
     } else {
       uint2 h, l;
-      split2(v0.x, v0.y, h.x, l.x); split2(v0.z, v0.w, h.y, l.y);
+      bf16_split2(v0.x, v0.y, h.x, l.x); bf16_split2(v0.z, v0.w, h.y, l.y);
       *reinterpret_cast<uint2*>(sh + a * XLD + b) = h;                 // 80-byte rows, b % 4 == 0: 8-byte aligned
       *reinterpret_cast<uint2*>(sl + a * XLD + b) = l;
-      split2(v1.x, v1.y, h.x, l.x); split2(v1.z, v1.w, h.y, l.y);
+      bf16_split2(v1.x, v1.y, h.x, l.x); bf16_split2(v1.z, v1.w, h.y, l.y);
       *reinterpret_cast<uint2*>(sh + (a + 32) * XLD + b) = h;
       *reinterpret_cast<uint2*>(sl + (a + 32) * XLD + b) = l;
     }
@@ -208,10 +204,6 @@ __global__ __launch_bounds__(256) void gemm_f32x3_kernel(GemmF32X g) {
     }
 }
 
-inline bool vec_ok(const void* p, long long ld, long long s1, long long s2) {
-  return ((uintptr_t)p & 15) == 0 && ld >= 4 && ld % 4 == 0 && s1 % 4 == 0 && s2 % 4 == 0;
-}
-
 std::atomic<long> g_x3_count{0}, g_x3_wide{0};
 
 template <int T>
@@ -233,14 +225,7 @@ long gemm_f32x3_count(int wide) { return wide ? g_x3_wide.load() : g_x3_count.lo
 
 int launch_gemm_f32x3(const GemmF32X& g_, hipStream_t s) {
   GemmF32X g = g_;
-  if (g.M <= 0 || g.N <= 0 || g.K <= 0 || !g.A || !g.W || !g.C) return 1;
-  if (g.batch < 1) g.batch = 1;
-  if (g.hb < 1) g.hb = 1;
-  if (g.batch % g.hb || g.batch > 65535) return 2;
-  if (g.ksplit < 1) g.ksplit = 1;
-  if (g.ksplit > 1 && (g.act != ACT_NONE || g.scale || g.resid)) return 2;
-  const int nkt = (g.K + XBK - 1) / XBK;
-  if (g.ksplit > nkt) g.ksplit = nkt;
+  if (const int rc = f32x_normalize(g, XBK)) return rc;
   // 128x128 from one such tile per CU up (256 CUs): below that the wide tile leaves CUs idle where the 64x64 grid fills them
   const long wide_tiles = (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch;
   const int opt = dod_option(DOD_OPT_F32X3_TILE);      // test hook: 64 / 128 force a form

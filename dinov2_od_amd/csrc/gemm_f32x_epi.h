@@ -6,6 +6,24 @@
 #pragma once
 #include "dod_common.h"
 
+// ---- host side, shared by the two launchers
+// 16-byte loads are allowed: aligned base, row pitch and batch strides multiples of four floats
+inline bool vec_ok(const void* p, long long ld, long long s1 = 0, long long s2 = 0) {
+  return ((uintptr_t)p & 15) == 0 && ld >= 4 && ld % 4 == 0 && s1 % 4 == 0 && s2 % 4 == 0;
+}
+// Argument check and defaults of a GemmF32X launch (bk = the kernel's k-tile): 0, or the launcher's return code (1: nothing to do, 2: rejected)
+inline int f32x_normalize(GemmF32X& g, int bk) {
+  if (g.M <= 0 || g.N <= 0 || g.K <= 0 || !g.A || !g.W || !g.C) return 1;
+  if (g.batch < 1) g.batch = 1;
+  if (g.hb < 1) g.hb = 1;
+  if (g.batch % g.hb || g.batch > 65535) return 2;
+  if (g.ksplit < 1) g.ksplit = 1;
+  if (g.ksplit > 1 && (g.act != ACT_NONE || g.scale || g.resid)) return 2;
+  const int nkt = (g.K + bk - 1) / bk;
+  if (g.ksplit > nkt) g.ksplit = nkt;
+  return 0;
+}
+
 // C = alpha acc (+ bias) -> activation (-> * scale[n]) (+ resid) (+ C): every thread stores its own 16 values
 __device__ __forceinline__ void f32x_epi_direct(const GemmF32X& g, float* cz, int m0, int n0, const f32x16& acc) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;

@@ -541,11 +541,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const void* __restr
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   auto ld4 = [&](int c) -> float4 {
-    if (IN_BF16) {
-      const uint2 u = *reinterpret_cast<const uint2*>((const bf16_t*)xin + (size_t)row * ld + c);
-      return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                         __uint_as_float(u.y & 0xffff0000u));
-    }
+    if (IN_BF16) return bf16_unpack4(*reinterpret_cast<const uint2*>((const bf16_t*)xin + (size_t)row * ld + c));
     return *reinterpret_cast<const float4*>((const float*)xin + (size_t)row * ld + c);
   };
   float amax = 0.f;
@@ -576,10 +572,8 @@ __global__ __launch_bounds__(256) void quant_mx_fp8_kernel(const void* __restric
     const int c = c0 + lane * 4;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (c < cols) {
-      if (IN_BF16) {
-        const uint2 u = *reinterpret_cast<const uint2*>((const bf16_t*)xin + (size_t)row * ld + c);
-        v = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-      } else v = *reinterpret_cast<const float4*>((const float*)xin + (size_t)row * ld + c);
+      if (IN_BF16) v = bf16_unpack4(*reinterpret_cast<const uint2*>((const bf16_t*)xin + (size_t)row * ld + c));
+      else v = *reinterpret_cast<const float4*>((const float*)xin + (size_t)row * ld + c);
     }
     float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
     amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
@@ -621,7 +615,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_reg_kernel(const bf16_t* _
     if (c < cols) v[i] = *reinterpret_cast<const uint4*>(xr + c);
     const unsigned w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fmaxf(fabsf(__uint_as_float(w[j] << 16)), fabsf(__uint_as_float(w[j] & 0xffff0000u))));
+    for (int j = 0; j < 4; ++j) { const float2 f = bf16_unpack2(w[j]); amax = fmaxf(amax, fmaxf(fabsf(f.x), fabsf(f.y))); }
   }
   amax = wave_max(amax);
   const float sc = amax > 0.f ? amax / 448.0f : 1.0f;
@@ -631,9 +625,10 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_reg_kernel(const bf16_t* _
   for (int i = 0; i < NV; ++i) {
     const int c = (i * 64 + lane) * 8;
     if (c >= cols) continue;
+    const float4 a = bf16_unpack4(make_uint2(v[i].x, v[i].y)), b = bf16_unpack4(make_uint2(v[i].z, v[i].w));
     uint2 o;
-    o.x = pack4_fp8(__uint_as_float(v[i].x << 16) * inv, __uint_as_float(v[i].x & 0xffff0000u) * inv, __uint_as_float(v[i].y << 16) * inv, __uint_as_float(v[i].y & 0xffff0000u) * inv);
-    o.y = pack4_fp8(__uint_as_float(v[i].z << 16) * inv, __uint_as_float(v[i].z & 0xffff0000u) * inv, __uint_as_float(v[i].w << 16) * inv, __uint_as_float(v[i].w & 0xffff0000u) * inv);
+    o.x = pack4_fp8(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
+    o.y = pack4_fp8(b.x * inv, b.y * inv, b.z * inv, b.w * inv);
     *reinterpret_cast<uint2*>(q + (size_t)row * ldq + c) = o;
   }
 }
@@ -667,10 +662,8 @@ __global__ __launch_bounds__(256) void swiglu_fp8_kernel(const bf16_t* __restric
   const bf16_t* pa = in + (size_t)row * 2 * Fh;
   const bf16_t* pb = pa + Fh;
   auto val4 = [&](int c) -> float4 {
-    const uint2 ua = *reinterpret_cast<const uint2*>(pa + c), ub = *reinterpret_cast<const uint2*>(pb + c);
-    const float a0 = __uint_as_float(ua.x << 16), a1 = __uint_as_float(ua.x & 0xffff0000u), a2 = __uint_as_float(ua.y << 16), a3 = __uint_as_float(ua.y & 0xffff0000u);
-    const float b0 = __uint_as_float(ub.x << 16), b1 = __uint_as_float(ub.x & 0xffff0000u), b2 = __uint_as_float(ub.y << 16), b3 = __uint_as_float(ub.y & 0xffff0000u);
-    return make_float4(a0 / (1.0f + expf(-a0)) * b0, a1 / (1.0f + expf(-a1)) * b1, a2 / (1.0f + expf(-a2)) * b2, a3 / (1.0f + expf(-a3)) * b3);
+    const float4 a = bf16_unpack4(*reinterpret_cast<const uint2*>(pa + c)), b = bf16_unpack4(*reinterpret_cast<const uint2*>(pb + c));
+    return make_float4(a.x / (1.0f + expf(-a.x)) * b.x, a.y / (1.0f + expf(-a.y)) * b.y, a.z / (1.0f + expf(-a.z)) * b.z, a.w / (1.0f + expf(-a.w)) * b.w);
   };
   const bool cached = Fh <= SW8_MAXC * 256;      // wave-uniform
   float4 v[SW8_MAXC];

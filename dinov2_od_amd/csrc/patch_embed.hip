@@ -14,6 +14,7 @@
 //   X3 = false: bf16 operands (bf16 / fp8 modes);  X3 = true: split products on hi / lo planes (parity-gated bf16x3 mode):
 //   pixel = hi + lo in registers, weight in the pair layout [Wh | Wl], Wl Ah + Wh Al + Wh Ah.
 #include "dod_common.h"
+#include "operand_rows.h"
 
 #define PE_M 128
 #define PE_N 128
@@ -108,8 +109,7 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const void* __restrict
     _Pragma("unroll") for (int i = 0; i < NP2; ++i) {                                                       \
       const unsigned hi_ = pack2bf(PV[2 * i], PV[2 * i + 1]);                                               \
       *reinterpret_cast<unsigned*>(sa_ + lofs[i]) = hi_;                                                    \
-      if (X3) *reinterpret_cast<unsigned*>(sa_ + PE_PLANE + lofs[i]) =                                      \
-          pack2bf(PV[2 * i] - __uint_as_float(hi_ << 16), PV[2 * i + 1] - __uint_as_float(hi_ & 0xffff0000u)); \
+      if (X3) *reinterpret_cast<unsigned*>(sa_ + PE_PLANE + lofs[i]) = bf16_rem2(PV[2 * i], PV[2 * i + 1], hi_); \
     }                                                                                                       \
     char* sw_ = sa_ + (X3 ? 2 : 1) * PE_PLANE;                                                              \
     *reinterpret_cast<uint4*>(sw_ + wofs0) = WA;                                                            \
@@ -208,13 +208,8 @@ __global__ void patch_pack_kernel(const float* __restrict__ W, int D, int p, bf1
     const int s = k >> 5, kk = k & 31, r = kk >> 4, j = kk & 15;
     const int c = s / (p / 2), si = s - c * (p / 2);
     const float v = j < p ? W[(((size_t)n * 3 + c) * p + (2 * si + r)) * p + j] : 0.f;
-    const bf16_t hi = f2bf(v);
-    if (x3) {
-      out[(size_t)n * 2 * kp + k] = hi;
-      out[(size_t)n * 2 * kp + kp + k] = f2bf(v - bf2f(hi));
-    } else {
-      out[idx] = hi;
-    }
+    if (x3) row_store_pair1(out + (size_t)n * 2 * kp, k, kp, v);
+    else out[idx] = f2bf(v);
   }
 }
 

@@ -3,6 +3,7 @@
 // one-time weight packing helpers (LoRA merge K8, casts, concatenation).  All HBM-bound:
 // wave-per-row with 16-byte accesses, fp32 statistics, shuffle reductions.
 #include "dod_common.h"
+#include "operand_rows.h"
 
 // ----------------------------------------------------------------------------- LayerNorm
 // nn.LayerNorm over the last dim (modeling_dinov2.py:348,353,441 eps 1e-6; deformable_attention.py:197-209
@@ -107,42 +108,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     if (EXACT || c < nc) {
       const float4 w = v[i];
       if (OUT & LN_F32) reinterpret_cast<float4*>(o.f32 + (size_t)row * D)[c] = w;
-      if (OUT & LN_H2) {   // H2 operand row (fp16 | e4m3 main, e4m3 remainder per 32-k block; dod_common.h)
-        uint2 f16; unsigned hi8, lo8;
-        h2_quad(w, 1.0f, f16, hi8, lo8);
-        char* ob = reinterpret_cast<char*>(o.split) + (size_t)row * 4 * D;
-        reinterpret_cast<uint2*>(ob)[c] = f16;
-        char* p8 = ob + h2_off8(D, 4 * c);
-        *reinterpret_cast<unsigned*>(p8) = hi8;
-        *reinterpret_cast<unsigned*>(p8 + 16) = lo8;
-      }
-      if (OUT & LN_PAIR) {   // split-product operand in the pair layout [hi | lo] (row pitch 2*D)
-        uint2 hi, lo;
-        hi.x = pack2bf(w.x, w.y);
-        hi.y = pack2bf(w.z, w.w);
-        lo.x = pack2bf(w.x - __uint_as_float(hi.x << 16), w.y - __uint_as_float(hi.x & 0xffff0000u));
-        lo.y = pack2bf(w.z - __uint_as_float(hi.y << 16), w.w - __uint_as_float(hi.y & 0xffff0000u));
-        bf16_t* ob = o.split + (size_t)row * 2 * D;
-        reinterpret_cast<uint2*>(ob)[c] = hi;
-        reinterpret_cast<uint2*>(ob + D)[c] = lo;
-      }
-      if (OUT & LN_S3) {     // bf16x3 activation operand [hi | hi | lo] (row pitch 3*D) of the decoder's query-side linears: saves their split3 launch
-        uint2 hi, lo;
-        hi.x = pack2bf(w.x, w.y);
-        hi.y = pack2bf(w.z, w.w);
-        lo.x = pack2bf(w.x - __uint_as_float(hi.x << 16), w.y - __uint_as_float(hi.x & 0xffff0000u));
-        lo.y = pack2bf(w.z - __uint_as_float(hi.y << 16), w.w - __uint_as_float(hi.y & 0xffff0000u));
-        bf16_t* ob = o.a3 + (size_t)row * 3 * D;
-        reinterpret_cast<uint2*>(ob)[c] = hi;
-        reinterpret_cast<uint2*>(ob + D)[c] = hi;
-        reinterpret_cast<uint2*>(ob + 2 * D)[c] = lo;
-      }
-      if (OUT & LN_BF16) {
-        uint2 p;
-        p.x = pack2bf(w.x, w.y);
-        p.y = pack2bf(w.z, w.w);
-        reinterpret_cast<uint2*>(o.bf16 + (size_t)row * D)[c] = p;
-      }
+      if (OUT & LN_H2) row_store_h2x4(o.split + (size_t)row * 2 * D, D, 4 * c, w);       // H2 operand row (4*D bytes)
+      if (OUT & LN_PAIR) row_store_pair4(o.split + (size_t)row * 2 * D, 4 * c, D, w);     // split-product operand [hi | lo] (row pitch 2*D)
+      // bf16x3 activation operand [hi | hi | lo] (row pitch 3*D) of the decoder's query-side linears: saves their split3 launch
+      if (OUT & LN_S3) row_store_s3x4(o.a3 + (size_t)row * 3 * D, 4 * c, D, w);
+      if (OUT & LN_BF16) row_store_bf16x4(o.bf16 + (size_t)row * D, 4 * c, w);
     }
   }
 }
@@ -231,27 +201,10 @@ __global__ __launch_bounds__(256) void rowstats_kernel(const float* __restrict__
     const int c = lane + 64 * i;
     if (!(EXACT || c < nc)) continue;
     const float4 w = v[i];
-    if (KIND == LNOP_H2) {
-      uint2 f16; unsigned hi8, lo8;
-      h2_quad(w, 1.0f, f16, hi8, lo8);
-      char* ob = reinterpret_cast<char*>(op) + (size_t)row * 4 * D;
-      reinterpret_cast<uint2*>(ob)[c] = f16;
-      char* p8 = ob + h2_off8(D, 4 * c);
-      *reinterpret_cast<unsigned*>(p8) = hi8;
-      *reinterpret_cast<unsigned*>(p8 + 16) = lo8;
-    } else {
-      uint2 hi;
-      hi.x = pack2bf(w.x, w.y);
-      hi.y = pack2bf(w.z, w.w);
-      bf16_t* ob = reinterpret_cast<bf16_t*>(op) + (size_t)row * (KIND == LNOP_PAIR ? 2 : 1) * D;
-      reinterpret_cast<uint2*>(ob)[c] = hi;
-      if (KIND == LNOP_PAIR) {
-        uint2 lo;
-        lo.x = pack2bf(w.x - __uint_as_float(hi.x << 16), w.y - __uint_as_float(hi.x & 0xffff0000u));
-        lo.y = pack2bf(w.z - __uint_as_float(hi.y << 16), w.w - __uint_as_float(hi.y & 0xffff0000u));
-        reinterpret_cast<uint2*>(ob + D)[c] = lo;
-      }
-    }
+    bf16_t* ob = reinterpret_cast<bf16_t*>(op) + (size_t)row * (KIND == LNOP_BF16 ? 1 : 2) * D;      // row pitch in 2-byte units
+    if (KIND == LNOP_H2) row_store_h2x4(ob, D, 4 * c, w);
+    else if (KIND == LNOP_PAIR) row_store_pair4(ob, 4 * c, D, w);
+    else row_store_bf16x4(ob, 4 * c, w);
   }
 }
 
@@ -521,9 +474,8 @@ __global__ void split3_kernel(const float* __restrict__ in, int ld_in, bf16_t* _
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const size_t r = i / K;
     const int c = (int)(i - r * K);
-    const float x = in[r * ld_in + c];
-    const bf16_t hi = f2bf(x);
-    const bf16_t lo = f2bf(x - bf2f(hi));
+    bf16_t hi, lo;
+    bf16_split1(in[r * ld_in + c], hi, lo);
     bf16_t* o = out + r * 3 * (size_t)K + c;
     o[0] = hi;
     o[K] = mode ? lo : hi;
@@ -536,11 +488,7 @@ __global__ void split2_kernel(const float* __restrict__ in, int ld_in, bf16_t* _
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const size_t r = i / K;
     const int c = (int)(i - r * K);
-    const float x = in[r * ld_in + c];
-    const bf16_t hi = f2bf(x);
-    bf16_t* o = out + r * 2 * (size_t)K + c;
-    o[0] = hi;
-    o[K] = f2bf(x - bf2f(hi));
+    row_store_pair1(out + r * 2 * (size_t)K, c, K, in[r * ld_in + c]);
   }
 }
 int launch_split2(const float* in, int ld_in, bf16_t* out, int rows, int K, hipStream_t s) {
@@ -575,15 +523,8 @@ __global__ __launch_bounds__(256) void split_h2_kernel(const float* __restrict__
   char* ob = out + (size_t)row * (wexp ? 3 : 4) * K;
   for (int c = lane * 4; c < K; c += 256) {
     const float4 v = make_float4(xr[c], xr[c + 1], xr[c + 2], xr[c + 3]);
-    uint2 f16; unsigned hi8, lo8;
-    h2_quad(v, shi, f16, hi8, lo8);
-    *reinterpret_cast<uint2*>(ob + 2 * c) = f16;
-    if (wexp) *reinterpret_cast<unsigned*>(ob + 2 * K + c) = lo8;
-    else {
-      char* p8 = ob + h2_off8(K, c);
-      *reinterpret_cast<unsigned*>(p8) = hi8;
-      *reinterpret_cast<unsigned*>(p8 + 16) = lo8;
-    }
+    if (wexp) row_store_h2w4(ob, K, c, v, shi);
+    else row_store_h2x4(ob, K, c, v);
   }
 }
 int launch_split_h2(const float* in, int ld_in, void* out, int rows, int K, unsigned char* wexp, hipStream_t s) {

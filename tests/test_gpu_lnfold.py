@@ -62,11 +62,8 @@ def _sample(M):
 SHAPES = [(300, 384, 384), (517, 192, 640), (2740, 768, 768), (64 * 1370, 768, 768), (64 * 1370, 768, 3072), (8224, 768, 3072)]
 
 
-@pytest.mark.parametrize("shifted", [True, False], ids=["shift", "noshift"])
-@pytest.mark.parametrize("fam", list(FAM))
-@pytest.mark.parametrize("M,D,K", SHAPES, ids=[f"{m}x{d}x{k}" for m, d, k in SHAPES])
-def test_residual_epilogue_emits_operand_rows_and_statistics(fam, M, D, K, shifted):
-    """out-proj (K = D) / fc2 (K = 4D) with the in-place fp32 residual + LayerScale epilogue (modeling_dinov2.py:367-370, 377-380)"""
+def _producer(fam, M, D, K, shifted):
+    """the unfolded launch and the folded producer on the same inputs -> (x_ref, x, op, part, stats)"""
     L = nat.lib()
     nat.check(L.dod_reserve_gemm_scratch(64 << 20))      # as dod_finalize_weights does: the K >= 2048 launches take the tail split (gemm_pp.hip)
     g = torch.Generator(device="cuda").manual_seed(M + 7 * D + K)
@@ -96,6 +93,21 @@ def test_residual_epilogue_emits_operand_rows_and_statistics(fam, M, D, K, shift
                                  nat.ptr(x), 0, D, 0, C.byref(ln), nat.stream_ptr()))
     nat.check(L.dod_op_ln_finalize(nat.ptr(part), M, D, EPS, nat.ptr(stats), nat.stream_ptr()))
     torch.cuda.synchronize()
+    return x_ref, x, op, part, stats
+
+
+def _operand_rows_are_the_split_of_x(fam, x, op, rows):
+    """the operand copy against the family's own split kernel (dod_op_split_pair / dod_op_split_h2) of the fp32 rows of the same launch, bit for bit"""
+    want = _operand(x, fam)[0]
+    assert torch.equal(op.view(torch.uint8)[rows], want.view(torch.uint8).view(op.shape[0], -1)[rows]), (fam, "operand rows differ from the split of x")
+
+
+@pytest.mark.parametrize("shifted", [True, False], ids=["shift", "noshift"])
+@pytest.mark.parametrize("fam", list(FAM))
+@pytest.mark.parametrize("M,D,K", SHAPES, ids=[f"{m}x{d}x{k}" for m, d, k in SHAPES])
+def test_residual_epilogue_emits_operand_rows_and_statistics(fam, M, D, K, shifted):
+    """out-proj (K = D) / fc2 (K = 4D) with the in-place fp32 residual + LayerScale epilogue (modeling_dinov2.py:367-370, 377-380)"""
+    x_ref, x, op, part, stats = _producer(fam, M, D, K, shifted)
     assert torch.equal(x, x_ref), "the folded producer must not change the residual rows"
     assert not torch.isnan(part).any(), "a (row, group) statistic was never written"
     xd = x.double()
@@ -114,6 +126,21 @@ def test_residual_epilogue_emits_operand_rows_and_statistics(fam, M, D, K, shift
         assert torch.equal(got, want.bfloat16().double())
     else:
         assert rel_err(got.numpy(), want.double().numpy()) < (2 ** -16 if fam == "bf16x3" else 2e-5)
+    _operand_rows_are_the_split_of_x(fam, x, op, rows)
+
+
+# 37 rows (no multiple of 4, 16 or 32), one partial tile and one partial 128-column group; 96 columns for H2 rows (three 16-k groups), 100 for
+# the bf16 forms (no multiple of 8 or 64)
+EDGE = [("bf16", 37, 100, 64), ("bf16x3", 37, 100, 64), ("fp16x2", 37, 96, 64)]
+
+
+@pytest.mark.parametrize("fam,M,D,K", EDGE, ids=[f"{f}-{m}x{d}x{k}" for f, m, d, k in EDGE])
+def test_residual_epilogue_operand_rows_at_edge_shapes(fam, M, D, K):
+    """every operand row of the folded producer at the smallest ragged shape: the split of the fp32 rows of the same launch, bit for bit"""
+    x_ref, x, op, part, _ = _producer(fam, M, D, K, True)
+    assert torch.equal(x, x_ref), "the folded producer must not change the residual rows"
+    assert not torch.isnan(part).any(), "a (row, group) statistic was never written"
+    _operand_rows_are_the_split_of_x(fam, x, op, torch.arange(M, device="cuda"))
 
 
 CONS = [(300, 1152, 384, "none"), (517, 520, 192, "gelu"), (2740, 2304, 768, "none"), (64 * 1370, 2304, 768, "none"), (64 * 1370, 3072, 768, "gelu"),
