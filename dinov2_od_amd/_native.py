@@ -232,13 +232,15 @@ SYMBOLS = {
     "dod_test_set_option": (_I, [C.c_char_p, _I]),
     "dod_test_counter": (C.c_long, [C.c_char_p]),
     "dod_test_gemm_plan": (_I, [_I, _I, _I, _I, C.c_uint, _I, C.c_size_t, _P, _I]),
+    "dod_test_packed_info": (_I, [_P, C.c_char_p, _P]),
+    "dod_test_packed_copy": (_I, [_P, C.c_char_p, _I, _P, C.c_size_t, _P]),
     "dod_version": (C.c_char_p, []),
     "dod_abi_version": (_I, []),
     "dod_device_count": (_I, []),
 }
 
 _lib = None
-ABI_VERSION = 6     # include/dinodet.h DOD_ABI_VERSION
+ABI_VERSION = 7     # include/dinodet.h DOD_ABI_VERSION
 
 
 def lib():
@@ -292,6 +294,33 @@ def gemm_plan(family, M, N, K, epi_flags, cus, scratch_bytes):
     if n < 0:
         raise ValueError(f"dod_test_gemm_plan rejected family={family} M={M} N={N} K={K} cus={cus}")
     return [(s.form, s.row0, s.rows, s.kslices, s.regmath, s.gm) for s in steps[:n]]
+
+
+PK_FORMAT = {-1: "absent", 0: "f32", 1: "bf16", 2: "pair", 3: "h2w", 4: "e4m3_rows", 5: "e4m3_mx", 6: "split3w"}      # enum dod_packed_format
+PK_ARRAY = {"w": 0, "bias": 1, "csum": 2, "wscale": 3, "wbs": 4, "wexp": 5}                                           # enum dod_packed_array
+
+
+class DodPackedInfo(C.Structure):
+    _fields_ = [("format", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("arrays", C.c_int32), ("pitch", C.c_int64),
+                ("bytes", C.c_int64 * 6), ("glu", C.c_int32), ("fold", C.c_int32), ("vp_alias", C.c_int32), ("reserved", C.c_int32)]
+
+
+def packed_info(handle, name):
+    """dod_test_packed_info (include/dinodet.h) -> dict(format, rows, cols, pitch, arrays: {name: bytes}, glu, fold, vp_alias)"""
+    info = DodPackedInfo()
+    check(lib().dod_test_packed_info(handle, name.encode(), C.byref(info)), handle)
+    arrays = {k: int(info.bytes[a]) for k, a in PK_ARRAY.items() if info.arrays >> a & 1}
+    return dict(format=PK_FORMAT[info.format], rows=info.rows, cols=info.cols, pitch=int(info.pitch), arrays=arrays, glu=bool(info.glu),
+                fold=bool(info.fold), vp_alias=info.vp_alias)
+
+
+def packed_array(handle, name, array="w", info=None):
+    """dod_test_packed_copy: one array of a packed operand as a uint8 CUDA tensor of exactly its bytes (copied on torch's current stream)"""
+    import torch
+    info = info or packed_info(handle, name)
+    out = torch.empty(info["arrays"][array], dtype=torch.uint8, device="cuda")
+    check(lib().dod_test_packed_copy(handle, name.encode(), PK_ARRAY[array], ptr(out), out.numel(), stream_ptr()), handle)
+    return out
 
 
 def set_option(name, value):

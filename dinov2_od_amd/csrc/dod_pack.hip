@@ -366,3 +366,138 @@ int dod::finalize_impl(dod_handle* h, hipStream_t s) {
   h->finalized = true;
   return DOD_OK;
 }
+
+// ----------------------------------------------------------------------------- read-only views of what finalize stored (dod_test_packed_*)
+namespace {
+
+// arrays of one packed operand in the order of enum dod_packed_array
+struct PackedView {
+  const void* p[DOD_PK_ARRAYS] = {};
+  size_t bytes[DOD_PK_ARRAYS] = {};
+  int format = DOD_PK_ABSENT, rows = 0, cols = 0;
+  size_t pitch = 0;
+  int glu = 0, fold = 0, vp_alias = -1;
+};
+
+void view_plain(PackedView& v, const void* p, int format, int rows, int cols, int cols_pad = 0) {
+  if (!p) return;
+  const int cp = cols_pad ? cols_pad : cols;
+  const size_t per = format == DOD_PK_F32 ? 4 : format == DOD_PK_BF16 ? 2 : format == DOD_PK_PAIR ? 4 : format == DOD_PK_SPLIT3W ? 6 : 1;
+  v.format = format; v.rows = rows; v.cols = cols; v.pitch = per * cp;
+  v.p[DOD_PK_W] = p; v.bytes[DOD_PK_W] = (size_t)rows * v.pitch;
+}
+
+void view_linear(const dod_handle* h, PackedView& v, const PackedLinear& L, int rows, int cols) {
+  if (L.W) {
+    const int format = L.wexp ? DOD_PK_H2W : L.wbs ? DOD_PK_E4M3_MX : L.wscale ? DOD_PK_E4M3_ROWS : is_x3(h) ? DOD_PK_PAIR : is_bf16(h) ? DOD_PK_BF16 : DOD_PK_F32;
+    if (format == DOD_PK_H2W) { v.format = format; v.rows = rows; v.cols = cols; v.pitch = (size_t)3 * cols; v.p[DOD_PK_W] = L.W; v.bytes[DOD_PK_W] = (size_t)rows * v.pitch; }
+    else view_plain(v, L.W, format, rows, cols);
+  } else { v.rows = rows; v.cols = cols; }
+  if (L.bias) { v.p[DOD_PK_BIAS] = L.bias; v.bytes[DOD_PK_BIAS] = (size_t)rows * 4; }
+  if (L.csum) { v.p[DOD_PK_CSUM] = L.csum; v.bytes[DOD_PK_CSUM] = (size_t)rows * 4; }
+  if (L.wscale) { v.p[DOD_PK_WSCALE] = L.wscale; v.bytes[DOD_PK_WSCALE] = (size_t)rows * 4; }
+  if (L.wbs) { v.p[DOD_PK_WBS] = L.wbs; v.bytes[DOD_PK_WBS] = (size_t)rows * (cols >> 5); }
+  if (L.wexp) { v.p[DOD_PK_WEXP] = L.wexp; v.bytes[DOD_PK_WEXP] = (size_t)rows; }
+}
+
+// "<prefix>.<index>.<field>" -> index and field; false when name has another form
+bool indexed(const char* name, const char* prefix, int* idx, const char** field) {
+  const size_t n = strlen(prefix);
+  if (strncmp(name, prefix, n) || name[n] != '.') return false;
+  char* end = nullptr;
+  const long i = strtol(name + n + 1, &end, 10);
+  if (end == name + n + 1 || *end != '.' || i < 0 || i > 1 << 20) return false;
+  *idx = (int)i; *field = end + 1;
+  return true;
+}
+
+// false: no operand of that name exists in any configuration
+bool packed_view(const dod_handle* h, const char* name, PackedView& v) {
+  const dod_config& c = h->cfg;
+  const int D = c.hidden, F = c.ffn_hidden, p = c.patch, Dd = c.dec_hidden, Q = c.num_queries, Fd = c.dim_feedforward;
+  const int wfmt = is_bf16(h) ? DOD_PK_BF16 : DOD_PK_F32;     // operand dtype outside the block linears
+  auto is = [&](const char* s) { return !strcmp(name, s); };
+  struct Plain { const char* name; const void* p; int format, rows, cols, cols_pad; };
+  int i = 0; const char* f = nullptr;
+  if (indexed(name, "block", &i, &f)) {
+    if (i >= (int)h->L.size()) return false;
+    const BLayer& L = h->L[i];
+    v.glu = L.glu; v.fold = L.fold;
+    const int F1 = c.swiglu ? 2 * F : F;
+    if (!strcmp(f, "qkv")) { view_linear(h, v, L.qkv, 3 * D, D); return true; }
+    if (!strcmp(f, "o")) { view_linear(h, v, L.o, D, D); return true; }
+    if (!strcmp(f, "fc1")) { view_linear(h, v, L.fc1, F1, D); return true; }
+    if (!strcmp(f, "fc2")) { view_linear(h, v, L.fc2, D, F); return true; }
+    const Plain t[] = {{"ln1w", L.ln1w, DOD_PK_F32, 1, D, 0}, {"ln1b", L.ln1b, DOD_PK_F32, 1, D, 0}, {"ln2w", L.ln2w, DOD_PK_F32, 1, D, 0},
+                       {"ln2b", L.ln2b, DOD_PK_F32, 1, D, 0}, {"ls1", L.ls1, DOD_PK_F32, 1, D, 0}, {"ls2", L.ls2, DOD_PK_F32, 1, D, 0}};
+    for (const Plain& e : t) if (!strcmp(f, e.name)) { view_plain(v, e.p, e.format, e.rows, e.cols, e.cols_pad); return true; }
+    return false;
+  }
+  if (indexed(name, "dec", &i, &f)) {
+    if (i >= (int)h->DL.size()) return false;
+    const DLayer& L = h->DL[i];
+    v.vp_alias = L.vp_alias;
+    const int S3 = DOD_PK_SPLIT3W, F32 = DOD_PK_F32, nc = h->ncat;
+    const Plain t[] = {
+      {"in_w", L.in_w, F32, 3 * Dd, Dd, 0}, {"in_b", L.in_b, F32, 1, 3 * Dd, 0}, {"out_w", L.out_w, F32, Dd, Dd, 0}, {"out_b", L.out_b, F32, 1, Dd, 0},
+      {"n1w", L.n1w, F32, 1, Dd, 0}, {"n1b", L.n1b, F32, 1, Dd, 0}, {"n2w", L.n2w, F32, 1, Dd, 0}, {"n2b", L.n2b, F32, 1, Dd, 0},
+      {"n3w", L.n3w, F32, 1, Dd, 0}, {"n3b", L.n3b, F32, 1, Dd, 0},
+      {"l1w", L.l1w, F32, Fd, Dd, 0}, {"l1b", L.l1b, F32, 1, Fd, 0}, {"l2w", L.l2w, F32, Dd, Fd, 0}, {"l2b", L.l2b, F32, 1, Dd, 0},
+      {"in_w3", L.in_w3, S3, 3 * Dd, Dd, 0}, {"out_w3", L.out_w3, S3, Dd, Dd, 0}, {"l1w3", L.l1w3, S3, Fd, Dd, 0}, {"l2w3", L.l2w3, S3, Dd, Fd, 0},
+      {"op_w3", L.op_w3, S3, Dd, Dd, 0}, {"ca_q_w3", L.ca_q_w3, S3, Dd, Dd, 0}, {"ca_out_w3", L.ca_out_w3, S3, Dd, Dd, 0},
+      {"cat_w", L.cat_w, F32, nc, Dd, 0}, {"cat_b", L.cat_b, F32, 1, nc, 0}, {"op_w", L.op_w, F32, Dd, Dd, 0}, {"op_b", L.op_b, F32, 1, Dd, 0},
+      {"vp_w", L.vp_w, wfmt, Dd, Dd, 0}, {"vp_w2", L.vp_w2, DOD_PK_PAIR, Dd, Dd, 0}, {"vp_b", L.vp_b, F32, 1, Dd, 0},
+      {"ca_q_w", L.ca_q_w, F32, Dd, Dd, 0}, {"ca_q_b", L.ca_q_b, F32, 1, Dd, 0}, {"ca_kv_w", L.ca_kv_w, wfmt, 2 * Dd, Dd, 0},
+      {"ca_kv_w2", L.ca_kv_w2, DOD_PK_PAIR, 2 * Dd, Dd, 0}, {"ca_kv_b", L.ca_kv_b, F32, 1, 2 * Dd, 0},
+      {"ca_out_w", L.ca_out_w, F32, Dd, Dd, 0}, {"ca_out_b", L.ca_out_b, F32, 1, Dd, 0}};
+    for (const Plain& e : t) if (!strcmp(f, e.name)) { view_plain(v, e.p, e.format, e.rows, e.cols, e.cols_pad); return true; }
+    return false;
+  }
+  const int K = 3 * p * p, kpe = 3 * (p / 2) * 32, G = c.pos_grid;
+  const Plain t[] = {
+    {"Wpatch", h->Wpatch, wfmt, D, K, h->Kp}, {"Wpatch2", h->Wpatch2, DOD_PK_PAIR, D, K, h->Kp2}, {"Wpe", h->Wpe, is_x3(h) ? DOD_PK_PAIR : DOD_PK_BF16, D, kpe, 0},
+    {"bpatch", h->bpatch, DOD_PK_F32, 1, D, 0}, {"cls", h->cls, DOD_PK_F32, 1, D, 0}, {"pos", h->pos, DOD_PK_F32, G * G + 1, D, 0},
+    {"lnfw", h->lnfw, DOD_PK_F32, 1, D, 0}, {"lnfb", h->lnfb, DOD_PK_F32, 1, D, 0},
+    {"Wproj", h->Wproj, is_x3(h) ? DOD_PK_PAIR : wfmt, c.target_dim, D, 0}, {"bproj", h->bproj, DOD_PK_F32, 1, c.target_dim, 0},
+    {"query", h->query, DOD_PK_F32, Q, Dd, 0}, {"cls_w", h->cls_w, DOD_PK_F32, c.num_classes, Dd, 0}, {"cls_b", h->cls_b, DOD_PK_F32, 1, c.num_classes, 0},
+    {"bb0_w", h->bb0_w, DOD_PK_F32, Dd / 2, Dd, 0}, {"bb0_b", h->bb0_b, DOD_PK_F32, 1, Dd / 2, 0}, {"bb0_w3", h->bb0_w3, DOD_PK_SPLIT3W, Dd / 2, Dd, 0},
+    {"bb2_w", h->bb2_w, DOD_PK_F32, 4, Dd / 2, 0}, {"bb2_b", h->bb2_b, DOD_PK_F32, 1, 4, 0},
+    {"l0_tgt", h->l0_tgt, DOD_PK_F32, Q, Dd, 0}, {"l0_proj", h->l0_proj, DOD_PK_F32, Q, h->ncat, 0}};
+  for (const Plain& e : t) if (is(e.name)) { view_plain(v, e.p, e.format, e.rows, e.cols, e.cols_pad); return true; }
+  return false;
+}
+
+int packed_lookup(const dod_handle* h, const char* name, PackedView& v, const char* who) {
+  if (!h) return fail(nullptr, DOD_ERR_INVALID, "%s: null handle", who);
+  if (!name) return fail(h, DOD_ERR_INVALID, "%s: null name", who);
+  if (!h->finalized) return fail(h, DOD_ERR_STATE, "%s: dod_finalize_weights has not been called", who);
+  if (!packed_view(h, name, v)) return fail(h, DOD_ERR_INVALID, "%s: no packed operand named '%s'", who, name);
+  return DOD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dod_test_packed_info(const dod_handle* h, const char* name, dod_packed_info* info) {
+  PackedView v;
+  const int rc = packed_lookup(h, name, v, "dod_test_packed_info"); if (rc) return rc;
+  if (!info) return fail(h, DOD_ERR_INVALID, "dod_test_packed_info: null info");
+  info->format = v.format; info->rows = v.rows; info->cols = v.cols; info->pitch = (int64_t)v.pitch;
+  info->glu = v.glu; info->fold = v.fold; info->vp_alias = v.vp_alias; info->reserved = 0; info->arrays = 0;
+  for (int a = 0; a < DOD_PK_ARRAYS; ++a) { info->bytes[a] = (int64_t)v.bytes[a]; if (v.p[a]) info->arrays |= 1 << a; }
+  return DOD_OK;
+}
+
+int dod_test_packed_copy(const dod_handle* h, const char* name, int array, void* dst, size_t dst_bytes, void* stream) {
+  PackedView v;
+  const int rc = packed_lookup(h, name, v, "dod_test_packed_copy"); if (rc) return rc;
+  if (array < 0 || array >= DOD_PK_ARRAYS) return fail(h, DOD_ERR_INVALID, "dod_test_packed_copy: array %d is not a dod_packed_array", array);
+  if (!dst) return fail(h, DOD_ERR_INVALID, "dod_test_packed_copy: null destination");
+  if (!v.p[array]) return fail(h, DOD_ERR_INVALID, "dod_test_packed_copy: '%s' has no array %d in this configuration", name, array);
+  if (dst_bytes < v.bytes[array]) return fail(h, DOD_ERR_INVALID, "dod_test_packed_copy: '%s' array %d holds %zu bytes, the destination %zu", name, array, v.bytes[array], dst_bytes);
+  HIPCHK(h, hipMemcpyAsync(dst, v.p[array], v.bytes[array], hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return DOD_OK;
+}
+
+}  // extern "C"

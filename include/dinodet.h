@@ -1072,6 +1072,37 @@ long dod_test_counter(const char* name);
  * "f32_ksplits" per f32 step with kslices > 1; "epi_regmath" per step with regmath. */
 typedef struct dod_gemm_step { int form, row0, rows, kslices, regmath, gm; } dod_gemm_step;
 int dod_test_gemm_plan(int family, int M, int N, int K, unsigned epi_flags, int cus, size_t scratch_bytes, dod_gemm_step* steps, int max_steps);
+/* What dod_finalize_weights stored, read-only (tests/test_gpu_pack.py holds every packed operand to its float64 definition).  Neither call
+ * changes the handle.  dod_test_packed_info describes the operand `name`; dod_test_packed_copy enqueues a device-to-device copy of one of its
+ * arrays (enum dod_packed_array) into dst, a device buffer of dst_bytes >= info.bytes[array], on `stream`.
+ *   names   "Wpatch" (im2col order, K = 3 p^2 padded to pitch), "Wpatch2" (bf16x3 / fp16x2: pair layout, K padded to a multiple of 32), "Wpe" (fused
+ *           patch embed: k' order of csrc/patch_embed.hip, 3 (p / 2) 32 columns), "bpatch", "cls", "pos", "lnfw", "lnfb", "Wproj", "bproj";
+ *           "block.<i>.qkv" / ".o" / ".fc1" / ".fc2" (with their bias / csum / wscale / wbs / wexp arrays), ".ln1w" ".ln1b" ".ln2w" ".ln2b" ".ls1" ".ls2";
+ *           "query", "cls_w", "cls_b", "bb0_w", "bb0_b", "bb0_w3", "bb2_w", "bb2_b", "l0_tgt", "l0_proj";
+ *           "dec.<j>." + in_w in_b out_w out_b n1w n1b n2w n2b n3w n3b l1w l1b l2w l2b, the split3 copies in_w3 out_w3 l1w3 l2w3 op_w3 ca_q_w3
+ *           ca_out_w3, deformable: cat_w cat_b op_w op_b vp_w vp_w2 vp_b, dense: ca_q_w ca_q_b ca_kv_w ca_kv_w2 ca_kv_b ca_out_w ca_out_b.
+ *   format  DOD_PK_ABSENT: the name is valid but this configuration / precision keeps no such operand (arrays == 0 unless a block linear kept
+ *           only its bias);  F32 / BF16: [rows, pitch / 4 or / 2] elements of which the first `cols` are data and the rest zero padding;
+ *           PAIR: bf16 [hi | lo], each plane pitch / 4 elements wide;  SPLIT3W: bf16 [hi | lo | hi], three planes of `cols`;  H2W: H2 weight
+ *           rows of 3 cols bytes with the WEXP array;  E4M3_ROWS: e4m3 [rows, cols] with the WSCALE array;  E4M3_MX: e4m3 [rows, cols] with the
+ *           WBS array in the [rows][2][cols / 64] order of dod_op_quant_mx_fp8.  Vectors report rows = 1.
+ *   glu, fold   the flags of block <i> (SwiGLU rows interleaved in fc1; LayerNorm folded into qkv / fc1), 0 for every other name
+ *   vp_alias    of decoder layer <j>: the earlier layer whose value projection it shares, or -1 (also for every other name)
+ * DOD_ERR_INVALID: NULL handle / name / info / dst, a name that no configuration has, an array the operand does not have, dst_bytes too small;
+ * DOD_ERR_STATE: the handle is not finalized. */
+enum dod_packed_format { DOD_PK_ABSENT = -1, DOD_PK_F32 = 0, DOD_PK_BF16 = 1, DOD_PK_PAIR = 2, DOD_PK_H2W = 3, DOD_PK_E4M3_ROWS = 4, DOD_PK_E4M3_MX = 5,
+                         DOD_PK_SPLIT3W = 6 };
+enum dod_packed_array { DOD_PK_W = 0, DOD_PK_BIAS = 1, DOD_PK_CSUM = 2, DOD_PK_WSCALE = 3, DOD_PK_WBS = 4, DOD_PK_WEXP = 5, DOD_PK_ARRAYS = 6 };
+typedef struct dod_packed_info {
+  int32_t format;           /* dod_packed_format */
+  int32_t rows, cols;
+  int32_t arrays;           /* bit a set: array a (dod_packed_array) exists */
+  int64_t pitch;            /* bytes per row of the W array */
+  int64_t bytes[6];         /* bytes of each array, 0 when absent */
+  int32_t glu, fold, vp_alias, reserved;
+} dod_packed_info;
+int dod_test_packed_info(const dod_handle* h, const char* name, dod_packed_info* info);
+int dod_test_packed_copy(const dod_handle* h, const char* name, int array, void* dst, size_t dst_bytes, void* stream);
 
 const char* dod_version(void);
 /* ABI revision of this header: bumped whenever an exported signature or struct layout changes (round 2's dod_set_weight gained its
@@ -1089,8 +1120,11 @@ const char* dod_version(void);
  * dod_coco_eval_append_detections and dod_coco_eval_confusion joined revision 6 the same way; the evaluator's workspace grew with them (the
  * per-image ground-truth lists), which a caller learns from dod_coco_eval_workspace_bytes as before.  The geometric warp
  * (dod_preprocess_warp, dod_preprocess_warp_u8) joined revision 6 by name as well, and so did the JPEG decode (dod_jpeg_*).
+ * Revision 7: the packed-operand accessor (dod_test_packed_info, dod_test_packed_copy, struct dod_packed_info) -- additive like the above, but it
+ * publishes the layout of what dod_finalize_weights keeps (the dod_packed_format / dod_packed_array numbering), which a tool built against this
+ * header reads through the struct: the revision is raised so that such a tool and the library agree on it.
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
-#define DOD_ABI_VERSION 6
+#define DOD_ABI_VERSION 7
 int dod_abi_version(void);
 /* Devices visible to the HIP runtime libdinodet.so is bound to (<= 0: none / error).  The host uses it to
  * verify the library shares PyTorch's HIP runtime (pointers and streams cross this ABI). */

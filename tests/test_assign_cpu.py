@@ -26,7 +26,7 @@ def lib():
 
 def test_assign_symbols_exported_at_abi_6(lib):
     hdr = open(os.path.join(ROOT, "include", "dinodet.h")).read()
-    assert int(re.search(r"#define DOD_ABI_VERSION (\d+)", hdr).group(1)) == 6 == nat.ABI_VERSION == lib.dod_abi_version()
+    assert int(re.search(r"#define DOD_ABI_VERSION (\d+)", hdr).group(1)) == 7 == nat.ABI_VERSION == lib.dod_abi_version()
     for name in ("dod_match_assign", "dod_match_assign_workspace_bytes"):
         assert re.search(rf"\b{name}\s*\(", hdr) and name in nat.SYMBOLS and hasattr(lib, name)
 

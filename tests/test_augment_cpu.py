@@ -166,11 +166,11 @@ def test_collate_raw_stacks_nothing():
 def test_bindings_resolve_and_the_abi_revision_stays():
     import os
     from dinov2_od_amd import _native as nat
-    assert nat.ABI_VERSION == 6 and len(nat.SYMBOLS["dod_preprocess_aug"][1]) == 17 and len(nat.SYMBOLS["dod_preprocess_aug_u8"][1]) == 17
+    assert nat.ABI_VERSION == 7 and len(nat.SYMBOLS["dod_preprocess_aug"][1]) == 17 and len(nat.SYMBOLS["dod_preprocess_aug_u8"][1]) == 17
     with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dinodet.h")) as f:
         header = f.read()
-    assert "#define DOD_ABI_VERSION 6" in header and "int dod_preprocess_aug(" in header and "int dod_preprocess_aug_u8(" in header
+    assert "#define DOD_ABI_VERSION 7" in header and "int dod_preprocess_aug(" in header and "int dod_preprocess_aug_u8(" in header
     if os.path.exists(nat.LIB_PATH):
         L = nat.lib()
-        assert L.dod_abi_version() == 6
+        assert L.dod_abi_version() == 7
         assert L.dod_preprocess_aug.argtypes == nat.SYMBOLS["dod_preprocess_aug"][1] and L.dod_preprocess_aug_u8.restype is not None

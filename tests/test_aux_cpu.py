@@ -146,4 +146,4 @@ def test_header_declares_the_new_symbols_at_abi_6():
     new = {f"dod_decoder_train_aux_{k}" for k in ("tape_bytes", "workspace_bytes", "forward", "backward")}
     new |= {f"dod_set_criterion_layers_{k}" for k in ("workspace_bytes", "forward", "backward")}
     assert new <= declared and new <= set(nat.SYMBOLS)
-    assert re.search(r"#define DOD_ABI_VERSION 6\b", hdr) and nat.ABI_VERSION == 6
+    assert re.search(r"#define DOD_ABI_VERSION 7\b", hdr) and nat.ABI_VERSION == 7

@@ -260,13 +260,13 @@ def test_train_augment_mixes_the_three_kinds(monkeypatch):
 # ---------------------------------------------------------------------------------------------------------------- 5. bindings
 def test_bindings_resolve_and_the_abi_revision_stays():
     from dinov2_od_amd import _native as nat
-    assert nat.ABI_VERSION == 6
+    assert nat.ABI_VERSION == 7
     for name in ("dod_preprocess_compose", "dod_preprocess_compose_u8"):
         assert len(nat.SYMBOLS[name][1]) == 22
     with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dinodet.h")) as f:
         header = f.read()
-    assert "#define DOD_ABI_VERSION 6" in header and "int dod_preprocess_compose(" in header and "int dod_preprocess_compose_u8(" in header
+    assert "#define DOD_ABI_VERSION 7" in header and "int dod_preprocess_compose(" in header and "int dod_preprocess_compose_u8(" in header
     if os.path.exists(nat.LIB_PATH):
         L = nat.lib()
-        assert L.dod_abi_version() == 6
+        assert L.dod_abi_version() == 7
         assert L.dod_preprocess_compose.argtypes == nat.SYMBOLS["dod_preprocess_compose"][1] and L.dod_preprocess_compose_u8.restype is not None

@@ -332,6 +332,46 @@ def test_create_validates_arguments(lib):
     assert make_config(bb, dc, "fp8").precision == 2          # DOD_PREC_FP8
 
 
+def test_packed_accessor_rejects_bad_arguments_before_any_copy(lib):
+    """dod_test_packed_info / dod_test_packed_copy: NULL handle, name, info or destination and a handle that is not finalized, before anything
+    is read (an unknown name, an absent array and a short destination need a finalized handle: tests/test_gpu_pack.py)"""
+    bb, dc = cases.cfg1(25)
+    h = C.c_void_p()
+    cfg = make_config(bb, dc, "bf16")
+    assert lib.dod_create(C.byref(cfg), C.byref(h)) == 0
+    info = nat.DodPackedInfo()
+    buf = (C.c_char * 64)()
+    assert lib.dod_test_packed_info(None, b"cls", C.byref(info)) == 1 and b"null handle" in lib.dod_last_error(None)
+    assert lib.dod_test_packed_copy(None, b"cls", 0, buf, 64, None) == 1 and b"null handle" in lib.dod_last_error(None)
+    assert lib.dod_test_packed_info(h, None, C.byref(info)) == 1 and b"null name" in lib.dod_last_error(h)
+    assert lib.dod_test_packed_copy(h, None, 0, buf, 64, None) == 1 and b"null name" in lib.dod_last_error(h)
+    for name in (b"cls", b"block.0.qkv", b"no.such.operand"):        # not finalized comes before the name is looked at
+        assert lib.dod_test_packed_info(h, name, C.byref(info)) == 3 and b"finalize" in lib.dod_last_error(h)
+        assert lib.dod_test_packed_copy(h, name, 0, buf, 64, None) == 3 and b"finalize" in lib.dod_last_error(h)
+    lib.dod_destroy(h)
+    assert C.sizeof(nat.DodPackedInfo) == 88                           # struct dod_packed_info
+    hdr = open(os.path.join(ROOT, "include", "dinodet.h")).read()
+    assert "int dod_test_packed_info(" in hdr and "int dod_test_packed_copy(" in hdr
+    for name, value in list(nat.PK_ARRAY.items()) + [(v, k) for k, v in nat.PK_FORMAT.items()]:      # the binding's numbering is the header's
+        token = {"w": "DOD_PK_W", "absent": "DOD_PK_ABSENT", "h2w": "DOD_PK_H2W", "split3w": "DOD_PK_SPLIT3W"}.get(name, "DOD_PK_" + name.upper())
+        assert re.search(rf"{token} = {value}\b", hdr), token
+
+
+@pytest.mark.parametrize("mode", ["bf16", "bf16x3", "fp16x2", "fp8"])
+def test_create_rejects_a_swiglu_width_the_fast_modes_cannot_pack(lib, mode):
+    """F = 344 (F % 64 != 0) exists in the fp32 mode only: the un-interleaved gate arm of dod_pack.hip for F % 32 != 0 is not reachable
+    through dod_create (tests/pack_cases.py REJECTED)"""
+    from tests import pack_cases as pc
+    cs = pc.case("swiglu128-f344")
+    assert (cs.name, mode) in pc.REJECTED
+    h = C.c_void_p()
+    cfg = make_config(cs.bb, cs.dc, mode)
+    assert lib.dod_create(C.byref(cfg), C.byref(h)) == 1 and b"ffn_hidden" in lib.dod_last_error(None)
+    cfg = make_config(cs.bb, cs.dc, "fp32")
+    assert lib.dod_create(C.byref(cfg), C.byref(h)) == 0
+    lib.dod_destroy(h)
+
+
 @pytest.mark.parametrize("deform", [True, False])
 def test_state_dict_keys_match_reference_layout(deform):
     """Keys/shapes equal the synthetic state dict, which tests/golden/make_goldens.py loads

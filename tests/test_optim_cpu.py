@@ -129,7 +129,7 @@ def test_state_dict_round_trips_with_torch_adam():
 
 def test_symbols_in_header_and_binding(lib):
     hdr = open(os.path.join(ROOT, "include", "dinodet.h")).read()
-    assert int(re.search(r"#define DOD_ABI_VERSION (\d+)", hdr).group(1)) == 6 == nat.ABI_VERSION == lib.dod_abi_version()
+    assert int(re.search(r"#define DOD_ABI_VERSION (\d+)", hdr).group(1)) == 7 == nat.ABI_VERSION == lib.dod_abi_version()
     for name in NAMES:
         assert re.search(rf"\b{name}\s*\(", hdr) and name in nat.SYMBOLS and hasattr(lib, name)
     assert "typedef struct dod_optim_tensor" in hdr and C.sizeof(nat.DodOptimTensor) == 48
