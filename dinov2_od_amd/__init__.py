@@ -11,7 +11,7 @@ def __getattr__(name):
     if name in ("DINOv2ObjectDetector", "DINOv2Backbone", "DETRDecoder"):
         from . import models
         return getattr(models, name)
-    if name == "optim":      # dinov2_od_amd.optim.Adam / clip_grad_norm_: the optimizer step on the HIP kernels
+    if name == "optim":      # dinov2_od_amd.optim.Adam / AdamW / ModelEMA / clip_grad_norm_: the optimizer step on the HIP kernels
         import importlib
         return importlib.import_module(".optim", __name__)
     if name in ("draw_detections", "log_images", "save_images"):      # dinov2_od_amd.visualize: boxes drawn into the batch on the GPU

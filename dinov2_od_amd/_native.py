@@ -80,6 +80,18 @@ class DodOptimTensor(C.Structure):
                 ("step_size", C.c_float), ("bc2_sqrt", C.c_float)]
 
 
+class DodOptimOptions(C.Structure):
+    """struct dod_optim_options (include/dinodet.h): what dod_optim_step takes beside the lists"""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("weight_decay", C.c_double), ("ema_w", C.c_double), ("eps", C.c_float),
+                ("max_norm", C.c_float), ("skip_nonfinite", C.c_int32), ("norm_ready", C.c_int32), ("total_norm_dev", C.c_void_p),
+                ("skipped_dev", C.c_void_p)]
+
+
+class DodOptimEmaTensor(C.Structure):
+    """struct dod_optim_ema_tensor (include/dinodet.h): one (average, parameter) pair of dod_optim_ema_update"""
+    _fields_ = [("e", C.c_void_p), ("p", C.c_void_p), ("n", C.c_int64)]
+
+
 class DodLnFold(C.Structure):
     """struct dod_ln_fold (include/dinodet.h): the folded-LayerNorm legs of dod_op_linear_ln"""
     _fields_ = [("stats", C.c_void_p), ("csum", C.c_void_p), ("op_out", C.c_void_p), ("part", C.c_void_p), ("shift", C.c_void_p),
@@ -227,6 +239,8 @@ SYMBOLS = {
     "dod_optim_workspace_bytes": (_SZ, [_I, _I64]),
     "dod_optim_clip_grad_norm": (_I, [_P, _I, _F, _P, _P, _SZ, _P]),
     "dod_optim_adam_step": (_I, [_P, _I, C.c_double, C.c_double, _F, C.c_double, _F, _P, _P, _SZ, _P]),
+    "dod_optim_step": (_I, [_P, _P, _P, _I, _P, _P, _SZ, _P]),
+    "dod_optim_ema_update": (_I, [_P, _I, C.c_double, _P]),
     "dod_optim_last_error": (C.c_char_p, []),
     "dod_reserve_gemm_scratch": (_I, [C.c_size_t]),
     "dod_test_set_option": (_I, [C.c_char_p, _I]),

@@ -68,6 +68,7 @@ long dod_test_counter(const char* name) {
   if (name && !strcmp(name, "optim_chunk_elems")) return optim_constant(0);
   if (name && !strcmp(name, "optim_table_tensors")) return optim_constant(1);
   if (name && !strcmp(name, "optim_norm_table_tensors")) return optim_constant(2);
+  if (name && !strcmp(name, "optim_ema_table_tensors")) return optim_constant(3);
   if (name && !strncmp(name, "form_", 5))
     for (int i = 0; i < FORM_COUNT; ++i)
       if (!strcmp(name + 5, k_form_names[i])) return g_form_launches[i].load();

@@ -39,7 +39,7 @@ enum { DOD_OPT_TAILSPLIT = 0,         // GEMM wave-quantisation tail split: 0 of
 int dod_option(int which);            // dod_api.hip; -1 when unset
 long gemm_tail_split_count();         // gemm_dispatch.hip: GEMM calls that took the tail-split path so far
 long optim_launch_count();            // optim.hip: launches of the optimizer entries so far
-long optim_constant(int which);       // optim.hip: 0 elements per workgroup, 1 / 2 tensors per update / norm launch
+long optim_constant(int which);       // optim.hip: 0 elements per workgroup, 1 / 2 / 3 tensors per update / norm / ema launch
 long gemm_rem_cut_count();            // gemm_dispatch.hip: GEMM calls whose short last round ran as a launch of its own
 long attn_half_tile_count();          // attn_bf16.hip: attention launches whose last key tile ran at half width
 long gemm_epi_regmath_count();        // gemm_dispatch.hip: launches of the 16-wave bf16 GEMM that took the register epilogue

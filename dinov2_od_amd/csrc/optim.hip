@@ -1,11 +1,14 @@
-// The optimizer step of the training loop on device: clip_grad_norm_ followed by Adam (L2 weight decay, no amsgrad) over a list of fp32
-// tensors, train.py:1101-1110 of the reference.  DESIGN.md section 6b states the arithmetic and its error bounds.
+// The optimizer step of the training loop on device: clip_grad_norm_ followed by Adam (L2 or decoupled weight decay, no amsgrad) over a
+// list of fp32 tensors, train.py:1101-1110 of the reference, with an optional exponential moving average of the weights written by the
+// thread that stores p' and an optional skip of the whole step on a non-finite norm.  DESIGN.md section 6b states the arithmetic and
+// its error bounds.
 //
 //   sumsq    one workgroup per chunk of one tensor's gradient; squares are accumulated in double from the first add on and every
 //            workgroup writes ONE partial sum to a workspace slot of its own.
 //   adam     every workgroup first adds up ALL partials in a fixed order (double; a few thousand values, L2 resident), forms the norm and
 //            the clip coefficient, then updates its own chunk once: one read of g, p, m, v and one write of p, m, v.
 //   scale    the standalone clip: the same reduction, then g *= coef in place.
+//   ema      the standalone moving average e += (p - e) w over a list of (e, p) pairs: the arithmetic of the fused form, one launch.
 // Tensor descriptors travel BY VALUE in the kernel arguments (gradients are fresh allocations every step: a device table would need a
 // staging buffer and an upload per step); a list longer than one table takes several launches.  The workgroup -> (tensor, chunk) map is a
 // binary search over a prefix array in the same arguments: wave-uniform, scalar loads only.  No atomics: two runs give the same bits.
@@ -23,7 +26,9 @@ constexpr int kThreads = 256;
 constexpr int kSlots = 4;                                  // float4 per thread and chunk
 constexpr int kChunk = kThreads * 4 * kSlots;              // 4096 elements per workgroup
 constexpr int kNormT = 128;                                // tensors per sumsq / scale launch   (2.6 KB of arguments)
-constexpr int kAdamT = 64;                                 // tensors per adam launch            (3.4 KB of arguments)
+constexpr int kAdamT = 56;                                 // tensors per adam launch            (3.4 KB of arguments)
+constexpr int kEmaT = 96;                                  // tensors per standalone ema launch  (2.7 KB of arguments)
+constexpr int kRuns = 4;                                   // runs of equal decoupled decay factors per adam launch
 constexpr int kMaxPartials = 4096;                         // sumsq workgroups take several chunks each beyond this many
 constexpr int kMaxGrid = 1 << 30;
 
@@ -34,14 +39,23 @@ struct NormArgs {
   int nt;
   int per;                                                 // chunks per workgroup (sumsq), 1 for scale
 };
-struct AdamTensor { float* p; const float* g; float* m; float* v; i64 n; float step_size, bc2_sqrt; };
+struct AdamTensor { float* p; const float* g; float* m; float* v; float* e; i64 n; float step_size, bc2_sqrt; };      // e: NULL = no average
 struct AdamArgs {
   AdamTensor t[kAdamT];
   int first[kAdamT + 1];
   int nt;
 };
-struct Hyper { double w1, b2, w2, wd, max_norm; float eps; };      // w1 = 1 - beta1, w2 = 1 - beta2, formed from the caller's doubles
-static_assert(sizeof(NormArgs) <= 3072 && sizeof(AdamArgs) + sizeof(Hyper) <= 3584, "kernel arguments stay well inside 4 KB");
+// w1 = 1 - beta1, w2 = 1 - beta2, formed from the caller's doubles; tensors run_first[r] .. run_first[r + 1] - 1 of the launch multiply p by
+// decay[r] = 1 - lr wd before the update (1.0: no decoupled decay); ema_w = 1 - d of the average; skip: a non-finite norm leaves everything alone
+struct Hyper { double w1, b2, w2, wd, max_norm, ema_w, decay[kRuns]; float eps; int run_first[kRuns + 1]; int nruns; int skip; };
+struct EmaArgs {
+  float* e[kEmaT];
+  const float* p[kEmaT];
+  i64 n[kEmaT];
+  int first[kEmaT + 1];
+  int nt;
+};
+static_assert(sizeof(NormArgs) <= 3072 && sizeof(EmaArgs) <= 3072 && sizeof(AdamArgs) + sizeof(Hyper) <= 3584, "kernel arguments stay well inside 4 KB");
 
 // largest i with first[i] <= b: b is blockIdx.x, so the whole search runs on the scalar unit
 template <int N> __device__ __forceinline__ int locate(const int (&first)[N], int nt, int b) {
@@ -107,8 +121,10 @@ __device__ __forceinline__ double clip_coef(const double* __restrict__ partial, 
 }
 
 // PyTorch's Adam for one element; g, m and v in double (the fp64 rate is no limit behind 28 bytes of traffic per element), each state
-// rounded once when stored; the quotient in fp32 from the stored values
-__device__ __forceinline__ void adam1(float graw, float& p, float& m, float& v, double coef, const Hyper& h, float step_size, float bc2_sqrt) {
+// rounded once when stored; the quotient in fp32 from the stored values.  dec != 1: AdamW's p *= 1 - lr wd comes first, in double, and
+// p' is rounded once from p dec - delta (delta the fp32 quotient term); dec == 1 is the fp32 subtraction of the L2 form, bit for bit.
+__device__ __forceinline__ void adam1(float graw, float& p, float& m, float& v, double coef, const Hyper& h, double dec, float step_size,
+                                      float bc2_sqrt) {
   double g = coef * (double)graw;
   if (h.wd != 0.0) g += h.wd * (double)p;
   const double md = (double)m + (g - (double)m) * h.w1;
@@ -116,24 +132,55 @@ __device__ __forceinline__ void adam1(float graw, float& p, float& m, float& v, 
   m = (float)md;
   v = (float)vd;
   const float den = sqrtf(v) / bc2_sqrt + h.eps;
-  p = p - step_size * (m / den);
+  if (dec == 1.0) {
+    p = p - step_size * (m / den);
+  } else {
+    const float delta = step_size * (m / den);
+    p = (float)((double)p * dec - (double)delta);
+  }
 }
 
+// the moving average of one element from the p just stored: e + (p - e) w in double, every operation rounded by itself (no fused
+// multiply-add: torch's float64 operations on the same values give the same bits), the result rounded once to fp32
+__device__ __forceinline__ float ema1(float e, float p, double w) {
+#pragma clang fp contract(off)
+  const double d = ((double)p - (double)e) * w;
+  return (float)((double)e + d);
+}
+
+__device__ __forceinline__ bool nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// np >= 0: the norm comes from the partial sums (first: workgroup 0 stores it).  np < 0: no clip; with h.skip the norm of an earlier
+// dod_optim_clip_grad_norm over the whole list is read from total_norm.  A skipped step returns before any store to p, m, v, e; the
+// counter has one writer (thread 0 of workgroup 0 of the first launch): a plain load and store.
+template <bool kEma>
 __global__ __launch_bounds__(kThreads) void optim_adam_kernel(const AdamArgs a, const Hyper h, const double* __restrict__ partial, int np,
-                                                              float* __restrict__ total_norm, int store_norm) {
+                                                              float* __restrict__ total_norm, int first, int* __restrict__ skipped) {
   __shared__ double s[kThreads];
   const int b = blockIdx.x, t = locate(a.first, a.nt, b), tid = threadIdx.x;
   double coef = 1.0;
-  if (np >= 0) {
+  if (np >= 0 || h.skip) {
     float nf;
-    coef = clip_coef(partial, np, h.max_norm, s, &nf);
-    if (store_norm && b == 0 && tid == 0) *total_norm = nf;
+    if (np >= 0) {
+      coef = clip_coef(partial, np, h.max_norm, s, &nf);
+      if (first && b == 0 && tid == 0) *total_norm = nf;
+    } else {
+      nf = *total_norm;
+    }
+    if (h.skip && nonfinite(nf)) {
+      if (first && b == 0 && tid == 0 && skipped) *skipped = *skipped + 1;
+      return;
+    }
   }
   const AdamTensor T = a.t[t];
+  int r = 0;
+  while (r + 1 < h.nruns && h.run_first[r + 1] <= t) ++r;
+  const double dec = h.decay[r];
+  const bool ema = kEma && T.e != nullptr;
   const i64 n = T.n, base = (i64)(b - a.first[t]) * kChunk;
-  const bool vec = ((((uintptr_t)T.p) | ((uintptr_t)T.g) | ((uintptr_t)T.m) | ((uintptr_t)T.v)) & 15) == 0;
+  const bool vec = ((((uintptr_t)T.p) | ((uintptr_t)T.g) | ((uintptr_t)T.m) | ((uintptr_t)T.v) | (ema ? (uintptr_t)T.e : 0)) & 15) == 0;
   if (vec) {
-    float4 G[kSlots], P[kSlots], M[kSlots], V[kSlots];
+    float4 G[kSlots], P[kSlots], M[kSlots], V[kSlots], E[kEma ? kSlots : 1];
     bool full[kSlots];
 #pragma unroll
     for (int k = 0; k < kSlots; ++k) {
@@ -144,24 +191,31 @@ __global__ __launch_bounds__(kThreads) void optim_adam_kernel(const AdamArgs a, 
         P[k] = *reinterpret_cast<const float4*>(T.p + e);
         M[k] = *reinterpret_cast<const float4*>(T.m + e);
         V[k] = *reinterpret_cast<const float4*>(T.v + e);
+        if constexpr (kEma) if (ema) E[k] = *reinterpret_cast<const float4*>(T.e + e);
       }
     }
 #pragma unroll
     for (int k = 0; k < kSlots; ++k) {
       const i64 e = base + ((i64)k * kThreads + tid) * 4;
       if (full[k]) {
-        adam1(G[k].x, P[k].x, M[k].x, V[k].x, coef, h, T.step_size, T.bc2_sqrt);
-        adam1(G[k].y, P[k].y, M[k].y, V[k].y, coef, h, T.step_size, T.bc2_sqrt);
-        adam1(G[k].z, P[k].z, M[k].z, V[k].z, coef, h, T.step_size, T.bc2_sqrt);
-        adam1(G[k].w, P[k].w, M[k].w, V[k].w, coef, h, T.step_size, T.bc2_sqrt);
+        adam1(G[k].x, P[k].x, M[k].x, V[k].x, coef, h, dec, T.step_size, T.bc2_sqrt);
+        adam1(G[k].y, P[k].y, M[k].y, V[k].y, coef, h, dec, T.step_size, T.bc2_sqrt);
+        adam1(G[k].z, P[k].z, M[k].z, V[k].z, coef, h, dec, T.step_size, T.bc2_sqrt);
+        adam1(G[k].w, P[k].w, M[k].w, V[k].w, coef, h, dec, T.step_size, T.bc2_sqrt);
         *reinterpret_cast<float4*>(T.p + e) = P[k];
         *reinterpret_cast<float4*>(T.m + e) = M[k];
         *reinterpret_cast<float4*>(T.v + e) = V[k];
+        if constexpr (kEma) if (ema) {
+          float4 x = E[k];
+          x.x = ema1(x.x, P[k].x, h.ema_w); x.y = ema1(x.y, P[k].y, h.ema_w); x.z = ema1(x.z, P[k].z, h.ema_w); x.w = ema1(x.w, P[k].w, h.ema_w);
+          *reinterpret_cast<float4*>(T.e + e) = x;
+        }
       } else {
         for (i64 i = e; i < n && i < e + 4; ++i) {      // the n mod 4 tail
           float p = T.p[i], m = T.m[i], v = T.v[i];
-          adam1(T.g[i], p, m, v, coef, h, T.step_size, T.bc2_sqrt);
+          adam1(T.g[i], p, m, v, coef, h, dec, T.step_size, T.bc2_sqrt);
           T.p[i] = p; T.m[i] = m; T.v[i] = v;
+          if (ema) T.e[i] = ema1(T.e[i], p, h.ema_w);
         }
       }
     }
@@ -169,9 +223,33 @@ __global__ __launch_bounds__(kThreads) void optim_adam_kernel(const AdamArgs a, 
     const i64 hi = base + kChunk < n ? base + kChunk : n;
     for (i64 i = base + tid; i < hi; i += kThreads) {
       float p = T.p[i], m = T.m[i], v = T.v[i];
-      adam1(T.g[i], p, m, v, coef, h, T.step_size, T.bc2_sqrt);
+      adam1(T.g[i], p, m, v, coef, h, dec, T.step_size, T.bc2_sqrt);
       T.p[i] = p; T.m[i] = m; T.v[i] = v;
+      if (ema) T.e[i] = ema1(T.e[i], p, h.ema_w);
     }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void optim_ema_kernel(const EmaArgs a, double w) {
+  const int b = blockIdx.x, t = locate(a.first, a.nt, b), tid = threadIdx.x;
+  float* __restrict__ e = a.e[t];
+  const float* __restrict__ p = a.p[t];
+  const i64 n = a.n[t], base = (i64)(b - a.first[t]) * kChunk, hi = base + kChunk < n ? base + kChunk : n;
+  if (((((uintptr_t)e) | ((uintptr_t)p)) & 15) == 0) {
+#pragma unroll
+    for (int k = 0; k < kSlots; ++k) {
+      const i64 i0 = base + ((i64)k * kThreads + tid) * 4;
+      if (i0 + 4 <= n) {
+        float4 x = *reinterpret_cast<const float4*>(e + i0);
+        const float4 y = *reinterpret_cast<const float4*>(p + i0);
+        x.x = ema1(x.x, y.x, w); x.y = ema1(x.y, y.y, w); x.z = ema1(x.z, y.z, w); x.w = ema1(x.w, y.w, w);
+        *reinterpret_cast<float4*>(e + i0) = x;
+      } else {
+        for (i64 i = i0; i < n && i < i0 + 4; ++i) e[i] = ema1(e[i], p[i], w);
+      }
+    }
+  } else {
+    for (i64 i = base + tid; i < hi; i += kThreads) e[i] = ema1(e[i], p[i], w);
   }
 }
 
@@ -270,10 +348,69 @@ int store_norm0(const char* who, float* total_norm_dev, hipStream_t s) {
   return launched(who);
 }
 
+// what both update entries run.  ema / decay: lists parallel to t, or NULL
+int run_step(const char* who, const dod_optim_tensor* t, float* const* ema, const double* decay, int n_tensors, const dod_optim_options& o,
+             void* ws, size_t ws_bytes, hipStream_t s) {
+  i64 total = 0;
+  if (int rc = check_list(who, t, n_tensors, true, &total)) return rc;
+  const bool clip = o.max_norm > 0.f, skip = o.skip_nonfinite != 0, ready = o.norm_ready != 0, norm = clip || (skip && !ready);
+  if (ready && (!skip || clip)) return ofail(DOD_ERR_INVALID, "%s: norm_ready goes with skip_nonfinite and max_norm <= 0 only", who);
+  if ((norm || skip) && !o.total_norm_dev) return ofail(DOD_ERR_INVALID, "%s: null total_norm_dev with max_norm > 0 or skip_nonfinite", who);
+  if (!(o.beta1 >= 0.0 && o.beta1 < 1.0 && o.beta2 >= 0.0 && o.beta2 < 1.0) || !(o.eps >= 0.f) || !(o.weight_decay >= 0.0) || !(o.max_norm == o.max_norm))
+    return ofail(DOD_ERR_INVALID, "%s: betas outside [0, 1), negative eps / weight_decay or a NaN max_norm", who);
+  if (ema && !(o.ema_w >= 0.0 && o.ema_w <= 1.0)) return ofail(DOD_ERR_INVALID, "%s: ema_w = %g outside [0, 1]", who, o.ema_w);
+  if (decay)
+    for (int i = 0; i < n_tensors; ++i)
+      if (!(decay[i] == decay[i])) return ofail(DOD_ERR_INVALID, "%s: tensor %d has a NaN decay factor", who, i);
+  if (total == 0) return norm ? store_norm0(who, o.total_norm_dev, s) : DOD_OK;
+  if (norm && (!ws || ws_bytes < ws_need(n_tensors, total)))
+    return ofail(DOD_ERR_INVALID, "%s: workspace of %zu bytes, %zu needed", who, ws ? ws_bytes : (size_t)0, ws_need(n_tensors, total));
+  double* partial = norm ? reinterpret_cast<double*>(dod::align_ws(ws)) : nullptr;
+  int np = -1;                                             // -1: no norm launch, the adam kernel skips the reduction
+  if (norm) if (int rc = run_sumsq(who, t, n_tensors, total, partial, &np, s)) return rc;
+  Hyper h;
+  h.w1 = 1.0 - o.beta1; h.b2 = o.beta2; h.w2 = 1.0 - o.beta2; h.wd = o.weight_decay; h.eps = o.eps; h.ema_w = o.ema_w; h.skip = skip;
+  h.max_norm = clip ? (double)o.max_norm : (double)INFINITY;      // the norm for the skip alone: the coefficient is 1
+  int i = 0, first_launch = 1;
+  while (i < n_tensors) {
+    AdamArgs a;
+    a.nt = 0; a.first[0] = 0;
+    h.nruns = 0;
+    for (int r = 0; r < kRuns; ++r) { h.decay[r] = 1.0; h.run_first[r] = 0; }
+    h.run_first[kRuns] = 0;
+    bool any_ema = false;
+    for (; i < n_tensors && a.nt < kAdamT; ++i) {
+      if (t[i].n == 0) continue;
+      const i64 c = chunks_of(t[i].n, kChunk);
+      if (a.first[a.nt] + c > kMaxGrid) break;
+      const double dec = decay ? decay[i] : 1.0;
+      if (h.nruns == 0 || dec != h.decay[h.nruns - 1]) {
+        if (h.nruns == kRuns) break;                       // a fifth decay factor: the next launch
+        h.decay[h.nruns] = dec; h.run_first[h.nruns] = a.nt;
+        ++h.nruns;
+      }
+      AdamTensor& d = a.t[a.nt];
+      d.p = t[i].p; d.g = t[i].g; d.m = t[i].m; d.v = t[i].v; d.e = ema ? ema[i] : nullptr; d.n = t[i].n;
+      d.step_size = t[i].step_size; d.bc2_sqrt = t[i].bc2_sqrt;
+      any_ema |= d.e != nullptr;
+      a.first[a.nt + 1] = a.first[a.nt] + (int)c;
+      ++a.nt;
+    }
+    if (!a.nt) continue;
+    if (any_ema)
+      hipLaunchKernelGGL(optim_adam_kernel<true>, dim3(a.first[a.nt]), dim3(kThreads), 0, s, a, h, partial, np, o.total_norm_dev, first_launch, o.skipped_dev);
+    else
+      hipLaunchKernelGGL(optim_adam_kernel<false>, dim3(a.first[a.nt]), dim3(kThreads), 0, s, a, h, partial, np, o.total_norm_dev, first_launch, o.skipped_dev);
+    if (int rc = launched(who)) return rc;
+    first_launch = 0;
+  }
+  return DOD_OK;
+}
+
 }  // namespace
 
 long optim_launch_count() { return g_launches.load(); }
-long optim_constant(int which) { return which == 0 ? kChunk : which == 1 ? kAdamT : kNormT; }
+long optim_constant(int which) { return which == 0 ? kChunk : which == 1 ? kAdamT : which == 2 ? kNormT : kEmaT; }
 
 extern "C" {
 
@@ -318,39 +455,47 @@ int dod_optim_clip_grad_norm(const dod_optim_tensor* t, int n_tensors, float max
 
 int dod_optim_adam_step(const dod_optim_tensor* t, int n_tensors, double beta1, double beta2, float eps, double weight_decay, float max_norm,
                         float* total_norm_dev, void* ws, size_t ws_bytes, void* stream) {
-  static const char* who = "dod_optim_adam_step";
-  i64 total = 0;
-  if (int rc = check_list(who, t, n_tensors, true, &total)) return rc;
-  const bool clip = max_norm > 0.f;
-  if (clip && !total_norm_dev) return ofail(DOD_ERR_INVALID, "%s: null total_norm_dev with max_norm > 0", who);
-  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.f) || !(weight_decay >= 0.0) || !(max_norm == max_norm))
-    return ofail(DOD_ERR_INVALID, "%s: betas outside [0, 1), negative eps / weight_decay or a NaN max_norm", who);
+  dod_optim_options o = {};
+  o.beta1 = beta1; o.beta2 = beta2; o.weight_decay = weight_decay; o.eps = eps; o.max_norm = max_norm; o.total_norm_dev = total_norm_dev;
+  return run_step("dod_optim_adam_step", t, nullptr, nullptr, n_tensors, o, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int dod_optim_step(const dod_optim_tensor* t, float* const* ema, const double* decay, int n_tensors, const dod_optim_options* o, void* ws,
+                   size_t ws_bytes, void* stream) {
+  static const char* who = "dod_optim_step";
+  if (!o) return ofail(DOD_ERR_INVALID, "%s: null options", who);
+  if (ema && n_tensors > 0)
+    for (int i = 0; i < n_tensors; ++i)
+      if (ema[i] && t && t[i].n > 0 && (ema[i] == t[i].p || ema[i] == t[i].m || ema[i] == t[i].v))
+        return ofail(DOD_ERR_INVALID, "%s: the average of tensor %d aliases its parameter or state", who, i);
+  return run_step(who, t, ema, decay, n_tensors, *o, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int dod_optim_ema_update(const dod_optim_ema_tensor* t, int n_tensors, double w, void* stream) {
+  static const char* who = "dod_optim_ema_update";
+  if (n_tensors < 0) return ofail(DOD_ERR_INVALID, "%s: n_tensors = %d is negative", who, n_tensors);
+  if (n_tensors > 0 && !t) return ofail(DOD_ERR_INVALID, "%s: null tensor list", who);
+  if (!(w >= 0.0 && w <= 1.0)) return ofail(DOD_ERR_INVALID, "%s: w = %g outside [0, 1]", who, w);
+  for (int i = 0; i < n_tensors; ++i) {
+    if (t[i].n < 0) return ofail(DOD_ERR_INVALID, "%s: tensor %d has n = %lld", who, i, (long long)t[i].n);
+    if (t[i].n > (i64)kChunk * kMaxGrid) return ofail(DOD_ERR_INVALID, "%s: tensor %d has more than 2^42 elements", who, i);
+    if (t[i].n > 0 && (!t[i].e || !t[i].p)) return ofail(DOD_ERR_INVALID, "%s: tensor %d has a null pointer", who, i);
+  }
   hipStream_t s = (hipStream_t)stream;
-  if (total == 0) return clip ? store_norm0(who, total_norm_dev, s) : DOD_OK;
-  if (clip && (!ws || ws_bytes < ws_need(n_tensors, total)))
-    return ofail(DOD_ERR_INVALID, "%s: workspace of %zu bytes, %zu needed", who, ws ? ws_bytes : (size_t)0, ws_need(n_tensors, total));
-  double* partial = clip ? reinterpret_cast<double*>(dod::align_ws(ws)) : nullptr;
-  int np = -1;                                             // -1: no clip, the adam kernel skips the reduction
-  if (clip) if (int rc = run_sumsq(who, t, n_tensors, total, partial, &np, s)) return rc;
-  Hyper h;
-  h.w1 = 1.0 - beta1; h.b2 = beta2; h.w2 = 1.0 - beta2; h.wd = weight_decay; h.max_norm = (double)max_norm; h.eps = eps;
-  int i = 0, first_launch = 1;
+  int i = 0;
   while (i < n_tensors) {
-    AdamArgs a;
+    EmaArgs a;
     a.nt = 0; a.first[0] = 0;
-    for (; i < n_tensors && a.nt < kAdamT; ++i) {
+    for (; i < n_tensors && a.nt < kEmaT; ++i) {
       if (t[i].n == 0) continue;
       const i64 c = chunks_of(t[i].n, kChunk);
       if (a.first[a.nt] + c > kMaxGrid) break;
-      AdamTensor& d = a.t[a.nt];
-      d.p = t[i].p; d.g = t[i].g; d.m = t[i].m; d.v = t[i].v; d.n = t[i].n; d.step_size = t[i].step_size; d.bc2_sqrt = t[i].bc2_sqrt;
-      a.first[a.nt + 1] = a.first[a.nt] + (int)c;
+      a.e[a.nt] = t[i].e; a.p[a.nt] = t[i].p; a.n[a.nt] = t[i].n; a.first[a.nt + 1] = a.first[a.nt] + (int)c;
       ++a.nt;
     }
     if (!a.nt) continue;
-    hipLaunchKernelGGL(optim_adam_kernel, dim3(a.first[a.nt]), dim3(kThreads), 0, s, a, h, partial, np, total_norm_dev, first_launch);
+    hipLaunchKernelGGL(optim_ema_kernel, dim3(a.first[a.nt]), dim3(kThreads), 0, s, a, w);
     if (int rc = launched(who)) return rc;
-    first_launch = 0;
   }
   return DOD_OK;
 }

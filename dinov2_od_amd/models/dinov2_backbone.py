@@ -156,6 +156,14 @@ class _EngineMixin:
             self.__dict__["_engine"] = eng
         return eng
 
+    def __getstate__(self):
+        """copy.deepcopy / pickle (torch.save(model), DataLoader workers): the engine owns a ctypes handle to device memory and the
+        named cache points at this tree's tensors, so neither travels; the copy builds its own lazily, at its first forward"""
+        state = self.__dict__.copy()
+        state.pop("_engine", None)
+        state.pop("_named_cache", None)
+        return state
+
     def _use_autograd(self, x=None):
         """train() mode -> the autograd composite (models/_autograd.py): the native kernels have no backward yet
         (SURVEY.md section 8f-1).  eval() mode is always native.  Like the native path the composite is GPU-only: a CPU

@@ -997,7 +997,7 @@ int dod_op_colsum_add(const float* src, int ld, int rows, int cols, float* dst, 
  * whose gradient was None on some step has a smaller t).  g, m and v are evaluated in double and rounded once when stored.
  * beta1 / beta2 / weight_decay are doubles: 1 - (float)0.999 is 1.3e-5 away from 0.001, 36 times the bound on v by itself, and where
  * coef * g_raw and weight_decay * p cancel, a rounded weight_decay would leave g with no correct digit.
- * The tensor descriptors travel in the kernel arguments: a list longer than one argument table (64 tensors for the update, 128
+ * The tensor descriptors travel in the kernel arguments: a list longer than one argument table (56 tensors for the update, 128
  * for the norm) takes more launches; tensors with n = 0 are skipped.  16-byte accesses where all pointers of a tensor are
  * 16-byte aligned, 4-byte ones otherwise and for the n mod 4 tail; nothing past n is read or written.  No atomics: two runs of
  * the same input give the same bits.  Everything is enqueued on `stream`; no synchronisation, no allocation.
@@ -1018,6 +1018,40 @@ int dod_optim_clip_grad_norm(const dod_optim_tensor* t, int n_tensors, float max
 int dod_optim_adam_step(const dod_optim_tensor* t, int n_tensors, double beta1, double beta2, float eps, double weight_decay, float max_norm,
                         float* total_norm_dev, void* ws, size_t ws_bytes, void* stream);
 const char* dod_optim_last_error(void);
+
+/* ---- the same step with decoupled weight decay (AdamW), a fused moving average of the weights and a skip on a non-finite norm ----
+ * dod_optim_step is dod_optim_adam_step (above: lists, workspace, alignment, errors, determinism) plus three things, each optional.
+ *   decay    NULL, or one double per tensor: p is multiplied by decay[i] = 1 - lr * weight_decay BEFORE the Adam update (PyTorch's
+ *            AdamW order), with options.weight_decay = 0.  A double, because 1 - 1e-8 is 1.0f.  With delta = step_size * m' / den the
+ *            fp32 term of the L2 form, p' = (float)((double)p * decay[i] - (double)delta): rounded once.  decay[i] == 1.0 is the L2
+ *            form's fp32 subtraction bit for bit.  A launch holds 4 runs of equal consecutive factors; a fifth starts another launch.
+ *   ema      NULL, or one pointer per tensor (NULL entries allowed): the thread that stores p' also stores
+ *            e' = (float)((double)e + ((double)p' - (double)e) * ema_w), ema_w = 1 - d a double (1 - (float)0.9999 is 3e-4 relative away
+ *            from 1e-4), p' the fp32 value just stored, every double operation rounded by itself (no fused multiply-add, so float64
+ *            arithmetic on the host gives the same bits).  The 16-byte path needs all five pointers aligned.  e must not alias p, m, v.
+ *   skip_nonfinite  the norm launch runs even with max_norm <= 0 (coefficient 1 then), and when the fp32 total_norm is inf or NaN every
+ *            workgroup returns before any store: p, m, v and e keep their bits.  total_norm is still stored, and thread 0 of workgroup 0
+ *            of the first update launch adds 1 to *skipped_dev (int32, may be NULL; one writer, a plain load and store).
+ *            norm_ready = 1 (with skip_nonfinite and max_norm <= 0): no norm launch; *total_norm_dev already holds the norm of an earlier
+ *            dod_optim_clip_grad_norm over the WHOLE list and is only read -- for several dod_optim_step calls that share one norm; pass
+ *            skipped_dev to one of them.
+ * With decay and ema NULL and skip_nonfinite 0 the call IS dod_optim_adam_step.  dod_optim_ema_update is the average alone over a list
+ * of (e, p, n), the same arithmetic in one launch per 96 tensors ("optim_ema_table_tensors"): for tensors that had no gradient this step
+ * and for callers with another optimizer.  Additional DOD_ERR_INVALID: NULL options, ema_w or w outside [0, 1], a NaN decay factor, an
+ * average that aliases its tensor, norm_ready without skip_nonfinite or with max_norm > 0. */
+typedef struct dod_optim_options {
+  double beta1, beta2;
+  double weight_decay;          /* L2: added to the gradient; 0 with a decay list */
+  double ema_w;                 /* 1 - d; read only with an ema list */
+  float eps, max_norm;          /* max_norm <= 0: no clip */
+  int32_t skip_nonfinite, norm_ready;
+  float* total_norm_dev;        /* needed with max_norm > 0 or skip_nonfinite */
+  int32_t* skipped_dev;
+} dod_optim_options;
+typedef struct dod_optim_ema_tensor { float* e; const float* p; int64_t n; } dod_optim_ema_tensor;
+int dod_optim_step(const dod_optim_tensor* t, float* const* ema, const double* decay, int n_tensors, const dod_optim_options* options,
+                   void* ws, size_t ws_bytes, void* stream);
+int dod_optim_ema_update(const dod_optim_ema_tensor* t, int n_tensors, double w, void* stream);
 
 /* Scratch of the GEMMs' wave-quantisation tail split (K-split partial slabs; gemm_pp.hip) and of the fp32 GEMM's K split (gemm_f32.hip, fixed size).  dod_finalize_weights reserves 64 MiB on the
  * current device; operator-level callers (tests, tools) reserve it themselves.  Never allocated inside a forward / stream capture. */
@@ -1123,6 +1157,8 @@ const char* dod_version(void);
  * Revision 7: the packed-operand accessor (dod_test_packed_info, dod_test_packed_copy, struct dod_packed_info) -- additive like the above, but it
  * publishes the layout of what dod_finalize_weights keeps (the dod_packed_format / dod_packed_array numbering), which a tool built against this
  * header reads through the struct: the revision is raised so that such a tool and the library agree on it.
+ * dod_optim_step and dod_optim_ema_update (with struct dod_optim_options and struct dod_optim_ema_tensor, which no earlier entry reads)
+ * joined revision 7 by name: no earlier signature or layout moved.
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 7
 int dod_abi_version(void);

@@ -4,10 +4,17 @@ layer: 57 tensors, 55 of them with a gradient, 5.6 M fp32 elements; synth weight
     torch       clip_grad_norm_(params, 1.0) + torch.optim.Adam(lr 1e-4, weight_decay 1e-4).step()    what the reference runs
     torch_fused the same with Adam(fused=True)
     native      dinov2_od_amd.optim.Adam(max_grad_norm=1.0).step()                                    two launches (csrc/optim.hip)
-One hipEvent pair per step on the compute stream; the three legs alternate step by step, each on its own copy of the parameters;
+and the same with decoupled weight decay and an exponential moving average (decay 0.9999) of the trainable set:
+    torch_adamw / torch_adamw_fused          clip_grad_norm_ + torch.optim.AdamW(fused=...).step()
+    torch_adamw_ema / torch_adamw_fused_ema  ... followed by torch._foreach_lerp_(shadows, params, 1e-4)
+    native_adamw                             optim.AdamW(max_grad_norm=1.0).step()
+    native_adamw_ema_fused                   optim.AdamW(max_grad_norm=1.0, ema=ModelEMA(...)).step(): the update launch writes the shadows
+    native_adamw_ema_standalone              optim.AdamW(max_grad_norm=1.0).step() + ModelEMA.update(): one more launch
+One hipEvent pair per step on the compute stream; the legs alternate step by step, each on its own copy of the parameters;
 the gradients are restored from a master copy before every step, outside the events (PyTorch's clip scales them in place).
-Median and p10 / p90 over --steps steps after --warmup; for the native leg also the bytes the arithmetic needs (one read of g for
-the norm; one read of g, p, m, v and one write of p, m, v for the update) over the median.  One JSON line on stdout.
+Median and p10 / p90 over --steps steps after --warmup; for the native legs also the bytes the arithmetic needs (one read of g for
+the norm; one read of g, p, m, v and one write of p, m, v for the update; one read and write of e for the average, and a read of p
+more where the average is a launch of its own) over the median.  One JSON line on stdout.
     python tools/bench_optim.py [--steps 100] [--warmup 10]"""
 import argparse
 import json
@@ -51,10 +58,14 @@ def main():
     hyp = dict(lr=1e-4, weight_decay=1e-4)
 
     def leg(make, clip):
-        params = [torch.nn.Parameter(t.clone()) for _, t in named]
+        """make(params, holder) -> optimizer, or (optimizer, what follows its step inside the timed window)"""
+        holder = torch.nn.Module()
+        holder.list = torch.nn.ParameterList([torch.nn.Parameter(t.clone()) for _, t in named])
+        params = list(holder.list)
         for p, g in zip(params, master):
             p.grad = None if g is None else g.clone()
-        opt = make(params)
+        made = make(params, holder)
+        opt, after = made if isinstance(made, tuple) else (made, None)
 
         def restore():
             for p, g in zip(params, master):
@@ -65,11 +76,30 @@ def main():
             if clip:
                 torch.nn.utils.clip_grad_norm_(params, 1.0)
             opt.step()
+            if after is not None:
+                after()
         return restore, step, params
 
-    legs = {"torch": leg(lambda ps: torch.optim.Adam(ps, **hyp), True),
-            "torch_fused": leg(lambda ps: torch.optim.Adam(ps, fused=True, **hyp), True),
-            "native": leg(lambda ps: optim.Adam(ps, max_grad_norm=1.0, **hyp), False)}
+    def with_lerp(cls, **kw):
+        def make(ps, holder):
+            shadows = [p.detach().clone() for p in ps]
+            return cls(ps, **kw, **hyp), lambda: torch._foreach_lerp_(shadows, [p.detach() for p in ps], 1e-4)
+        return make
+
+    def native_then_update(ps, holder):
+        ema = optim.ModelEMA(holder, decay=0.9999)
+        return optim.AdamW(ps, max_grad_norm=1.0, **hyp), ema.update
+
+    legs = {"torch": leg(lambda ps, h: torch.optim.Adam(ps, **hyp), True),
+            "torch_fused": leg(lambda ps, h: torch.optim.Adam(ps, fused=True, **hyp), True),
+            "native": leg(lambda ps, h: optim.Adam(ps, max_grad_norm=1.0, **hyp), False),
+            "torch_adamw": leg(lambda ps, h: torch.optim.AdamW(ps, **hyp), True),
+            "torch_adamw_fused": leg(lambda ps, h: torch.optim.AdamW(ps, fused=True, **hyp), True),
+            "torch_adamw_ema": leg(with_lerp(torch.optim.AdamW), True),
+            "torch_adamw_fused_ema": leg(with_lerp(torch.optim.AdamW, fused=True), True),
+            "native_adamw": leg(lambda ps, h: optim.AdamW(ps, max_grad_norm=1.0, **hyp), False),
+            "native_adamw_ema_fused": leg(lambda ps, h: optim.AdamW(ps, max_grad_norm=1.0, ema=optim.ModelEMA(h, decay=0.9999), **hyp), False),
+            "native_adamw_ema_standalone": leg(native_then_update, False)}
     before = _native.lib().dod_test_counter(b"optim_launches")
     ms = {k: [] for k in legs}
     for it in range(a.warmup + a.steps):
@@ -84,17 +114,26 @@ def main():
                 ms[name].append(s.elapsed_time(e))
     launches = (_native.lib().dod_test_counter(b"optim_launches") - before) / (a.warmup + a.steps)
     n_grad = sum(g.numel() for g in master if g is not None)
+    n_all = sum(t.numel() for _, t in named)
     nbytes = 4 * n_grad * (1 + 4 + 3)
+    native_bytes = {"native": nbytes, "native_adamw": nbytes, "native_adamw_ema_fused": nbytes + 4 * 2 * n_all,
+                    "native_adamw_ema_standalone": nbytes + 4 * 3 * n_all}
     out = {"tool": "bench_optim", "device": torch.cuda.get_device_name(0), "torch_version": torch.__version__, "tensors": len(named),
-           "tensors_with_grad": sum(g is not None for g in master), "elements_with_grad": n_grad, "native_launches_per_step": launches,
-           "native_bytes_per_step": nbytes}
+           "tensors_with_grad": sum(g is not None for g in master), "elements_with_grad": n_grad,
+           "native_launches_per_step_all_native_legs": launches, "native_bytes_per_step": nbytes}
     for k in legs:
         out[k] = _stats(ms[k])
-    out["native"]["achieved_GBps"] = round(nbytes / (out["native"]["median_ms"] * 1e-3) / 1e9, 1)
-    # the three legs saw the same gradients from the same start: their parameters agree to fp32 rounding of the same formula
+    for k, nb in native_bytes.items():
+        out[k]["bytes_per_step"] = nb
+        out[k]["achieved_GBps"] = round(nb / (out[k]["median_ms"] * 1e-3) / 1e9, 1)
+    # the legs of one family saw the same gradients from the same start: their parameters agree to fp32 rounding of the same formula
     ref = legs["torch"][2]
     for k in ("torch_fused", "native"):
         out[k]["max_abs_diff_vs_torch"] = float(max((p.detach() - q.detach()).abs().max() for p, q in zip(legs[k][2], ref)))
+    ref = legs["torch_adamw"][2]
+    for k in legs:
+        if "adamw" in k and k != "torch_adamw":
+            out[k]["max_abs_diff_vs_torch_adamw"] = float(max((p.detach() - q.detach()).abs().max() for p, q in zip(legs[k][2], ref)))
     print(json.dumps(out))
 
 
