@@ -17,4 +17,7 @@ def __getattr__(name):
     if name in ("draw_detections", "log_images", "save_images"):      # dinov2_od_amd.visualize: boxes drawn into the batch on the GPU
         import importlib
         return getattr(importlib.import_module(".visualize", __name__), name)
+    if name in ("Tracker", "TrackedDetections"):      # dinov2_od_amd.tracking: ByteTrack association on the GPU behind detect
+        import importlib
+        return getattr(importlib.import_module(".tracking", __name__), name)
     raise AttributeError(name)

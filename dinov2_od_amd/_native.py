@@ -110,6 +110,13 @@ class DodDrawStyle(C.Structure):
                 ("palette", C.c_void_p), ("names", C.c_void_p), ("n_names", C.c_int32), ("name_len", C.c_int32), ("font", C.c_void_p)]
 
 
+class DodTrackParams(C.Structure):
+    """struct dod_track_params (include/dinodet.h): the thresholds of dod_track_update"""
+    _fields_ = [("track_thresh", C.c_float), ("low_thresh", C.c_float), ("new_thresh", C.c_float), ("match_thresh", C.c_float),
+                ("second_thresh", C.c_float), ("tentative_thresh", C.c_float), ("max_age", C.c_int32), ("fuse_score", C.c_int32),
+                ("class_aware", C.c_int32)]
+
+
 # include/dinodet_tuning.h: exported by -DDINODET_TUNING builds only (tools/ load one through DINODET_LIB); bound when present
 TUNING_SYMBOLS = {
     "dod_debug_gemm_stamps": (_I, [_P]),
@@ -194,6 +201,11 @@ SYMBOLS = {
     "dod_match_cost": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P]),
     "dod_match_assign_workspace_bytes": (_SZ, [_I, _I, _I]),
     "dod_match_assign": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _SZ, _P]),
+    "dod_track_state_bytes": (_SZ, [_I, _I]),
+    "dod_track_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "dod_track_reset": (_I, [_P, _I, _I, _P, _P]),
+    "dod_track_update": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, C.POINTER(DodTrackParams), _P, _P, _P, _SZ, _P]),
+    "dod_track_export": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dod_coco_eval_workspace_bytes": (_SZ, [_I64, _I, _I, _I64]),
     "dod_coco_eval_set_gt": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dod_coco_eval_reset": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P]),

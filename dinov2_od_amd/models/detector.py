@@ -90,6 +90,12 @@ class DINOv2ObjectDetector(_EngineMixin, nn.Module):   # state-dict keys already
         finally:
             self.train(was_training)
 
+    def track(self, pixel_values, tracker, sizes=None, **kw):
+        """`detect(pixel_values, sizes, **kw)` followed by `tracker.update`: image b of the batch is the next frame of the tracker's
+        stream b (tracking.Tracker with num_streams = the batch size).  Returns tracking.TrackedDetections: the Detections plus the track
+        id and the filtered box of every row.  No host sync."""
+        return tracker.update(self.detect(pixel_values, sizes, **kw))
+
     def detect_sliced(self, images, size=None, tile=None, overlap=0.2, full_view=True, flip=False, max_batch=64, **kw):
         """raw uint8 RGB images [H_i, W_i, 3] (as `preprocess_batch` takes them) -> slicing.SlicedDetections in each image's own
         pixels: the model runs on the whole image (full_view), on overlapping tiles of `tile` source pixels a side (slicing.plan_views;

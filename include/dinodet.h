@@ -687,6 +687,71 @@ size_t dod_match_assign_workspace_bytes(int B, int Q, int G);
 int dod_match_assign(const float* cost, const int32_t* gt_offsets, int B, int Q, int G, const int64_t* labels, int C,
                      int32_t* match, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- multi-object tracking on device: ByteTrack association behind dod_detect -----------------------------------------
+ * One launch per frame for S independent streams (cameras), the track table resident on the device: no host sync, no allocation,
+ * no global atomics, the result a function of the input bits.  It equals the numpy + scipy restatement in tests/track_cases.py
+ * bit for bit.  A tracker owns S streams of T slots each (S >= 1, T in 1..512); a frame brings K <= 1024 rows per stream, the
+ * tensors dod_detect writes: scores fp32 [S, K], labels int32 [S, K], boxes fp32 [S, K, 4] pixel xyxy, counts int32 [S].
+ * A slot is FREE (0), TENTATIVE (1), TRACKED (2) or LOST (3).  Every stream keeps frame (0 after reset), next_id (1 after reset:
+ * the first id is 1) and an overflow counter.  One update of stream s does, in this order:
+ *   0. frame += 1.  Row j < counts[s] (counts clamped to 0..K) is VALID when its score and four coordinates are finite and
+ *      x2 > x1, y2 > y1, compared in fp32; every other row is ignored and gets id -1.  The measurement, in double from the widened
+ *      fp32 values:  w = x2 - x1, h = y2 - y1, z = (x1 + 0.5 w, y1 + 0.5 h, w / h, h).
+ *   1. Predict every TRACKED, LOST and TENTATIVE slot; a LOST slot's velocity of h is set to 0 first, as ByteTrack does.  The
+ *      filter is ByteTrack's constant-velocity Kalman filter over (cx, cy, a, h), std weights 1/20 and 1/160, aspect-ratio constants
+ *      1e-2 / 1e-5 / 1e-1, carried in its block form: with a diagonal initial covariance and diagonal noise the 8 x 8 covariance
+ *      never leaves four independent 2 x 2 blocks (p, c, v) = (var x, cov(x, x'), var x'), and the innovation is a scalar per component:
+ *        predict  q_p = (h/20)^2, q_v = (h/160)^2 from h BEFORE the step (component a: 1e-2^2, 1e-5^2);
+ *                 x += x';  p = (((p + c) + c) + v) + q_p;  c = c + v;  v = v + q_v          (p from the old c and v, c from the old v)
+ *        update   r = (h/20)^2 from the predicted h (component a: 1e-1^2);  s = p + r;  k_p = p / s;  k_v = c / s;  y = z - x;
+ *                 x += k_p y;  x' += k_v y;  p -= (k_p k_p) s;  c -= (k_p k_v) s;  v -= (k_v k_v) s
+ *        init     x = z, x' = 0, p = (2 h/20)^2, c = 0, v = (10 h/160)^2 from the measured h (component a: 1e-2^2, 1e-5^2)
+ *      all in double, every operation rounded once (no FMA contraction), in the order tests/track_cases.py spells out.
+ *   2. high = the valid rows with score > track_thresh, low = those with low_thresh < score <= track_thresh, both in row order.
+ *   3. First association: rows = the TRACKED and LOST slots in slot order, columns = high.  cost = 1 - iou * score with fuse_score,
+ *      else 1 - iou, in double, narrowed once to fp32.  iou is taken between the slot's predicted mean as xyxy (w = a h, x1 = cx - 0.5 w,
+ *      y1 = cy - 0.5 h, x2 = cx + 0.5 w, y2 = cy + 0.5 h) and the row's box: widths and heights clamped at 0, union = (area_a + area_b) -
+ *      inter, 0 unless union > 0; with class_aware it counts as 0 when the slot's label differs from the row's.  The rectangular
+ *      problem is solved exactly as scipy.optimize.linear_sum_assignment solves the fp32 matrix (the solver of dod_match_assign, ties
+ *      included); pairs with cost <= match_thresh (fp32) are kept.  A kept pair is a HIT: Kalman update, state TRACKED, last_frame =
+ *      frame, the slot takes the row's score and label, the row gets the slot's id.
+ *   4. Second association: the TRACKED slots (not LOST) still without a hit against low, cost 1 - iou, threshold second_thresh.
+ *      Slots still without a hit become LOST.
+ *   5. Tentative: the TENTATIVE slots against the high rows left over from step 3, threshold tentative_thresh, fuse_score as in
+ *      step 3.  Hits become TRACKED, misses FREE.
+ *   6. Expire: a LOST slot with frame - last_frame > max_age becomes FREE.
+ *   7. Birth: every high row still without a slot and with score >= new_thresh takes the lowest FREE slot, in row order: filter
+ *      initialised from z, id = next_id++, score, label, last_frame = frame.  At frame 1 the state is TRACKED and the row gets the id;
+ *      later the state is TENTATIVE and the row keeps -1.  Without a free slot the row is dropped and overflow += 1.
+ * A slot that becomes FREE keeps its other fields until a birth overwrites them: only `state` says whether they mean anything.
+ * Left out on purpose: ByteTrack's remove_duplicate_stracks, appearance / ReID costs, camera-motion compensation.  Two choices differ
+ * from ByteTrack: association is "scipy, then filter by the threshold" (what Ultralytics does without `lap`; ByteTrack calls lapjv
+ * with a cost limit), and tentative slots are predicted too.
+ * Outputs per row: ids int32 [S, K] (-1 where untracked or padding), track_boxes fp32 [S, K, 4] = the slot's post-update mean as
+ * xyxy, narrowed once, 0 where the id is -1.  Nothing else of the input is copied or changed.
+ *   state       dod_track_state_bytes(S, T) bytes, 8-byte aligned, owned by the caller; dod_track_reset before the first update.
+ *               stream_mask: int32 [S] (DEVICE), non-zero = reset that stream, or NULL = all; a stream that is not reset is not touched.
+ *   workspace   dod_track_workspace_bytes(S, T, K) bytes, 8-byte aligned: per stream the compacted cost matrix (T * K floats) and the
+ *               solver's state for the problems with rows + columns > 1024 (smaller ones keep it in LDS).
+ *   export      the table as typed arrays (DEVICE): mean fp64 [S, T, 8] (cx, cy, a, h and their velocities), cov fp64 [S, T, 12]
+ *               (component-major: p, c, v of cx, then cy, a, h), state / id / label / last_frame int32 [S, T], score fp32 [S, T],
+ *               frame / next_id / overflow int32 [S].  Ten copies on `stream`.
+ * The byte queries return 0 outside the limits.  DOD_ERR_INVALID before any launch: a NULL or misaligned pointer (stream_mask may be
+ * NULL), S outside 1..65535, T outside 1..512, K outside 1..1024, a NaN threshold, low_thresh > track_thresh, max_age < 0, a
+ * workspace smaller than the query's answer.  All data pointers are DEVICE pointers; params is read on the host. */
+typedef struct dod_track_params {
+  float track_thresh, low_thresh, new_thresh, match_thresh, second_thresh, tentative_thresh;
+  int32_t max_age, fuse_score, class_aware;
+} dod_track_params;
+size_t dod_track_state_bytes(int S, int T);
+size_t dod_track_workspace_bytes(int S, int T, int K);
+int dod_track_reset(void* state, int S, int T, const int32_t* stream_mask, void* stream);
+int dod_track_update(void* state, int S, int T, const float* scores, const int32_t* labels, const float* boxes, const int32_t* counts,
+                     int K, const dod_track_params* params, int32_t* ids, float* track_boxes, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int dod_track_export(const void* state, int S, int T, double* mean, double* cov, int32_t* slot_state, int32_t* id, int32_t* label,
+                     int32_t* last_frame, float* score, int32_t* frame, int32_t* next_id, int32_t* overflow, void* stream);
+
 /* ---- COCO bbox evaluation on device (compute_coco_metrics, dino_detector/utils.py:243-276) ---------------------------
  * pycocotools' COCOeval (iouType 'bbox', useCats = 1, default parameters: 10 IoU thresholds, 101 recall thresholds, area
  * ranges all / small / medium / large, maxDets 1 / 10 / 100) restated operation for operation in double precision
@@ -1158,7 +1223,7 @@ const char* dod_version(void);
  * publishes the layout of what dod_finalize_weights keeps (the dod_packed_format / dod_packed_array numbering), which a tool built against this
  * header reads through the struct: the revision is raised so that such a tool and the library agree on it.
  * dod_optim_step and dod_optim_ema_update (with struct dod_optim_options and struct dod_optim_ema_tensor, which no earlier entry reads)
- * joined revision 7 by name: no earlier signature or layout moved.
+ * joined revision 7 by name: no earlier signature or layout moved.  So did the tracker (dod_track_* with struct dod_track_params).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 7
 int dod_abi_version(void);
