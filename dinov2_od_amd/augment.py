@@ -31,7 +31,12 @@ from . import _native as nat
 from . import preprocess as _pre
 
 MIN_BOX = 0.001        # the reference dataset's own minimum normalised width / height (dataset.py:90)
-MAX_TAPS = 32          # csrc/preproc.hip PP_MAXK: ceil(crop / out) * 2 + 1 filter taps at most (down-scaling up to 15x)
+MAX_TAPS = 32          # csrc/preproc.hip PP_MAXK: the filter taps at most (down-scaling up to 15x)
+
+
+def _taps(crop, dest):
+    """the filter taps of resizing `crop` pixels to `dest` (csrc/preproc.hip pp_taps_ok): ceil(crop / dest) * 2 + 1"""
+    return -(-int(crop) // int(dest)) * 2 + 1
 
 
 def _check_params(shapes, crops, flips, jitter, out_h, out_w):
@@ -54,9 +59,9 @@ def _check_params(shapes, crops, flips, jitter, out_h, out_w):
             raise ValueError(f"jitter: expected [{B}, 3] factors (brightness, contrast, saturation), got shape {jitter.shape}")
         if not np.isfinite(jitter).all() or (jitter < 0).any():
             raise ValueError("jitter: factors must be finite and >= 0")
-    kh, kv = -(-int(crops[:, 2].max()) // out_w) * 2 + 1, -(-int(crops[:, 3].max()) // out_h) * 2 + 1
-    if kh > MAX_TAPS or kv > MAX_TAPS:
-        raise ValueError(f"a crop is more than 15x the output {out_h}x{out_w}: the filter would need {max(kh, kv)} taps (> {MAX_TAPS})")
+    k = max(_taps(crops[:, 2].max(), out_w), _taps(crops[:, 3].max(), out_h))
+    if k > MAX_TAPS:
+        raise ValueError(f"a crop is more than 15x the output {out_h}x{out_w}: the filter would need {k} taps (> {MAX_TAPS})")
     return crops.astype(np.int32), flips, jitter
 
 
@@ -128,17 +133,14 @@ def _launch_aug(src, src_offs, hs, ws, crops, flips, jitter, out_h, out_w, as_ui
     dev = src.device
     B = len(crops)
     tmp_offs, tmp_bytes = _pre._tmp_layout(crops[:, 3], out_w, crops[:, 2] if jitter is not None else None)
-    meta = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (src_offs, hs, ws, tmp_offs)]
-    crops_t, flips_t = staged if staged is not None else (torch.from_numpy(crops).to(dev), torch.from_numpy(flips).to(dev))
-    jit = torch.from_numpy(jitter).to(dev) if jitter is not None else None
-    # the luma sums of the contrast step: only when some image has a contrast factor != 1 (the reduction is not launched otherwise)
-    lsum = torch.empty(B, dtype=torch.int64, device=dev) if jitter is not None and (jitter[:, 1] != 1.0).any() else None
+    meta = _pre._upload(dev, src_offs, hs, ws, tmp_offs, jitter)
+    crops_t, flips_t = staged if staged is not None else _pre._upload(dev, crops, flips)
+    lsum = _pre._luma_sums(jitter, B, dev)
     tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
     out = _pre._out_buffer(B, out_h, out_w, as_uint8, dev)
-    fn = nat.lib().dod_preprocess_aug_u8 if as_uint8 else nat.lib().dod_preprocess_aug
-    nat.check(fn(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), B, nat.ptr(crops_t), nat.ptr(flips_t), nat.ptr(jit),
-                 nat.ptr(lsum), int(crops[:, 3].max()), int(crops[:, 2].max()), out_h, out_w, nat.ptr(tmp), nat.ptr(meta[3]), nat.ptr(out),
-                 nat.stream_ptr()))
+    nat.check(_pre._entry("dod_preprocess_aug", as_uint8)(
+        nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), B, nat.ptr(crops_t), nat.ptr(flips_t), nat.ptr(meta[4]), nat.ptr(lsum),
+        int(crops[:, 3].max()), int(crops[:, 2].max()), out_h, out_w, nat.ptr(tmp), nat.ptr(meta[3]), nat.ptr(out), nat.stream_ptr()))
     return out
 
 
@@ -148,10 +150,6 @@ def _launch_aug(src, src_offs, hs, ws, crops, flips, jitter, out_h, out_w, as_ui
 #     canvas = Image.new("RGB", (out_w, out_h), fill)
 #     for (src, crop, flip, jitter, dest) in pieces:  canvas.paste(chain(images[src], crop, jitter, (dw, dh), flip), (dx, dy))
 MAX_PIECES = 16        # csrc/preproc.hip PP_MAXP: pieces per canvas
-
-
-def _taps(crop, dest):
-    return -(-int(crop) // int(dest)) * 2 + 1
 
 
 def _check_fill(fill, N):
@@ -262,16 +260,15 @@ def _launch_compose(src, src_offs, hs, ws, rows, offs, jitter, fill, per_canvas,
     S, P, N = len(hs), len(rows), len(offs) - 1
     cw, ch, dw = (rows[:, k].astype(np.int64) for k in (3, 4, 8))
     tmp_offs, tmp_bytes = _pre._tmp_layout(np.maximum(ch, 0), np.maximum(dw, 0), np.maximum(cw, 0) if jitter is not None else None)
-    meta = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (src_offs, hs, ws, rows, offs, tmp_offs, fill)]
-    jit = torch.from_numpy(jitter).to(dev) if jitter is not None else None
-    lsum = torch.empty(P, dtype=torch.int64, device=dev) if jitter is not None and (jitter[:, 1] != 1.0).any() else None
+    meta = _pre._upload(dev, src_offs, hs, ws, rows, offs, tmp_offs, fill, jitter)
+    lsum = _pre._luma_sums(jitter, P, dev)
     tmp = torch.empty(max(1, tmp_bytes), dtype=torch.uint8, device=dev)
     if out is None:
         out = _pre._out_buffer(N, out_h, out_w, as_uint8, dev)
-    fn = nat.lib().dod_preprocess_compose_u8 if as_uint8 else nat.lib().dod_preprocess_compose
-    nat.check(fn(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), S, nat.ptr(meta[3]), nat.ptr(meta[4]), N, P, nat.ptr(jit),
-                 nat.ptr(lsum), nat.ptr(meta[6]), int(per_canvas), int(ch.max()), int(cw.max()), int(dw.max()), out_h, out_w, nat.ptr(tmp),
-                 nat.ptr(meta[5]), nat.ptr(out), nat.stream_ptr()))
+    nat.check(_pre._entry("dod_preprocess_compose", as_uint8)(
+        nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), S, nat.ptr(meta[3]), nat.ptr(meta[4]), N, P, nat.ptr(meta[7]), nat.ptr(lsum),
+        nat.ptr(meta[6]), int(per_canvas), int(ch.max()), int(cw.max()), int(dw.max()), out_h, out_w, nat.ptr(tmp), nat.ptr(meta[5]), nat.ptr(out),
+        nat.stream_ptr()))
     return out
 
 
@@ -511,12 +508,11 @@ def _launch_warp(src, src_offs, hs, ws, coeffs, fill, per_image, out_h, out_w, a
     returns it).  Nothing is validated here (the tests hand the kernel what the host would refuse); out: None or the buffer to write."""
     dev = src.device
     B = len(hs)
-    meta = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (src_offs, hs, ws, coeffs, fill)]
+    meta = _pre._upload(dev, src_offs, hs, ws, coeffs, fill)
     if out is None:
         out = _pre._out_buffer(B, out_h, out_w, as_uint8, dev)
-    fn = nat.lib().dod_preprocess_warp_u8 if as_uint8 else nat.lib().dod_preprocess_warp
-    nat.check(fn(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), B, nat.ptr(meta[3]), nat.ptr(meta[4]), int(per_image), out_h,
-                 out_w, nat.ptr(out), nat.stream_ptr()))
+    nat.check(_pre._entry("dod_preprocess_warp", as_uint8)(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), B, nat.ptr(meta[3]),
+                                                           nat.ptr(meta[4]), int(per_image), out_h, out_w, nat.ptr(out), nat.stream_ptr()))
     return out
 
 

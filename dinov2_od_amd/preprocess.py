@@ -133,6 +133,21 @@ def _out_buffer(n, out_h, out_w, as_uint8, dev):
     return torch.empty(n, 3, out_h, out_w, dtype=torch.float32, device=dev)
 
 
+def _entry(name, as_uint8):
+    """the C entry `name` for the float32 CHW output, or its `_u8` twin for the uint8 HWC bytes"""
+    return getattr(nat.lib(), name + "_u8" if as_uint8 else name)
+
+
+def _upload(dev, *arrays):
+    """host metadata arrays -> device tensors, one copy each (None stays None)"""
+    return [None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in arrays]
+
+
+def _luma_sums(jitter, n, dev):
+    """the luma sums of the contrast step: only when some item has a contrast factor != 1 (the reduction is not launched otherwise)"""
+    return torch.empty(n, dtype=torch.int64, device=dev) if jitter is not None and (jitter[:, 1] != 1.0).any() else None
+
+
 def preprocess_batch(images, size=(224, 224), device="cuda", as_uint8=False):
     """images: sequence of uint8 RGB images [H_i, W_i, 3] (numpy arrays, torch tensors or PIL images), or a `Staged` batch that is on
     the device already (`jpeg.decode_jpeg_batch`); size: (height, width) as torchvision's Resize takes it.  Returns float32 [B, 3, height, width] on `device` -- or, with as_uint8, the resampled
@@ -144,12 +159,11 @@ def preprocess_batch(images, size=(224, 224), device="cuda", as_uint8=False):
     dev = torch.device(device)
     src, src_offs, hs, ws = srcs.stage(dev)
     tmp_offs, tmp_bytes = _tmp_layout(hs, out_w)
-    meta = [torch.from_numpy(x).to(dev) for x in (src_offs, hs, ws, tmp_offs)]
+    meta = _upload(dev, src_offs, hs, ws, tmp_offs)
     tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
     out = _out_buffer(B, out_h, out_w, as_uint8, dev)
-    fn = nat.lib().dod_preprocess_u8 if as_uint8 else nat.lib().dod_preprocess
-    nat.check(fn(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), B, int(hs.max()), int(ws.max()), out_h, out_w, nat.ptr(tmp),
-                 nat.ptr(meta[3]), nat.ptr(out), nat.stream_ptr()))
+    nat.check(_entry("dod_preprocess", as_uint8)(nat.ptr(src), nat.ptr(meta[0]), nat.ptr(meta[1]), nat.ptr(meta[2]), B, int(hs.max()), int(ws.max()),
+                                                 out_h, out_w, nat.ptr(tmp), nat.ptr(meta[3]), nat.ptr(out), nat.stream_ptr()))
     return out
 
 

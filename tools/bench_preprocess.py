@@ -46,10 +46,8 @@ def augment_leg(R):
     lsum = torch.empty(B, dtype=torch.int64, device="cuda")
 
     def setup(c, jittered):
-        # tmp per image: crop height x out_w x 3, and with jitter the jittered crop behind it (include/dinodet.h)
-        sz = c[:, 3].astype(np.int64) * (R + (c[:, 2].astype(np.int64) if jittered else 0)) * 3
-        to = np.concatenate([[0], np.cumsum(sz)[:-1]]).astype(np.int64)
-        return [torch.from_numpy(x).cuda() for x in (so, hs, ws, to, c)], torch.empty(int(sz.sum()), dtype=torch.uint8, device="cuda")
+        to, nbytes = pre._tmp_layout(c[:, 3], R, c[:, 2] if jittered else None)
+        return [torch.from_numpy(x).cuda() for x in (so, hs, ws, to, c)], torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     mp, tp = setup(full, False)
     mc, tc = setup(crops, False)
     mpj, tpj = setup(full, True)
@@ -101,11 +99,10 @@ def mosaic_leg(R):
         if jitter is not None and (jitter == 1.0).all():
             jitter = None
         cw, ch, dw = (rows[:, k].astype(np.int64) for k in (3, 4, 8))
-        sz = ch * (dw + (cw if jitter is not None else 0)) * 3
-        to = np.concatenate([[0], np.cumsum(sz)[:-1]]).astype(np.int64)
+        to, nbytes = pre._tmp_layout(ch, dw, cw if jitter is not None else None)
         d = [torch.from_numpy(x).cuda() for x in (rows, offs, to)] + [torch.from_numpy(jitter).cuda() if jitter is not None else None,
                                                                       torch.empty(len(rows), dtype=torch.int64, device="cuda") if jitter is not None else None,
-                                                                      torch.empty(int(sz.sum()), dtype=torch.uint8, device="cuda")]
+                                                                      torch.empty(nbytes, dtype=torch.uint8, device="cuda")]
         keep.append(d)
         frac = float((cw * ch).sum()) / (B * 480 * 640)
         return frac, lambda: nat.check(L.dod_preprocess_compose(nat.ptr(src), nat.ptr(base[0]), nat.ptr(base[1]), nat.ptr(base[2]), B, nat.ptr(d[0]), nat.ptr(d[1]),
@@ -113,11 +110,10 @@ def mosaic_leg(R):
                                                                 R, R, nat.ptr(d[5]), nat.ptr(d[2]), nat.ptr(out), nat.stream_ptr()))
 
     def single(c, f, j):
-        sz = c[:, 3].astype(np.int64) * (R + (c[:, 2].astype(np.int64) if j is not None else 0)) * 3
-        to = np.concatenate([[0], np.cumsum(sz)[:-1]]).astype(np.int64)
+        to, nbytes = pre._tmp_layout(c[:, 3], R, c[:, 2] if j is not None else None)
         d = [torch.from_numpy(x).cuda() for x in (to, c, f)] + [torch.from_numpy(j).cuda() if j is not None else None,
                                                                 torch.empty(B, dtype=torch.int64, device="cuda") if j is not None else None,
-                                                                torch.empty(int(sz.sum()), dtype=torch.uint8, device="cuda")]
+                                                                torch.empty(nbytes, dtype=torch.uint8, device="cuda")]
         keep.append(d)
         frac = float((c[:, 2].astype(np.int64) * c[:, 3]).sum()) / (B * 480 * 640)
         return frac, lambda: nat.check(L.dod_preprocess_aug(nat.ptr(src), nat.ptr(base[0]), nat.ptr(base[1]), nat.ptr(base[2]), B, nat.ptr(d[1]), nat.ptr(d[2]), nat.ptr(d[3]),
@@ -186,11 +182,10 @@ def warp_leg(R):
                                     nat.ptr(dst), nat.stream_ptr()))
 
     def chain(c, f, j, dst):
-        sz = c[:, 3].astype(np.int64) * (R + (c[:, 2].astype(np.int64) if j is not None else 0)) * 3
-        to = np.concatenate([[0], np.cumsum(sz)[:-1]]).astype(np.int64)
+        to, nbytes = pre._tmp_layout(c[:, 3], R, c[:, 2] if j is not None else None)
         d = [torch.from_numpy(x).cuda() for x in (to, c, f)] + [torch.from_numpy(j).cuda() if j is not None else None,
                                                                 torch.empty(B, dtype=torch.int64, device="cuda") if j is not None else None,
-                                                                torch.empty(int(sz.sum()), dtype=torch.uint8, device="cuda")]
+                                                                torch.empty(nbytes, dtype=torch.uint8, device="cuda")]
         keep.append(d)
         fn = L.dod_preprocess_aug_u8 if dst.dtype == torch.uint8 else L.dod_preprocess_aug
         return lambda: nat.check(fn(nat.ptr(src), nat.ptr(base[0]), nat.ptr(base[1]), nat.ptr(base[2]), B, nat.ptr(d[1]), nat.ptr(d[2]), nat.ptr(d[3]), nat.ptr(d[4]),
@@ -199,11 +194,10 @@ def warp_leg(R):
     def compose(plan, dst):
         rows, offs, jitter = aug._check_pieces(shapes, plan, R, R)
         cw, ch, dw = (rows[:, k].astype(np.int64) for k in (3, 4, 8))
-        sz = ch * (dw + (cw if jitter is not None else 0)) * 3
-        to = np.concatenate([[0], np.cumsum(sz)[:-1]]).astype(np.int64)
+        to, nbytes = pre._tmp_layout(ch, dw, cw if jitter is not None else None)
         d = [torch.from_numpy(x).cuda() for x in (rows, offs, to)] + [torch.from_numpy(jitter).cuda() if jitter is not None else None,
                                                                       torch.empty(len(rows), dtype=torch.int64, device="cuda") if jitter is not None else None,
-                                                                      torch.empty(int(sz.sum()), dtype=torch.uint8, device="cuda")]
+                                                                      torch.empty(nbytes, dtype=torch.uint8, device="cuda")]
         keep.append(d)
         fn = L.dod_preprocess_compose_u8 if dst.dtype == torch.uint8 else L.dod_preprocess_compose
         return lambda: nat.check(fn(nat.ptr(src), nat.ptr(base[0]), nat.ptr(base[1]), nat.ptr(base[2]), B, nat.ptr(d[0]), nat.ptr(d[1]), B, len(rows), nat.ptr(d[3]),
@@ -309,10 +303,10 @@ for R in (224, 518):
     L = nat.lib(); B = len(imgs)
     hs = np.array([a.shape[0] for a in imgs], np.int32); ws = np.array([a.shape[1] for a in imgs], np.int32)
     so = np.concatenate([[0], np.cumsum(hs.astype(np.int64) * ws * 3)[:-1]]).astype(np.int64)
-    to = np.concatenate([[0], np.cumsum(hs.astype(np.int64) * R * 3)[:-1]]).astype(np.int64)
+    to, nbytes = pre._tmp_layout(hs, R)
     src = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).cuda()
     m = [torch.from_numpy(x).cuda() for x in (so, hs, ws, to)]
-    tmp = torch.empty(int((hs.astype(np.int64) * R * 3).sum()), dtype=torch.uint8, device="cuda")
+    tmp = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     out = torch.empty(B, 3, R, R, device="cuda")
     run = lambda: nat.check(L.dod_preprocess(nat.ptr(src), nat.ptr(m[0]), nat.ptr(m[1]), nat.ptr(m[2]), B, 480, 640, R, R, nat.ptr(tmp), nat.ptr(m[3]), nat.ptr(out), nat.stream_ptr()))
     for _ in range(3): run()
