@@ -117,6 +117,11 @@ class DodTrackParams(C.Structure):
                 ("class_aware", C.c_int32)]
 
 
+class DodTrackAppParams(C.Structure):
+    """struct dod_track_app_params (include/dinodet.h): the gates and the momentum of dod_track_update_app / dod_track_embed_commit"""
+    _fields_ = [("appearance_thresh", C.c_float), ("proximity_thresh", C.c_float), ("momentum", C.c_float)]
+
+
 # include/dinodet_tuning.h: exported by -DDINODET_TUNING builds only (tools/ load one through DINODET_LIB); bound when present
 TUNING_SYMBOLS = {
     "dod_debug_gemm_stamps": (_I, [_P]),
@@ -137,6 +142,7 @@ SYMBOLS = {
     "dod_workspace_bytes": (_SZ, [_P, _I, _I, _I]),
     "dod_num_tokens": (_I, [_P, _I, _I]),
     "dod_forward": (_I, [_P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
+    "dod_forward_mem": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "dod_forward_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
     "dod_backbone_forward": (_I, [_P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
     "dod_backbone_prefix": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _SZ, _P]),
@@ -206,6 +212,10 @@ SYMBOLS = {
     "dod_track_reset": (_I, [_P, _I, _I, _P, _P]),
     "dod_track_update": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, C.POINTER(DodTrackParams), _P, _P, _P, _SZ, _P]),
     "dod_track_export": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dod_roi_embed": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "dod_track_embed_dots": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "dod_track_update_app": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, C.POINTER(DodTrackParams), C.POINTER(DodTrackAppParams), _P, _P, _P, _P, _P, _SZ, _P]),
+    "dod_track_embed_commit": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "dod_coco_eval_workspace_bytes": (_SZ, [_I64, _I, _I, _I64]),
     "dod_coco_eval_set_gt": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dod_coco_eval_reset": (_I, [_P, _SZ, _I64, _I, _I, _I64, _P]),

@@ -223,6 +223,27 @@ int dod_forward(dod_handle* h, const float* pixels, int B, int H, int W, float* 
   return decoder_impl(h, bw.mem, B, N, dw, det, (hipStream_t)stream);
 }
 
+// dod_forward that also hands out the decoder's memory: an entry of its own, so that dod_forward's path has no branch for it.  The copy sits
+// where tap 1000 reads, between the two schedules, before the decoder can reuse the workspace.
+int dod_forward_mem(dod_handle* h, const float* pixels, int B, int H, int W, float* det, float* memory, void* workspace, size_t wsb, void* stream) {
+  int rc;
+  if (h && (!pixels || !det || !memory || !workspace)) return fail(h, DOD_ERR_INVALID, "null buffer");      // an argument error whatever the handle's state
+  if (!check_common(h, B, H, W, &rc)) return rc;
+  if (wsb < dod_workspace_bytes(h, B, H, W)) return fail(h, DOD_ERR_STATE, "workspace too small: %zu < %zu", wsb, dod_workspace_bytes(h, B, H, W));
+  const int N = dod_num_tokens(h, H, W);
+  Carver c(align_ws(workspace));
+  BbWS bw; DecWS dw;
+  carve_backbone(h, c, B, N, &bw);
+  carve_decoder(h, c, B, N, &dw, false);
+  CARVE_FITS(h, c, workspace, wsb)
+  hipStream_t s = (hipStream_t)stream;
+  rc = backbone_impl(h, pixels, B, H, W, bw, nullptr, true, s); if (rc) return rc;
+  const size_t n = (size_t)B * N * h->cfg.dec_hidden;
+  if (is_bf16(h)) KCHK(h, launch_widen_bf16((const bf16_t*)bw.mem, memory, n, s));
+  else HIPCHK(h, hipMemcpyAsync(memory, bw.mem, n * 4, hipMemcpyDeviceToDevice, s));
+  return decoder_impl(h, bw.mem, B, N, dw, det, s);
+}
+
 int dod_forward_u8(dod_handle* h, const uint8_t* pixels_hwc, int B, int H, int W, float* det, void* workspace, size_t wsb, void* stream) {
   int rc;
   if (!check_common(h, B, H, W, &rc)) return rc;

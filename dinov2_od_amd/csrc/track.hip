@@ -14,9 +14,15 @@
 //   lanes over matched pairs for the Kalman update: the pairs of one solution touch distinct slots and distinct rows
 // The lists (slot list, high rows, low rows, the slot every row ended on) live in LDS.  Every loop is bounded by T or K; the solver's
 // by the column count.
+//
+// dod_track_update_app is the same kernel instantiated a second time (template on a bool): the first and the tentative pass take
+// min(that cost, the gated appearance distance) from the similarity matrix dod_track_embed_dots wrote (the strided-batched fp32 GEMM), and
+// every row leaves with slot + 1024 * kind in `assoc`, which dod_track_embed_commit turns into the slots' smoothed embeddings.  The slots'
+// embeddings are a tensor of the caller's; the table and the plain instantiation are what they were.
 #include "dod_common.h"
 #include "../../include/dinodet.h"
 #include "lsap.h"
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -75,6 +81,15 @@ struct TrkArgs {
   unsigned char* workspace;
   size_t cost_bytes, stream_bytes;          // of one stream's share of the workspace: the cost matrix, then the solver state
 };
+
+// dod_track_update_app: the same arguments, the similarity matrix, the two gates and the one new output
+struct TrkAppArgs : TrkArgs {
+  const float* dots;                        // [S, T, K]
+  float app_thresh, prox_thresh;
+  int* assoc;                               // [S, K]
+};
+constexpr int kTrkKind = 1024;              // assoc = slot + kTrkKind * kind; a slot is below kTrkMaxT
+static_assert(kTrkMaxT <= kTrkKind, "a slot index fits below the kind");
 
 __device__ __forceinline__ bool trk_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
@@ -162,7 +177,10 @@ __device__ __forceinline__ double trk_iou(const double a[4], const double b[4]) 
 
 // One association pass of stream s: the slots rows[0 .. nr) against the detection rows cols[0 .. nc).  All lanes call it with uniform
 // arguments.  A kept pair is a hit: Kalman update, TRACKED, last = frame, the slot takes the row's score and label, slot_of[row] = slot.
-__device__ __forceinline__ void trk_associate(const TrkArgs& a, size_t s, const int* rows, int nr, const int* cols, int nc, bool fuse, float thresh,
+// APP (the first and the tentative pass of dod_track_update_app): the cost is min(today's cost, the gated appearance distance), and
+// slot_of[row] carries kind 1 (slot + kTrkKind): the row's embedding is to be blended into the slot's.
+template <bool APP>
+__device__ __forceinline__ void trk_associate(const std::conditional_t<APP, TrkAppArgs, TrkArgs>& a, size_t s, const int* rows, int nr, const int* cols, int nc, bool fuse, float thresh,
                                               int frame, float* __restrict__ cost, unsigned char* lds, unsigned char* wstate, int* slot_of, int* slabel) {
   if (nr == 0 || nc == 0) return;
   const int lane = threadIdx.x;
@@ -192,8 +210,18 @@ __device__ __forceinline__ void trk_associate(const TrkArgs& a, size_t s, const 
     db[0] = (double)cbox[4 * k]; db[1] = (double)cbox[4 * k + 1]; db[2] = (double)cbox[4 * k + 2]; db[3] = (double)cbox[4 * k + 3];
     double iou = trk_iou(sbox + 4 * i, db);
     if (a.p.class_aware && slabel[i] != clabel[k]) iou = 0.0;
-    if (fuse) iou = iou * (double)cscore[k];
-    cost[e] = (float)(1.0 - iou);
+    if constexpr (APP) {
+      const double d_iou = 1.0 - iou;
+      const double base = fuse ? 1.0 - iou * (double)cscore[k] : d_iou;
+      const double gap = 1.0 - (double)a.dots[(t0 + rows[i]) * a.K + cols[k]];
+      double d_app = 0.5 * (gap > 0.0 ? gap : 0.0);
+      if (d_app > (double)a.app_thresh) d_app = 1.0;
+      if (d_iou > (double)a.prox_thresh) d_app = 1.0;
+      cost[e] = (float)(d_app < base ? d_app : base);
+    } else {
+      if (fuse) iou = iou * (double)cscore[k];
+      cost[e] = (float)(1.0 - iou);
+    }
   }
   __syncthreads();
   const bool tr = nc < nr;                   // scipy solves the transpose when columns < rows
@@ -220,13 +248,16 @@ __device__ __forceinline__ void trk_associate(const TrkArgs& a, size_t s, const 
       a.tab.last[t0 + t] = frame;
       a.tab.score[t0 + t] = a.scores[r0 + j];
       a.tab.label[t0 + t] = a.labels[r0 + j];
-      slot_of[j] = t;
+      slot_of[j] = APP ? t + kTrkKind : t;
     }
   }
   __syncthreads();
 }
 
-__global__ __launch_bounds__(DOD_WAVE) void track_update_kernel(TrkArgs a) {
+// APP = dod_track_update_app: in that instantiation slot_of[row] holds slot + kTrkKind * kind (0: second pass, 1: first or tentative pass, 2: birth,
+// at every frame), which the last loop writes out as `assoc` and takes apart again for the ids
+template <bool APP>
+__global__ __launch_bounds__(DOD_WAVE) void track_update_kernel(std::conditional_t<APP, TrkAppArgs, TrkArgs> a) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kTrkLdsBytes];
   __shared__ int hi[kTrkMaxK], lo[kTrkMaxK], slot_of[kTrkMaxK], rows[kTrkMaxT], slabel[kTrkMaxT];
   const int lane = threadIdx.x, T = a.T, K = a.K;
@@ -266,7 +297,7 @@ __global__ __launch_bounds__(DOD_WAVE) void track_update_kernel(TrkArgs a) {
   }
   __syncthreads();
   // 3. high pass
-  trk_associate(a, s, rows, n, hi, nhi, a.p.fuse_score != 0, a.p.match_thresh, frame, cost, lds, wstate, slot_of, slabel);
+  trk_associate<APP>(a, s, rows, n, hi, nhi, a.p.fuse_score != 0, a.p.match_thresh, frame, cost, lds, wstate, slot_of, slabel);
   // 4. low pass: the TRACKED slots without a hit against the low rows, plain IoU
   n = 0;
   for (int base = 0; base < T; base += DOD_WAVE) {
@@ -274,7 +305,7 @@ __global__ __launch_bounds__(DOD_WAVE) void track_update_kernel(TrkArgs a) {
     n = trk_push(t < T && tab.state[t0 + t] == TRK_TRACKED && tab.last[t0 + t] != frame, t, rows, n);
   }
   __syncthreads();
-  trk_associate(a, s, rows, n, lo, nlo, false, a.p.second_thresh, frame, cost, lds, wstate, slot_of, slabel);
+  trk_associate<false>(a, s, rows, n, lo, nlo, false, a.p.second_thresh, frame, cost, lds, wstate, slot_of, slabel);
   // ... the ones still without a hit become LOST; 5. tentative pass against the high rows left over (the low list's storage is free now)
   n = 0;
   for (int base = 0; base < T; base += DOD_WAVE) {
@@ -290,7 +321,7 @@ __global__ __launch_bounds__(DOD_WAVE) void track_update_kernel(TrkArgs a) {
     nleft = trk_push(i < nhi && slot_of[j] < 0, j, lo, nleft);
   }
   __syncthreads();
-  trk_associate(a, s, rows, n, lo, nleft, a.p.fuse_score != 0, a.p.tentative_thresh, frame, cost, lds, wstate, slot_of, slabel);
+  trk_associate<APP>(a, s, rows, n, lo, nleft, a.p.fuse_score != 0, a.p.tentative_thresh, frame, cost, lds, wstate, slot_of, slabel);
   // tentative misses are freed; 6. expiry; the free slots in slot order
   n = 0;
   for (int base = 0; base < T; base += DOD_WAVE) {
@@ -319,12 +350,17 @@ __global__ __launch_bounds__(DOD_WAVE) void track_update_kernel(TrkArgs a) {
     tab.score[t0 + t] = a.scores[r0 + j];
     tab.last[t0 + t] = frame;
     tab.state[t0 + t] = frame == 1 ? TRK_TRACKED : TRK_TENTATIVE;
-    if (frame == 1) slot_of[j] = t;
+    if constexpr (APP) slot_of[j] = t + 2 * kTrkKind;
+    else if (frame == 1) slot_of[j] = t;
   }
   __syncthreads();
   // the rows' ids and boxes
   for (int j = lane; j < K; j += DOD_WAVE) {
-    const int t = slot_of[j];
+    int t = slot_of[j];
+    if constexpr (APP) {
+      a.assoc[r0 + j] = t;
+      if (t >= 0) t = (t >= 2 * kTrkKind && frame != 1) ? -1 : t % kTrkKind;      // a later birth is TENTATIVE: the row keeps id -1
+    }
     float* o = a.track_boxes + (r0 + j) * 4;
     if (t < 0) {
       a.ids[r0 + j] = -1;
@@ -355,6 +391,38 @@ __global__ __launch_bounds__(DOD_WAVE) void track_reset_kernel(TrkTable tab, int
   if (threadIdx.x == 0) { tab.frame[s] = 0; tab.next_id[s] = 1; tab.overflow[s] = 0; }
 }
 
+// dod_track_embed_commit: one wave per row (s, j).  Kind 2 stores the row's embedding in its slot; kind 1 blends it into the slot's,
+// x = m E + (1 - m) e per element in double, and writes x / |x| (zeros when |x| is 0); kind 0 and -1 leave the table alone.  The rows of a
+// frame name distinct slots, and a lane writes only the elements it read itself: plain stores, no atomics.
+__global__ __launch_bounds__(DOD_WAVE) void track_embed_commit_kernel(float* __restrict__ slot_emb, const float* __restrict__ emb,
+                                                                      const int* __restrict__ assoc, int T, int K, int D, float momentum) {
+  const size_t s = blockIdx.y, j = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int v = assoc[s * K + j];
+  if (v < 0) return;
+  const int kind = v / kTrkKind, t = v % kTrkKind;
+  if (kind < 1 || kind > 2 || t >= T) return;
+  float* E = slot_emb + (s * T + t) * D;
+  const float* e = emb + (s * K + j) * D;
+  if (kind == 2) {
+    for (int c = lane; c < D; c += DOD_WAVE) E[c] = e[c];
+    return;
+  }
+  const double m = (double)momentum, m1 = 1.0 - m;
+  double ss = 0.0;
+  for (int c = lane; c < D; c += DOD_WAVE) {
+    const double x = m * (double)E[c] + m1 * (double)e[c];
+    ss = ss + x * x;
+  }
+  for (int off = DOD_WAVE / 2; off > 0; off >>= 1) ss = ss + __shfl_xor(ss, off, DOD_WAVE);
+  const double nrm = sqrt(ss);
+  for (int c = lane; c < D; c += DOD_WAVE) {
+    const double x = m * (double)E[c] + m1 * (double)e[c];
+    E[c] = ss > 0.0 ? (float)(x / nrm) : 0.0f;
+  }
+}
+
+constexpr int kTrkMaxD = 2048;
 bool trk_shape_ok(int S, int T) { return S >= 1 && S <= kTrkMaxS && T >= 1 && T <= kTrkMaxT; }
 bool trk_rows_ok(int K) { return K >= 1 && K <= kTrkMaxK; }
 
@@ -378,9 +446,9 @@ extern "C" int dod_track_reset(void* state, int S, int T, const int32_t* stream_
   return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
 }
 
-extern "C" int dod_track_update(void* state, int S, int T, const float* scores, const int32_t* labels, const float* boxes, const int32_t* counts,
-                                int K, const dod_track_params* params, int32_t* ids, float* track_boxes, void* workspace, size_t workspace_bytes,
-                                void* stream) {
+// the argument check dod_track_update and dod_track_update_app share, and the arguments both kernels take
+static int trk_update_args(void* state, int S, int T, const float* scores, const int32_t* labels, const float* boxes, const int32_t* counts, int K,
+                           const dod_track_params* params, int32_t* ids, float* track_boxes, void* workspace, size_t workspace_bytes, TrkArgs& a) {
   if (!state || ((uintptr_t)state & 7) != 0 || !scores || !labels || !boxes || !counts || !params || !ids || !track_boxes) return DOD_ERR_INVALID;
   if (!trk_shape_ok(S, T) || !trk_rows_ok(K)) return DOD_ERR_INVALID;
   const dod_track_params& p = *params;
@@ -389,7 +457,6 @@ extern "C" int dod_track_update(void* state, int S, int T, const float* scores, 
     if (v != v) return DOD_ERR_INVALID;
   if (p.max_age < 0 || !(p.low_thresh <= p.track_thresh)) return DOD_ERR_INVALID;
   if (!workspace || ((uintptr_t)workspace & 7) != 0 || workspace_bytes < dod_track_workspace_bytes(S, T, K)) return DOD_ERR_INVALID;
-  TrkArgs a;
   trk_carve((unsigned char*)state, S, T, &a.tab);
   a.T = T; a.K = K;
   a.scores = scores; a.labels = (const int*)labels; a.boxes = boxes; a.counts = (const int*)counts;
@@ -398,7 +465,51 @@ extern "C" int dod_track_update(void* state, int S, int T, const float* scores, 
   a.workspace = (unsigned char*)workspace;
   a.cost_bytes = trk_up((size_t)T * K * sizeof(float));
   a.stream_bytes = a.cost_bytes + trk_up((size_t)(T + K) * kUnitBytes);
-  hipLaunchKernelGGL(track_update_kernel, dim3((unsigned)S), dim3(DOD_WAVE), 0, (hipStream_t)stream, a);
+  return DOD_OK;
+}
+
+extern "C" int dod_track_update(void* state, int S, int T, const float* scores, const int32_t* labels, const float* boxes, const int32_t* counts,
+                                int K, const dod_track_params* params, int32_t* ids, float* track_boxes, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  TrkArgs a;
+  if (const int rc = trk_update_args(state, S, T, scores, labels, boxes, counts, K, params, ids, track_boxes, workspace, workspace_bytes, a)) return rc;
+  hipLaunchKernelGGL(track_update_kernel<false>, dim3((unsigned)S), dim3(DOD_WAVE), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+}
+
+static bool trk_app_params_ok(const dod_track_app_params* q) {
+  return q && q->appearance_thresh == q->appearance_thresh && q->proximity_thresh == q->proximity_thresh && q->momentum >= 0.0f && q->momentum <= 1.0f;
+}
+static bool trk_embed_ok(int D) { return D >= 4 && D <= kTrkMaxD && D % 4 == 0; }
+
+extern "C" int dod_track_update_app(void* state, int S, int T, const float* scores, const int32_t* labels, const float* boxes, const int32_t* counts,
+                                    int K, const dod_track_params* params, const dod_track_app_params* app_params, const float* dots, int32_t* ids,
+                                    float* track_boxes, int32_t* assoc, void* workspace, size_t workspace_bytes, void* stream) {
+  TrkAppArgs a;
+  if (!trk_app_params_ok(app_params) || !dots || !assoc) return DOD_ERR_INVALID;
+  if (const int rc = trk_update_args(state, S, T, scores, labels, boxes, counts, K, params, ids, track_boxes, workspace, workspace_bytes, a)) return rc;
+  a.dots = dots; a.assoc = (int*)assoc;
+  a.app_thresh = app_params->appearance_thresh; a.prox_thresh = app_params->proximity_thresh;
+  hipLaunchKernelGGL(track_update_kernel<true>, dim3((unsigned)S), dim3(DOD_WAVE), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+}
+
+extern "C" int dod_track_embed_dots(const float* slot_emb, const float* emb, int S, int T, int K, int D, float* dots, void* stream) {
+  if (!slot_emb || !emb || !dots || !trk_shape_ok(S, T) || !trk_rows_ok(K) || !trk_embed_ok(D)) return DOD_ERR_INVALID;
+  GemmF32X g = {};
+  g.A = slot_emb; g.lda = D; g.a_sb = (long long)T * D;
+  g.W = emb; g.ldw = D; g.w_sb = (long long)K * D;
+  g.C = dots; g.ldc = K; g.c_sb = (long long)T * K;
+  g.M = T; g.N = K; g.K = D; g.batch = S; g.hb = 1; g.alpha = 1.0f; g.ksplit = 1;
+  const int rc = launch_gemm_f32x(g, (hipStream_t)stream);
+  return rc == 0 ? DOD_OK : (rc == 3 ? DOD_ERR_HIP : DOD_ERR_INVALID);
+}
+
+extern "C" int dod_track_embed_commit(float* slot_emb, const float* emb, const int32_t* assoc, int S, int T, int K, int D, float momentum, void* stream) {
+  if (!slot_emb || !emb || !assoc || !trk_shape_ok(S, T) || !trk_rows_ok(K) || !trk_embed_ok(D)) return DOD_ERR_INVALID;
+  if (!(momentum >= 0.0f && momentum <= 1.0f)) return DOD_ERR_INVALID;
+  hipLaunchKernelGGL(track_embed_commit_kernel, dim3((unsigned)K, (unsigned)S), dim3(DOD_WAVE), 0, (hipStream_t)stream, slot_emb, emb, (const int*)assoc, T, K, D,
+                     momentum);
   return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
 }
 

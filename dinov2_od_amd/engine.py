@@ -202,15 +202,8 @@ class Engine:
         return (K >= 2 and B >= max(self.micro_min_batch, K)
                 and B * self._lib.dod_num_tokens(self._h, H, W) >= self.micro_min_rows)
 
-    def _launch_micro(self, x):
-        """the forward of a large batch as `micro_streams` concurrent micro-batches (fork / join on side streams; inside a caller's
-        stream capture the side streams join the capture).  Detections are bit-identical to the single launch."""
-        B, _, H, W = x.shape
-        K = self.micro_streams
-        if not self._micro_ok(B, H, W) or self._tap_bufs:
-            return self._launch_forward(x)
-        sizes = [B // K + (1 if k < B % K else 0) for k in range(K)]
-        offs = [sum(sizes[:k]) for k in range(K)]
+    def _micro_state(self, sizes, H, W, x):
+        """(workspaces, side streams) of the micro-batches `sizes` of x, made once per shape"""
         key = (tuple(sizes), H, W, x.device)
         st = self._micro.get(key)
         if st is None:
@@ -220,9 +213,20 @@ class Engine:
                 if nb == 0:
                     raise ValueError(f"unsupported input {tuple(x.shape)}")
                 wss.append(torch.empty(nb, dtype=torch.uint8, device=x.device))
-            st = (wss, [torch.cuda.Stream(device=x.device) for _ in range(K - 1)])
+            st = (wss, [torch.cuda.Stream(device=x.device) for _ in range(len(sizes) - 1)])
             self._micro[key] = st
-        wss, side = st
+        return st
+
+    def _launch_micro(self, x):
+        """the forward of a large batch as `micro_streams` concurrent micro-batches (fork / join on side streams; inside a caller's
+        stream capture the side streams join the capture).  Detections are bit-identical to the single launch."""
+        B, _, H, W = x.shape
+        K = self.micro_streams
+        if not self._micro_ok(B, H, W) or self._tap_bufs:
+            return self._launch_forward(x)
+        sizes = [B // K + (1 if k < B % K else 0) for k in range(K)]
+        offs = [sum(sizes[:k]) for k in range(K)]
+        wss, side = self._micro_state(sizes, H, W, x)
         det = torch.empty(B, self.dc.num_queries, self.dc.num_classes + 4, dtype=torch.float32, device=x.device)
         cur = torch.cuda.current_stream(x.device)
         # the (H, W) position table is built (hipMalloc + resize kernel) by the first forward at a new grid, on the stream of THAT
@@ -246,6 +250,45 @@ class Engine:
             if self.use_graph and not torch.cuda.is_current_stream_capturing() and not self._tap_bufs:
                 return self._forward_graph(x)
             return self._launch_micro(x)
+
+    def forward_mem(self, pixel_values, named):
+        """[B, 3, H, W] -> (packed detections [B, Q, C+4], memory [B, N, Dd] fp32): dod_forward_mem, the forward that also hands out the
+        decoder's memory (the backbone's tokens after the final LayerNorm and projection, CLS first).  Detections are bit-identical
+        to `forward`'s.  Always eager: with use_graph on this entry still launches kernel by kernel (no graph is captured or replayed
+        for it); large batches run as micro-batches like the eager `forward`, memory sliced like the detections."""
+        x = self._check_pixels(pixel_values)
+        self.sync_weights(named)
+        B, _, H, W = x.shape
+        with self._on_device(x):
+            N = self._lib.dod_num_tokens(self._h, H, W)
+            det = torch.empty(B, self.dc.num_queries, self.dc.num_classes + 4, dtype=torch.float32, device=x.device)
+            mem = torch.empty(B, N, self.dc.hidden_dim, dtype=torch.float32, device=x.device)
+
+            def launch(xk, ws, dk, mk):
+                nat.check(self._lib.dod_forward_mem(self._h, nat.ptr(xk), xk.shape[0], H, W, nat.ptr(dk), nat.ptr(mk), nat.ptr(ws), ws.numel(),
+                                                    nat.stream_ptr()), self._h)
+
+            K = self.micro_streams
+            if not self._micro_ok(B, H, W) or self._tap_bufs:
+                nbytes = self._lib.dod_workspace_bytes(self._h, B, H, W)
+                if nbytes == 0:
+                    raise ValueError(f"unsupported input {tuple(x.shape)}")
+                launch(x, self._workspace(nbytes, x.device), det, mem)
+                return det, mem
+            sizes = [B // K + (1 if k < B % K else 0) for k in range(K)]
+            offs = [sum(sizes[:k]) for k in range(K)]
+            wss, side = self._micro_state(sizes, H, W, x)
+            cur = torch.cuda.current_stream(x.device)
+            nat.check(self._lib.dod_prepare(self._h, H, W, nat.stream_ptr()), self._h)      # as _launch_micro: the position table before the fork
+            for sd in side:
+                sd.wait_stream(cur)
+            launch(x[:sizes[0]], wss[0], det[:sizes[0]], mem[:sizes[0]])
+            for k, sd in enumerate(side, start=1):
+                with torch.cuda.stream(sd):
+                    launch(x[offs[k]:offs[k] + sizes[k]], wss[k], det[offs[k]:offs[k] + sizes[k]], mem[offs[k]:offs[k] + sizes[k]])
+            for sd in side:
+                cur.wait_stream(sd)
+        return det, mem
 
     def forward_u8(self, pixels_hwc, named):
         """uint8 [B, H, W, 3] (preprocess_batch(..., as_uint8=True)) -> packed detections; ToTensor's / 255 happens in the patch

@@ -90,10 +90,52 @@ class DINOv2ObjectDetector(_EngineMixin, nn.Module):   # state-dict keys already
         finally:
             self.train(was_training)
 
-    def track(self, pixel_values, tracker, sizes=None, **kw):
+    def _token_grid(self, pixel_values):
+        p = self._bb_cfg.patch
+        return pixel_values.shape[-2] // p, pixel_values.shape[-1] // p
+
+    def detect_embed(self, pixel_values, sizes=None, grid=4, **kw):
+        """`detect` plus one appearance vector per detection: (postprocess.Detections, embeddings [B, K, D] fp32).  One forward
+        (Engine.forward_mem: the same detections, and the backbone tokens it computed anyway), postprocess.detect_packed with **kw, then
+        reid.roi_embed pools the tokens under the detections' own boxes, in the detections' own pixel frame, from grid x grid samples:
+        unit vectors, zeros for padding rows.  No host sync."""
+        from ..postprocess import detect_packed
+        from ..reid import roi_embed
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                det, mem = self._get_engine().forward_mem(pixel_values, self._engine_named())
+                if sizes is None:
+                    sizes = (pixel_values.shape[-2], pixel_values.shape[-1])
+                out = detect_packed(det, self._dc_cfg.num_classes, sizes, **kw)
+                return out, roi_embed(mem, out.boxes, out.counts, sizes, grid, 1, self._token_grid(pixel_values))
+        finally:
+            self.train(was_training)
+
+    def embed(self, pixel_values, boxes, counts=None, sizes=None, grid=4):
+        """[B,3,H,W] and caller-supplied boxes [B, K, 4] fp32 xyxy (pixels of `sizes`: (height, width), None = the input's own; counts
+        [B] int32 or None = every row) -> [B, K, D] fp32 unit vectors pooled from the backbone tokens (reid.roi_embed): the building
+        block for retrieval and few-shot labelling on this backbone.  Eval-mode forward under no_grad; no host sync."""
+        from ..reid import roi_embed
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                _, mem = self._get_engine().forward_mem(pixel_values, self._engine_named())
+                if sizes is None:
+                    sizes = (pixel_values.shape[-2], pixel_values.shape[-1])
+                return roi_embed(mem, boxes, counts, sizes, grid, 1, self._token_grid(pixel_values))
+        finally:
+            self.train(was_training)
+
+    def track(self, pixel_values, tracker, sizes=None, grid=4, **kw):
         """`detect(pixel_values, sizes, **kw)` followed by `tracker.update`: image b of the batch is the next frame of the tracker's
         stream b (tracking.Tracker with num_streams = the batch size).  Returns tracking.TrackedDetections: the Detections plus the track
-        id and the filtered box of every row.  No host sync."""
+        id and the filtered box of every row.  With a Tracker(appearance=True) it is `detect_embed(pixel_values, sizes, grid, **kw)`
+        followed by `tracker.update(detections, embeddings)`.  No host sync."""
+        if getattr(tracker, "appearance", False):
+            return tracker.update(*self.detect_embed(pixel_values, sizes, grid, **kw))
         return tracker.update(self.detect(pixel_values, sizes, **kw))
 
     def detect_sliced(self, images, size=None, tile=None, overlap=0.2, full_view=True, flip=False, max_batch=64, **kw):

@@ -10,6 +10,11 @@ track table stays on the device.
         t = model.track(frames, tracker, top_k=100, threshold=0.1)      # detect + tracker.update -> TrackedDetections
         canvas = draw_detections(frames_u8, t.by_id())          # coloured and captioned by track id
 
+Geometry alone swaps ids when two objects cross or one stops while another passes.  `Tracker(appearance=True)` also keeps a smoothed
+embedding per track on the device and fuses appearance into the first and the tentative association the way BoT-SORT does
+(dod_track_update_app): the embeddings are `model.detect_embed`'s, pooled from the backbone tokens the forward computed anyway
+(reid.roi_embed), and `model.track` passes them on by itself.  Still no host sync.
+
 The header states the semantics and tests/track_cases.py restates them in numpy + scipy; the kernel's result equals that restatement
 bit for bit.  No CPU fallback: without the HIP library and a GPU this module raises.
 """
@@ -23,6 +28,7 @@ from .postprocess import Detections, MAX_TOP_K
 
 MAX_TRACKS = 512                       # include/dinodet.h dod_track_update: slots per stream
 MAX_STREAMS = 65535
+MAX_EMBED_DIM = 2048                   # dod_track_embed_dots: channels of an embedding (a multiple of 4)
 FREE, TENTATIVE, TRACKED, LOST = 0, 1, 2, 3       # slot states, as `tracks()["state"]` holds them
 _THRESHOLDS = ("track_thresh", "low_thresh", "new_thresh", "match_thresh", "second_thresh", "tentative_thresh")
 
@@ -52,10 +58,15 @@ class Tracker:
     defaults are ByteTrack's.  `update` takes the Detections of one frame of every stream (row s = stream s) and returns them with track
     ids; `reset` forgets the tracks of all or some streams; `tracks` returns the table; `check` is the one call that syncs.
     fuse_score: the first and the tentative pass use 1 - iou * score as cost instead of 1 - iou.  class_aware: a track is only matched
-    to rows of its own label.  device: where the table lives (None: the device of the first update's detections)."""
+    to rows of its own label.  device: where the table lives (None: the device of the first update's detections).
+    appearance: `update` also takes one unit vector per row (reid.roi_embed) and the first and the tentative pass use
+    min(that cost, d_app) with d_app = 0.5 * (1 - <track embedding, row embedding>), counted as 1 where it exceeds appearance_thresh or
+    where 1 - iou exceeds proximity_thresh (BoT-SORT's gates and defaults); a track's embedding is the one it was born with, blended
+    with every first- or tentative-pass hit as E = normalise(momentum * E + (1 - momentum) * e).  Without it nothing new is allocated."""
 
     def __init__(self, num_streams=1, max_tracks=128, track_thresh=0.5, low_thresh=0.1, new_thresh=0.6, match_thresh=0.8,
-                 second_thresh=0.5, tentative_thresh=0.7, max_age=30, fuse_score=True, class_aware=False, device=None):
+                 second_thresh=0.5, tentative_thresh=0.7, max_age=30, fuse_score=True, class_aware=False, device=None,
+                 appearance=False, appearance_thresh=0.25, proximity_thresh=0.5, momentum=0.9):
         S, T = int(num_streams), int(max_tracks)
         if not 1 <= S <= MAX_STREAMS:
             raise ValueError(f"num_streams must be in 1..{MAX_STREAMS}, got {num_streams}")
@@ -73,6 +84,19 @@ class Tracker:
             raise ValueError(f"max_age must be a non-negative integer, got {max_age}")
         p.max_age, p.fuse_score, p.class_aware = int(max_age), int(bool(fuse_score)), int(bool(class_aware))
         self.num_streams, self.max_tracks, self.params = S, T, p
+        self.appearance = bool(appearance)
+        self.app_params = None
+        if self.appearance:
+            q = nat.DodTrackAppParams()
+            for name, v in (("appearance_thresh", appearance_thresh), ("proximity_thresh", proximity_thresh), ("momentum", momentum)):
+                v = float(v)
+                if math.isnan(v):
+                    raise ValueError(f"{name} must be a number, got NaN")
+                setattr(q, name, v)
+            if not 0.0 <= float(momentum) <= 1.0:
+                raise ValueError(f"momentum must lie in [0, 1], got {momentum}")
+            self.app_params = q
+        self._emb = None                                         # slot_emb [S, T, D], allocated by the first update of an appearance tracker
         self.device = None if device is None else torch.device(device)
         self._state = self._ws = None
 
@@ -109,11 +133,25 @@ class Tracker:
             mask = m.to(self.device)
         with torch.cuda.device(self.device):
             nat.check(nat.lib().dod_track_reset(nat.ptr(state), self.num_streams, self.max_tracks, nat.ptr(mask), nat.stream_ptr()))
+            if self._emb is not None:
+                if idx is None:
+                    self._emb.zero_()
+                else:
+                    self._emb[torch.tensor(idx, dtype=torch.int64).to(self.device)] = 0.0
 
-    def update(self, detections):
+    def embeddings(self):
+        """slot_emb [S, T, D] fp32: the smoothed unit embedding of every slot (the tensor itself; a FREE slot's row is stale), or None
+        before the first update of an appearance tracker"""
+        if not self.appearance:
+            raise ValueError("this tracker keeps no embeddings (appearance=False)")
+        return self._emb
+
+    def update(self, detections, embeddings=None):
         """detections: a postprocess.Detections (or SlicedDetections / FusedDetections) of one frame per stream: scores [S, K] fp32,
         labels [S, K] int32, boxes [S, K, 4] fp32 pixel xyxy, counts [S] int32, K <= 1024.  Returns TrackedDetections on the same
-        tensors plus ids and track_boxes.  One launch on the current stream, no host sync."""
+        tensors plus ids and track_boxes.  One launch on the current stream, no host sync.  An appearance tracker takes
+        embeddings [S, K, D] fp32 (one unit vector per row, D a multiple of 4 up to 2048: reid.roi_embed) as well -- three launches:
+        similarities, association, the tracks' embeddings -- and a tracker without appearance takes none."""
         S, T = self.num_streams, self.max_tracks
         try:
             scores, labels, boxes, queries, counts = (detections.scores, detections.labels, detections.boxes, detections.queries,
@@ -132,6 +170,19 @@ class Tracker:
         if tuple(labels.shape) != (S, K) or tuple(boxes.shape) != (S, K, 4) or tuple(counts.shape) != (S,):
             raise ValueError(f"detections must hold labels [{S}, {K}], boxes [{S}, {K}, 4] and counts [{S}], got {tuple(labels.shape)}, "
                              f"{tuple(boxes.shape)} and {tuple(counts.shape)}")
+        if self.appearance != (embeddings is not None):
+            raise ValueError("update takes embeddings exactly when the tracker was made with appearance=True")
+        if self.appearance:
+            e = embeddings
+            if not (isinstance(e, torch.Tensor) and e.dtype == torch.float32 and e.dim() == 3 and tuple(e.shape[:2]) == (S, K)):
+                raise ValueError(f"embeddings must be a fp32 tensor [{S}, {K}, D]")
+            D = int(e.shape[2])
+            if not 4 <= D <= MAX_EMBED_DIM or D % 4:
+                raise ValueError(f"embeddings must hold 4..{MAX_EMBED_DIM} channels, a multiple of 4, got {D}")
+            if self._emb is not None and self._emb.shape[2] != D:
+                raise ValueError(f"embeddings have {D} channels, the tracks' {self._emb.shape[2]}")
+            if not e.is_cuda:
+                raise ValueError("embeddings must be on the GPU (there is no CPU fallback)")
         if not (scores.is_cuda and labels.is_cuda and boxes.is_cuda and counts.is_cuda):      # last: every argument is checked whether or not a GPU is present
             raise ValueError("detections must be on the GPU (there is no CPU fallback)")
         state = self._ensure(scores.device)
@@ -145,6 +196,21 @@ class Tracker:
             ws = self._ws[1]
             ids = torch.empty(S, K, dtype=torch.int32, device=self.device)
             tb = torch.empty(S, K, 4, dtype=torch.float32, device=self.device)
+            if self.appearance:
+                if embeddings.device != self.device:
+                    raise ValueError(f"the tracker lives on {self.device}, the embeddings on {embeddings.device}")
+                em = embeddings.contiguous()
+                if self._emb is None:
+                    self._emb = torch.zeros(S, T, D, dtype=torch.float32, device=self.device)
+                dots = torch.empty(S, T, K, dtype=torch.float32, device=self.device)
+                assoc = torch.empty(S, K, dtype=torch.int32, device=self.device)
+                nat.check(L.dod_track_embed_dots(nat.ptr(self._emb), nat.ptr(em), S, T, K, D, nat.ptr(dots), nat.stream_ptr()))
+                nat.check(L.dod_track_update_app(nat.ptr(state), S, T, nat.ptr(sc), nat.ptr(lb), nat.ptr(bx), nat.ptr(ct), K, C.byref(self.params),
+                                                 C.byref(self.app_params), nat.ptr(dots), nat.ptr(ids), nat.ptr(tb), nat.ptr(assoc), nat.ptr(ws),
+                                                 ws.numel(), nat.stream_ptr()))
+                nat.check(L.dod_track_embed_commit(nat.ptr(self._emb), nat.ptr(em), nat.ptr(assoc), S, T, K, D, self.app_params.momentum,
+                                                   nat.stream_ptr()))
+                return TrackedDetections(scores, labels, boxes, queries, counts, ids, tb)
             nat.check(L.dod_track_update(nat.ptr(state), S, T, nat.ptr(sc), nat.ptr(lb), nat.ptr(bx), nat.ptr(ct), K, C.byref(self.params),
                                          nat.ptr(ids), nat.ptr(tb), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
         return TrackedDetections(scores, labels, boxes, queries, counts, ids, tb)

@@ -113,6 +113,14 @@ int dod_num_tokens(const dod_handle* h, int H, int W);     /* N = (H/p)*(W/p) + 
 int dod_forward(dod_handle* h, const float* pixels, int B, int H, int W, float* detections,
                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* dod_forward that also hands out the decoder's memory -- the DINOv2 patch tokens after the final LayerNorm and projection, which the
+ * forward leaves in HBM anyway -- into `memory` [B, N, Dd] fp32 (caller-owned; token 0 of an image is CLS).  It is filled where tap 1000
+ * reads, between the backbone and the decoder schedule: one device-to-device copy in the fp32 and bf16x3 modes, one widening pass in the
+ * bf16 / fp8 modes.  Detections are bit-identical to dod_forward's on the same input, mode and workspace; the workspace query is the
+ * same.  memory == NULL returns DOD_ERR_INVALID.  What dod_roi_embed pools from. */
+int dod_forward_mem(dod_handle* h, const float* pixels, int B, int H, int W, float* detections, float* memory,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* The same forward from the device input pipeline's bytes: pixels_hwc = uint8 [B, H, W, 3] (dod_preprocess_u8: the resampled
  * image before ToTensor); the patch-embedding kernel applies ToTensor's x / 255 in its load stage, so the fp32 CHW batch of
  * train.py:584-587 never exists in HBM.  Same detections, bit for bit, as dod_forward on dod_preprocess's output.
@@ -724,7 +732,8 @@ int dod_match_assign(const float* cost, const int32_t* gt_offsets, int B, int Q,
  *      initialised from z, id = next_id++, score, label, last_frame = frame.  At frame 1 the state is TRACKED and the row gets the id;
  *      later the state is TENTATIVE and the row keeps -1.  Without a free slot the row is dropped and overflow += 1.
  * A slot that becomes FREE keeps its other fields until a birth overwrites them: only `state` says whether they mean anything.
- * Left out on purpose: ByteTrack's remove_duplicate_stracks, appearance / ReID costs, camera-motion compensation.  Two choices differ
+ * Left out on purpose: ByteTrack's remove_duplicate_stracks (duplicate removal) and camera-motion compensation; appearance costs are
+ * dod_track_update_app's, below.  Two choices differ
  * from ByteTrack: association is "scipy, then filter by the threshold" (what Ultralytics does without `lap`; ByteTrack calls lapjv
  * with a cost limit), and tentative slots are predicted too.
  * Outputs per row: ids int32 [S, K] (-1 where untracked or padding), track_boxes fp32 [S, K, 4] = the slot's post-update mean as
@@ -751,6 +760,66 @@ int dod_track_update(void* state, int S, int T, const float* scores, const int32
                      void* stream);
 int dod_track_export(const void* state, int S, int T, double* mean, double* cov, int32_t* slot_state, int32_t* id, int32_t* label,
                      int32_t* last_frame, float* score, int32_t* frame, int32_t* next_id, int32_t* overflow, void* stream);
+
+/* ---- ROI embeddings from the backbone tokens -------------------------------------------------------------------------
+ * One unit vector per box, pooled from features [B, N, D] fp32 (dod_forward_mem's memory, or dod_backbone_forward's features) by
+ * torchvision's aligned ROIAlign rules.  One launch, no host sync, no atomics; tests/roi_embed_cases.py restates it in numpy.
+ *   tokens      the tokens first_token + r * gw + c of image b form a gh x gw map (first_token = 1 skips CLS); the centre of token
+ *               (r, c) is at (c + 0.5, r + 0.5) in map units.
+ *   valid rows  row (b, k) is VALID when k < counts[b] (counts clamped to 0..K; NULL = K), its four coordinates are finite and x2 > x1,
+ *               y2 > y1, compared in fp32 -- dod_track_update's rule.
+ *   box         xyxy in the pixel frame sizes[b] = (height, width) (NULL = 1 x 1: normalised boxes).  In double from the widened values:
+ *               u = (x * gw) / width clipped to [0, gw], v = (y * gh) / height clipped to [0, gh]; a box that is empty after clipping
+ *               (not u2 > u1 and v2 > v1, which a size that is not a positive number ends in as well) is invalid.
+ *   samples     grid x grid points u_i = u1 + (i + 0.5) (u2 - u1) / grid, v_j likewise; each is sampled bilinearly at (u_i - 0.5, v_j - 0.5):
+ *               the coordinate is clamped to [0, gw - 1] / [0, gh - 1], the lower neighbour is its floor, the upper neighbour is clamped
+ *               to the last index.
+ *   pooled      the mean of the grid^2 samples.  Bilinear sampling on a product grid is separable, so this is
+ *                 p = sum_r sum_c wy[r] wx[c] f[r, c, :]
+ *               with wx[c] = (sum over the samples i of the weight they give column c, lower neighbour before upper) / grid and wy likewise:
+ *               non-negative, each set sums to 1, at most 2 * grid of each are non-zero.  The weights are computed in double and narrowed
+ *               once; w = wy[r] * wx[c] is one fp32 product; p accumulates in fp32 as p = fmaf(w, f, p) over the tokens with w != 0 in
+ *               row-major order.  A token with w == 0 is not read.
+ *   output      emb [B, K, D] = p / |p| (|p| from the fp32 p, in double; the quotient narrowed once), all zeros when |p| == 0.  Invalid
+ *               and padding rows are zeros.  Every element is written exactly once; nothing outside the gh * gw tokens of the row's own
+ *               image is read.
+ * DOD_ERR_INVALID before any launch: a NULL features / boxes / emb, features or emb not 16-byte aligned, B < 1, K outside 1..1024,
+ * D outside 4..2048 or not a multiple of 4, grid outside 1..8, gh or gw < 1, first_token < 0, first_token + gh * gw > N. */
+int dod_roi_embed(const float* features, int B, int N, int D, int first_token, int gh, int gw,
+                  const float* boxes /* [B, K, 4] xyxy */, const int32_t* counts /* [B] or NULL = K */,
+                  const float* sizes /* [B, 2] (height, width) or NULL = 1 x 1 */, int K, int grid,
+                  float* emb /* [B, K, D] */, void* stream);
+
+/* ---- appearance in the tracker's association: BoT-SORT's fusion on dod_roi_embed's vectors -----------------------------
+ * The track table keeps its layout; the slots' embeddings live in a tensor of the caller's, slot_emb [S, T, D] fp32 (zeros at the start;
+ * the row of a FREE slot is never read).  One frame is three launches behind dod_detect and dod_roi_embed (emb [S, K, D]):
+ *   dod_track_embed_dots     dots[s, t, j] = <slot_emb[s, t], emb[s, j]> for every t < T, j < K, fp32 [S, T, K]: the strided-batched fp32
+ *                            product of dod_op_gemm_f32x.
+ *   dod_track_update_app     dod_track_update with another cost in steps 3 and 5 (first and tentative association); steps 0..7 are
+ *                            otherwise the ones above, word for word, and step 4 stays pure IoU.  In double:
+ *                              d_iou = 1 - iou                               (iou as above, class_aware included)
+ *                              base  = fuse_score ? 1 - iou * score : d_iou  (dod_track_update's cost)
+ *                              d_app = 0.5 * max(0, 1 - (double) dots[s, slot, row])          (x > 0 ? x : 0)
+ *                              if (d_app > appearance_thresh) d_app = 1;   if (d_iou > proximity_thresh) d_app = 1
+ *                              cost  = (float) min(base, d_app)                               (d_app < base ? d_app : base)
+ *                            With appearance_thresh < 0 every d_app is 1, and while base <= 1 (scores >= 0) ids, track boxes and the table equal
+ *                            dod_track_update's bit for bit.  One more output, assoc int32 [S, K]: -1, or slot + 1024 * kind with
+ *                              kind 0  hit in step 4: the embedding is left alone (low-score boxes are the occluded ones)
+ *                              kind 1  hit in step 3 or 5: blend
+ *                              kind 2  birth in step 7: store -- at every frame, also where the birth is TENTATIVE and the row's id stays -1
+ *   dod_track_embed_commit   kind 2: slot_emb[s, slot] = emb[s, row].  kind 1: x = m E + (1 - m) e per element in double (m the widened
+ *                            fp32 momentum, one rounding per operation), E' = (float)(x / sqrt(sum x^2)), zeros when the sum is 0.  The
+ *                            rows of a frame name distinct slots: one wave per row, plain stores.
+ * DOD_ERR_INVALID before any launch: what dod_track_update rejects, a NULL app_params / dots / assoc / slot_emb / emb, a NaN threshold,
+ * a momentum outside [0, 1] (NaN included), D outside 4..2048 or not a multiple of 4. */
+typedef struct dod_track_app_params {
+  float appearance_thresh, proximity_thresh, momentum;      /* BoT-SORT's 0.25, 0.5, 0.9 */
+} dod_track_app_params;
+int dod_track_embed_dots(const float* slot_emb, const float* emb, int S, int T, int K, int D, float* dots, void* stream);
+int dod_track_update_app(void* state, int S, int T, const float* scores, const int32_t* labels, const float* boxes, const int32_t* counts,
+                         int K, const dod_track_params* params, const dod_track_app_params* app_params, const float* dots, int32_t* ids,
+                         float* track_boxes, int32_t* assoc, void* workspace, size_t workspace_bytes, void* stream);
+int dod_track_embed_commit(float* slot_emb, const float* emb, const int32_t* assoc, int S, int T, int K, int D, float momentum, void* stream);
 
 /* ---- COCO bbox evaluation on device (compute_coco_metrics, dino_detector/utils.py:243-276) ---------------------------
  * pycocotools' COCOeval (iouType 'bbox', useCats = 1, default parameters: 10 IoU thresholds, 101 recall thresholds, area
@@ -1223,7 +1292,9 @@ const char* dod_version(void);
  * publishes the layout of what dod_finalize_weights keeps (the dod_packed_format / dod_packed_array numbering), which a tool built against this
  * header reads through the struct: the revision is raised so that such a tool and the library agree on it.
  * dod_optim_step and dod_optim_ema_update (with struct dod_optim_options and struct dod_optim_ema_tensor, which no earlier entry reads)
- * joined revision 7 by name: no earlier signature or layout moved.  So did the tracker (dod_track_* with struct dod_track_params).
+ * joined revision 7 by name: no earlier signature or layout moved.  So did the tracker (dod_track_* with struct dod_track_params), and
+ * after it dod_forward_mem, dod_roi_embed and the appearance entries (dod_track_embed_dots, dod_track_update_app, dod_track_embed_commit with
+ * struct dod_track_app_params, which no earlier entry reads).
  * A C caller compiled against DOD_ABI_VERSION checks it once at load. */
 #define DOD_ABI_VERSION 7
 int dod_abi_version(void);

@@ -13,7 +13,14 @@ tracker must at least pay for the same frame, and next to the detect call it fol
              number of frames, synchronised; samples of all legs alternating in one process, warm-up first; median / p10 / p90 per call
   agreement  the device ids of the 48 forward frames equal the restatement's (asserted)
 One JSON line on stdout.
-    python tools/bench_track.py [--steps 30] [--warmup 5]"""
+    python tools/bench_track.py [--steps 30] [--warmup 5]
+  --appearance   the appearance tracker's launches instead, on the same two scenes with D = the default decoder width and a 16 x 16 token
+             map (224 x 224 input): roi_embed, embed_dots, update_app next to dod_track_update on the same frames (two tables, one
+             each), embed_commit, and model.track end to end with and without appearance (the default detector, batch = the scene's
+             streams).  Every call is timed on its own with a hipEvent pair, the versions alternating frame by frame, 200 frames a run,
+             two runs in the same call: median and p10 / p90 per call and run.  roi_embed's bytes are computed from the shapes (token
+             rows read + rows written).
+  --roi-only     nothing but 200 roi_embed launches per scene: for a kernel-trace run of its own"""
 import argparse
 import ctypes as C
 import json
@@ -86,12 +93,126 @@ def _stats(ms, reps):
             "samples": len(ms), "calls_per_sample": reps}
 
 
+def _per_call(fns, frames):
+    """every fn once per frame, in turn, each between its own event pair -> name -> [ms]"""
+    ev = {k: [] for k, _ in fns}
+    for _ in range(frames):
+        for k, fn in fns:
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            fn()
+            e.record()
+            ev[k].append((s, e))
+    torch.cuda.synchronize()
+    return {k: [s.elapsed_time(e) for s, e in v] for k, v in ev.items()}
+
+
+def _pcts(ms):
+    a = np.asarray(ms)
+    return {"median_ms": round(float(np.median(a)), 4), "p10_ms": round(float(np.percentile(a, 10)), 4), "p90_ms": round(float(np.percentile(a, 90)), 4)}
+
+
+def appearance(a):
+    from dinov2_od_amd import reid
+    from dinov2_od_amd.config import REF_DEFAULTS
+    from dinov2_od_amd.models import DINOv2ObjectDetector
+    from tests import roi_embed_cases as rc
+    L = nat.lib()
+    RUN, GH, GW, AREA = 200, 16, 16, 1450.0
+    model = None if a.roi_only else DINOv2ObjectDetector(pretrained=False).cuda().eval()
+    D = model._dc_cfg.hidden_dim if model is not None else (REF_DEFAULTS["hidden_dim"] or 768)
+    out = {"tool": "bench_track --appearance", "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "D": D, "token_map": [GH, GW],
+           "frames_per_run": RUN, "runs": 2}
+    for S, K, T, n_obj in SCENES:
+        frames = scene(S, K, n_obj, FRAMES)
+        dets = [Detections(*(torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (f[0], f[1], f[2])), torch.zeros(S, K, dtype=torch.int32, device="cuda"),
+                           torch.from_numpy(f[3]).cuda()) for f in frames]
+        mem = torch.from_numpy(synth.normal(5, f"bench_track.mem.{S}", (S, 1 + GH * GW, D), 1.0).astype(np.float32)).cuda()
+        sizes = torch.full((S, 2), AREA, device="cuda")
+        embs = [reid.roi_embed(mem, d.boxes, d.counts, sizes, 4, 1, (GH, GW)) for d in dets]
+        # bytes of one roi_embed launch, from the shapes: every touched token row is read once per box, every output row written once
+        rows = 0
+        for b in frames[0][2].reshape(-1, 4):
+            m = rc.map_box(b, (AREA, AREA), GH, GW)
+            if m is not None:
+                rows += int((rc.axis_weights(m[0], m[2], GW, 4) != 0).sum()) * int((rc.axis_weights(m[1], m[3], GH, 4) != 0).sum())
+        roi_bytes = (rows + S * K) * D * 4 + S * K * 16
+        order = list(range(FRAMES - 2, 0, -1)) + list(range(FRAMES))
+        pos = [0]
+
+        def nxt():
+            i = order[pos[0] % len(order)]
+            pos[0] += 1
+            return i
+
+        emb_out = torch.empty(S, K, D, device="cuda")
+        cur = [0]
+
+        def roi():
+            d = dets[cur[0]]
+            nat.check(L.dod_roi_embed(nat.ptr(mem), S, 1 + GH * GW, D, 1, GH, GW, nat.ptr(d.boxes), nat.ptr(d.counts), nat.ptr(sizes), K, 4, nat.ptr(emb_out),
+                                      nat.stream_ptr()))
+
+        key = f"S{S}_K{K}_T{T}"
+        if a.roi_only:
+            for _ in range(RUN):
+                roi()
+            torch.cuda.synchronize()
+            out[key] = {"roi_embed_bytes": roi_bytes, "token_rows_read": rows, "launches": RUN}
+            continue
+        plain, app = Tracker(num_streams=S, max_tracks=T), Tracker(num_streams=S, max_tracks=T, appearance=True)
+        for d, e in zip(dets, embs):                                        # both tables into their steady state
+            plain.update(d), app.update(d, e)
+        ids, tb = torch.empty(S, K, dtype=torch.int32, device="cuda"), torch.empty(S, K, 4, device="cuda")
+        assoc, dots = torch.empty(S, K, dtype=torch.int32, device="cuda"), torch.empty(S, T, K, device="cuda")
+        ws = torch.empty(L.dod_track_workspace_bytes(S, T, K), dtype=torch.uint8, device="cuda")
+
+        def step():
+            cur[0] = nxt()
+
+        def f_dots():
+            nat.check(L.dod_track_embed_dots(nat.ptr(app._emb), nat.ptr(embs[cur[0]]), S, T, K, D, nat.ptr(dots), nat.stream_ptr()))
+
+        def f_app():
+            d = dets[cur[0]]
+            nat.check(L.dod_track_update_app(nat.ptr(app._state), S, T, nat.ptr(d.scores), nat.ptr(d.labels), nat.ptr(d.boxes), nat.ptr(d.counts), K,
+                                             C.byref(app.params), C.byref(app.app_params), nat.ptr(dots), nat.ptr(ids), nat.ptr(tb), nat.ptr(assoc),
+                                             nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+
+        def f_plain():
+            d = dets[cur[0]]
+            nat.check(L.dod_track_update(nat.ptr(plain._state), S, T, nat.ptr(d.scores), nat.ptr(d.labels), nat.ptr(d.boxes), nat.ptr(d.counts), K,
+                                         C.byref(plain.params), nat.ptr(ids), nat.ptr(tb), nat.ptr(ws), ws.numel(), nat.stream_ptr()))
+
+        def f_commit():
+            nat.check(L.dod_track_embed_commit(nat.ptr(app._emb), nat.ptr(embs[cur[0]]), nat.ptr(assoc), S, T, K, D, app.app_params.momentum, nat.stream_ptr()))
+
+        x = torch.from_numpy(synth.make_pixels(S, 224, 224, seed=1).astype(np.float32)).cuda()
+        kw = dict(top_k=K, threshold=-1.0)
+        mp, ma = Tracker(num_streams=S, max_tracks=T), Tracker(num_streams=S, max_tracks=T, appearance=True)
+        legs = [("step", step), ("roi_embed", roi), ("embed_dots", f_dots), ("update_app", f_app), ("update_plain", f_plain), ("embed_commit", f_commit)]
+        e2e = [("track_plain", lambda: model.track(x, mp, **kw)), ("track_appearance", lambda: model.track(x, ma, **kw))]
+        _per_call(legs, a.warmup * 4), _per_call(e2e, a.warmup * 2)
+        leg = {"roi_embed_bytes": roi_bytes, "token_rows_read": rows, "dots_bytes_read_by_update_app": S * T * K * 4}
+        for run in range(2):
+            t = _per_call(legs, RUN)
+            t.update(_per_call(e2e, RUN))
+            leg[f"run{run + 1}"] = {k: _pcts(v) for k, v in t.items() if k != "step"}
+        leg["overflow"] = app.check()
+        out[key] = leg
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--appearance", action="store_true")
+    ap.add_argument("--roi-only", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_track needs a GPU"
+    if a.appearance or a.roi_only:
+        return appearance(a)
     L = nat.lib()
     out = {"tool": "bench_track", "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "frames": FRAMES}
     for S, K, T, n_obj in SCENES:
