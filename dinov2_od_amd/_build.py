@@ -23,7 +23,7 @@ OBJ = os.path.join(ROOT, "build", "obj")
 SOURCES = ["dod_api.hip", "dod_pack.hip", "dod_forward.hip", "gemm_bf16.hip", "gemm_f32.hip", "gemm_f32x3.hip", "attn_bf16.hip", "attn_f32.hip", "rowops.hip", "deform.hip",
            "postproc.hip", "matchcost.hip", "gemm_fp8.hip", "attn_x3.hip", "gemm_x3.hip", "gemm_dispatch.hip", "preproc.hip", "attn_f32m.hip", "gemm_pp.hip", "train_ops.hip", "dec_train.hip", "tail_train.hip", "patch_embed.hip",
            "criterion.hip", "assign.hip", "cocoeval.hip", "optim.hip", "detect.hip", "draw.hip", "detect_views.hip", "warp.hip", "jpeg.hip", "track.hip", "roi_embed.hip"]
-HEADERS = [os.path.join(CSRC, "dod_common.h"), os.path.join(CSRC, "dod_internal.h"), os.path.join(CSRC, "train_internal.h"), os.path.join(CSRC, "gemm_epi.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(CSRC, "gemm_f32x_epi.h"), os.path.join(CSRC, "operand_rows.h"), os.path.join(CSRC, "detect_select.h"), os.path.join(CSRC, "jpeg_entropy.h"), os.path.join(CSRC, "lsap.h"), os.path.join(ROOT, "include", "dinodet.h"),
+HEADERS = [os.path.join(CSRC, "dod_common.h"), os.path.join(CSRC, "dod_internal.h"), os.path.join(CSRC, "train_internal.h"), os.path.join(CSRC, "gemm_epi.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(CSRC, "gemm_f32x_epi.h"), os.path.join(CSRC, "operand_rows.h"), os.path.join(CSRC, "detect_select.h"), os.path.join(CSRC, "jpeg_entropy.h"), os.path.join(CSRC, "lsap.h"), os.path.join(CSRC, "stream_slabs.h"), os.path.join(ROOT, "include", "dinodet.h"),
            os.path.join(ROOT, "include", "dinodet_tuning.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-I" + os.path.join(ROOT, "include")]

@@ -371,11 +371,13 @@ class DodError(RuntimeError):
 _EXC = {1: ValueError, 2: KeyError, 3: RuntimeError, 4: RuntimeError}
 
 
-def check(rc, handle=None):
+def check(rc, handle=None, exc=_EXC, default=DodError):
+    """raise the exception of a non-zero dod_status with the message of the handle, or (no handle) of the calling thread;
+    exc / default: the status -> exception type mapping of a call site whose types are not _EXC's"""
     if rc != 0:
         msg = lib().dod_last_error(handle)
         msg = msg.decode() if msg else f"dinodet error {rc}"
-        raise _EXC.get(rc, DodError)(msg)
+        raise exc.get(rc, default)(msg)
 
 
 def stream_ptr():

@@ -84,10 +84,10 @@ extern "C" size_t dod_match_assign_workspace_bytes(int B, int Q, int G) {
 
 extern "C" int dod_match_assign(const float* cost, const int32_t* gt_offsets, int B, int Q, int G, const int64_t* labels, int C,
                                 int32_t* match, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!gt_offsets || !match || !status || B <= 0 || Q <= 0 || G < 0 || (labels && C <= 0)) return DOD_ERR_INVALID;
-  if (G > 0 && !cost) return DOD_ERR_INVALID;
-  if (!workspace || workspace_bytes < dod_match_assign_workspace_bytes(B, Q, G)) return DOD_ERR_STATE;
+  if (!gt_offsets || !match || !status || B <= 0 || Q <= 0 || G < 0 || (labels && C <= 0)) return dod_fail(DOD_ERR_INVALID, "dod_match_assign: null offsets / match / status, non-positive B / Q, negative G, or labels with C <= 0");
+  if (G > 0 && !cost) return dod_fail(DOD_ERR_INVALID, "dod_match_assign: null cost with G > 0");
+  if (!workspace || workspace_bytes < dod_match_assign_workspace_bytes(B, Q, G)) return dod_fail(DOD_ERR_STATE, "dod_match_assign: null or short workspace");
   hipLaunchKernelGGL(match_assign_kernel, dim3((unsigned)B), dim3(DOD_WAVE), 0, (hipStream_t)stream, cost, gt_offsets, Q, G,
                      (const long long*)labels, C, match, status, (unsigned char*)workspace);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_match_assign");
 }

@@ -240,20 +240,20 @@ __global__ __launch_bounds__(256) void crit_backward_kernel(CritArgs a, const fl
 
 int crit_nwg(int B, int Q) { return (int)(((long long)B * Q + kRowsPerWg - 1) / kRowsPerWg); }
 
-// host-side shape / stride validation shared by forward and backward
-int crit_args(CritArgs& a, const float* pred_logits, long long logits_row_stride, const float* pred_boxes,
+// host-side shape / stride validation shared by forward and backward (who: the entry point, for the message)
+int crit_args(const char* who, CritArgs& a, const float* pred_logits, long long logits_row_stride, const float* pred_boxes,
               long long boxes_row_stride, int layers, int B, int Q, int C, const int64_t* labels, const float* gt_boxes, int G,
               const int32_t* match, long long M, const float* num_boxes, float alpha, float gamma) {
-  if (!pred_logits || layers <= 0 || B <= 0 || Q <= 0 || C <= 0 || G < 0) return DOD_ERR_INVALID;
+  if (!pred_logits || layers <= 0 || B <= 0 || Q <= 0 || C <= 0 || G < 0) return dod_fail(DOD_ERR_INVALID, "%s: null pred_logits, non-positive layers / B / Q / C or negative G", who);
   const long long rows = (long long)layers * B * Q;
-  if ((long long)B * Q > 0x7fffffffLL || rows > 0x7fffffffLL || rows * C > 0x7fffffffffffLL) return DOD_ERR_INVALID;
-  if ((long long)layers * crit_nwg(B, Q) > 0x7fffffffLL) return DOD_ERR_INVALID;
-  if (logits_row_stride < C) return DOD_ERR_INVALID;
-  if (pred_boxes && boxes_row_stride < 4) return DOD_ERR_INVALID;
-  if (G > 0 && !labels) return DOD_ERR_INVALID;
-  if (G > 0 && pred_boxes && !gt_boxes) return DOD_ERR_INVALID;
-  if (match ? M != rows : G != rows) return DOD_ERR_INVALID;     // without a table, row r's target is labels[r]
-  if (!(gamma >= 0.f) || !(alpha == alpha)) return DOD_ERR_INVALID;
+  if ((long long)B * Q > 0x7fffffffLL || rows > 0x7fffffffLL || rows * C > 0x7fffffffffffLL) return dod_fail(DOD_ERR_INVALID, "%s: layers=%d B=%d Q=%d C=%d beyond the index range", who, layers, B, Q, C);
+  if ((long long)layers * crit_nwg(B, Q) > 0x7fffffffLL) return dod_fail(DOD_ERR_INVALID, "%s: layers=%d B=%d Q=%d beyond the grid range", who, layers, B, Q);
+  if (logits_row_stride < C) return dod_fail(DOD_ERR_INVALID, "%s: logits row stride %lld below C = %d", who, logits_row_stride, C);
+  if (pred_boxes && boxes_row_stride < 4) return dod_fail(DOD_ERR_INVALID, "%s: boxes row stride %lld below 4", who, boxes_row_stride);
+  if (G > 0 && !labels) return dod_fail(DOD_ERR_INVALID, "%s: null labels with G > 0", who);
+  if (G > 0 && pred_boxes && !gt_boxes) return dod_fail(DOD_ERR_INVALID, "%s: null gt_boxes with G > 0 and pred_boxes", who);
+  if (match ? M != rows : G != rows) return dod_fail(DOD_ERR_INVALID, "%s: %lld match / target rows for %lld predictions", who, match ? M : (long long)G, rows);     // without a table, row r's target is labels[r]
+  if (!(gamma >= 0.f) || !(alpha == alpha)) return dod_fail(DOD_ERR_INVALID, "%s: negative or NaN gamma, or NaN alpha", who);
   a.logits = pred_logits; a.ls = logits_row_stride;
   a.boxes = pred_boxes; a.bs = boxes_row_stride;
   a.R = B * Q; a.C = C; a.G = G; a.wgl = crit_nwg(B, Q);
@@ -270,22 +270,47 @@ extern "C" size_t dod_set_criterion_layers_workspace_bytes(int layers, int B, in
 }
 extern "C" size_t dod_set_criterion_workspace_bytes(int B, int Q, int C) { return dod_set_criterion_layers_workspace_bytes(1, B, Q, C); }
 
+// the two passes; their entry points are these with who = their own name (the one-layer forms: layers = 1)
+static int crit_forward(const char* who, const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
+                        int64_t boxes_row_stride, int layers, int B, int Q, int C, const int64_t* labels,
+                        const float* gt_boxes, int G, const int32_t* match, int M,
+                        const float* num_boxes, float alpha, float gamma, float* losses, float* elem_loss,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  CritArgs a;
+  const int rc = crit_args(who, a, pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, layers, B, Q, C, labels, gt_boxes, G,
+                           match, M, num_boxes, alpha, gamma);
+  if (rc != DOD_OK) return rc;
+  if (!losses || !workspace) return dod_fail(DOD_ERR_INVALID, "%s: null losses or workspace", who);
+  if (workspace_bytes < dod_set_criterion_layers_workspace_bytes(layers, B, Q, C)) return dod_fail(DOD_ERR_STATE, "%s: workspace too small", who);
+  float* part = (float*)workspace;
+  hipLaunchKernelGGL(crit_forward_kernel, dim3((unsigned)(layers * a.wgl)), dim3(256), 0, (hipStream_t)stream, a, part, elem_loss);
+  hipLaunchKernelGGL(crit_finalize_kernel, dim3((unsigned)layers), dim3(256), 0, (hipStream_t)stream, (const float*)part, a.wgl,
+                     num_boxes, losses);
+  return dod_launched(who);
+}
+
+static int crit_backward(const char* who, const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
+                         int64_t boxes_row_stride, int layers, int B, int Q, int C, const int64_t* labels,
+                         const float* gt_boxes, int G, const int32_t* match, int M,
+                         const float* num_boxes, float alpha, float gamma, const float* d_losses,
+                         const float* d_elem, float* d_logits, float* d_boxes, void* stream) {
+  CritArgs a;
+  const int rc = crit_args(who, a, pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, layers, B, Q, C, labels, gt_boxes, G,
+                           match, M, num_boxes, alpha, gamma);
+  if (rc != DOD_OK) return rc;
+  if (!d_logits || (!d_losses && !d_elem) || (pred_boxes && d_boxes && !d_losses)) return dod_fail(DOD_ERR_INVALID, "%s: null d_logits, or no upstream gradient for an output asked for", who);
+  hipLaunchKernelGGL(crit_backward_kernel, dim3((unsigned)(layers * a.wgl)), dim3(256), 0, (hipStream_t)stream, a, d_losses,
+                     d_elem, d_logits, d_boxes);
+  return dod_launched(who);
+}
+
 extern "C" int dod_set_criterion_layers_forward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
                                                 int64_t boxes_row_stride, int layers, int B, int Q, int C, const int64_t* labels,
                                                 const float* gt_boxes, int G, const int32_t* match, int M,
                                                 const float* num_boxes, float alpha, float gamma, float* losses, float* elem_loss,
                                                 void* workspace, size_t workspace_bytes, void* stream) {
-  CritArgs a;
-  const int rc = crit_args(a, pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, layers, B, Q, C, labels, gt_boxes, G,
-                           match, M, num_boxes, alpha, gamma);
-  if (rc != DOD_OK) return rc;
-  if (!losses || !workspace) return DOD_ERR_INVALID;
-  if (workspace_bytes < dod_set_criterion_layers_workspace_bytes(layers, B, Q, C)) return DOD_ERR_STATE;
-  float* part = (float*)workspace;
-  hipLaunchKernelGGL(crit_forward_kernel, dim3((unsigned)(layers * a.wgl)), dim3(256), 0, (hipStream_t)stream, a, part, elem_loss);
-  hipLaunchKernelGGL(crit_finalize_kernel, dim3((unsigned)layers), dim3(256), 0, (hipStream_t)stream, (const float*)part, a.wgl,
-                     num_boxes, losses);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return crit_forward("dod_set_criterion_layers_forward", pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, layers, B, Q, C, labels, gt_boxes, G,
+                      match, M, num_boxes, alpha, gamma, losses, elem_loss, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dod_set_criterion_layers_backward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
@@ -293,24 +318,17 @@ extern "C" int dod_set_criterion_layers_backward(const float* pred_logits, int64
                                                  const float* gt_boxes, int G, const int32_t* match, int M,
                                                  const float* num_boxes, float alpha, float gamma, const float* d_losses,
                                                  const float* d_elem, float* d_logits, float* d_boxes, void* stream) {
-  CritArgs a;
-  const int rc = crit_args(a, pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, layers, B, Q, C, labels, gt_boxes, G,
-                           match, M, num_boxes, alpha, gamma);
-  if (rc != DOD_OK) return rc;
-  if (!d_logits || (!d_losses && !d_elem) || (pred_boxes && d_boxes && !d_losses)) return DOD_ERR_INVALID;
-  hipLaunchKernelGGL(crit_backward_kernel, dim3((unsigned)(layers * a.wgl)), dim3(256), 0, (hipStream_t)stream, a, d_losses,
-                     d_elem, d_logits, d_boxes);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return crit_backward("dod_set_criterion_layers_backward", pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, layers, B, Q, C, labels, gt_boxes, G,
+                       match, M, num_boxes, alpha, gamma, d_losses, d_elem, d_logits, d_boxes, stream);
 }
 
-// one layer: the same kernels with layers = 1
 extern "C" int dod_set_criterion_forward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
                                          int64_t boxes_row_stride, int B, int Q, int C, const int64_t* labels,
                                          const float* gt_boxes, int G, const int32_t* match, int M, const float* num_boxes,
                                          float alpha, float gamma, float* losses, float* elem_loss, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-  return dod_set_criterion_layers_forward(pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, 1, B, Q, C, labels, gt_boxes, G,
-                                          match, M, num_boxes, alpha, gamma, losses, elem_loss, workspace, workspace_bytes, stream);
+  return crit_forward("dod_set_criterion_forward", pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, 1, B, Q, C, labels, gt_boxes, G,
+                      match, M, num_boxes, alpha, gamma, losses, elem_loss, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dod_set_criterion_backward(const float* pred_logits, int64_t logits_row_stride, const float* pred_boxes,
@@ -318,6 +336,6 @@ extern "C" int dod_set_criterion_backward(const float* pred_logits, int64_t logi
                                           const float* gt_boxes, int G, const int32_t* match, int M,
                                           const float* num_boxes, float alpha, float gamma, const float* d_losses,
                                           const float* d_elem, float* d_logits, float* d_boxes, void* stream) {
-  return dod_set_criterion_layers_backward(pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, 1, B, Q, C, labels, gt_boxes, G,
-                                           match, M, num_boxes, alpha, gamma, d_losses, d_elem, d_logits, d_boxes, stream);
+  return crit_backward("dod_set_criterion_backward", pred_logits, logits_row_stride, pred_boxes, boxes_row_stride, 1, B, Q, C, labels, gt_boxes, G,
+                       match, M, num_boxes, alpha, gamma, d_losses, d_elem, d_logits, d_boxes, stream);
 }

@@ -212,7 +212,7 @@ int build_cat(const Dims& d, const dod_dec_train_params* p, const Scratch& sc, h
 int deform_forward(const dod_config* cfg, bool aux, const dod_dec_train_params* p, const float* memory, int B, int N, float dropout_p, uint64_t seed, float* det,
                    void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
   Dims d;
-  if (!make_dims(cfg, B, N, &d)) return tfail(DOD_ERR_INVALID, "decoder train: unsupported configuration (deformable branch, head_dim <= 128, Dd <= 1024, Q <= %d)", MHA_MAXQ);
+  if (!make_dims(cfg, B, N, &d)) return dod_fail(DOD_ERR_INVALID, "decoder train: unsupported configuration (deformable branch, head_dim <= 128, Dd <= 1024, Q <= %d)", MHA_MAXQ);
   const int nh = aux ? d.L : 1;
   Tape t; Scratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
   int rc = entry_check("decoder train", p && memory && det && tape && ws, dropout_p, tape_bytes, carve_tape(d, nh, tape, t) + 256, ws_bytes, carve_scratch(d, nh, ws, sc) + 256); if (rc) return rc;
@@ -242,7 +242,7 @@ int deform_backward(const dod_config* cfg, bool aux, const dod_dec_train_params*
                     const float* d_det, const void* tape, size_t tape_bytes, const dod_dec_train_params* grads, float* d_memory, void* ws, size_t ws_bytes,
                     void* stream) {
   Dims d;
-  if (!make_dims(cfg, B, N, &d)) return tfail(DOD_ERR_INVALID, "decoder train: unsupported configuration");
+  if (!make_dims(cfg, B, N, &d)) return dod_fail(DOD_ERR_INVALID, "decoder train: unsupported configuration");
   const int nh = aux ? d.L : 1;
   Tape t; Scratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
   int rc = entry_check("decoder train", p && memory && d_det && tape && grads && ws, 0.f, tape_bytes, carve_tape(d, nh, tape, t) + 256, ws_bytes, carve_scratch(d, nh, ws, sc) + 256); if (rc) return rc;
@@ -370,7 +370,7 @@ size_t dod_dense_decoder_train_workspace_bytes(const dod_config* cfg, int B, int
 int dod_dense_decoder_train_forward(const dod_config* cfg, const dod_dense_dec_train_params* p, const float* memory, int B, int N, float dropout_p,
                                     uint64_t seed, float* det, void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
   QDims d;
-  if (!make_ddims(cfg, B, N, &d)) return tfail(DOD_ERR_INVALID, "dense decoder train: unsupported configuration (nn.TransformerDecoder branch, head_dim <= 128, Dd <= 1024, Q and N <= %d, <= 16 layers)", MHA_MAXQ);
+  if (!make_ddims(cfg, B, N, &d)) return dod_fail(DOD_ERR_INVALID, "dense decoder train: unsupported configuration (nn.TransformerDecoder branch, head_dim <= 128, Dd <= 1024, Q and N <= %d, <= 16 layers)", MHA_MAXQ);
   DTape t; DScratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
   int rc = entry_check("dense decoder train", dense_params_ok(p, d.L) && memory && det && tape && ws, dropout_p, tape_bytes, carve_dtape(d, tape, t) + 256, ws_bytes,
                        carve_dscratch(d, ws, sc) + 256); if (rc) return rc;
@@ -396,7 +396,7 @@ int dod_dense_decoder_train_backward(const dod_config* cfg, const dod_dense_dec_
                                      uint64_t seed, const float* d_det, const void* tape, size_t tape_bytes, const dod_dense_dec_train_params* grads,
                                      float* d_memory, void* ws, size_t ws_bytes, void* stream) {
   QDims d;
-  if (!make_ddims(cfg, B, N, &d)) return tfail(DOD_ERR_INVALID, "dense decoder train: unsupported configuration");
+  if (!make_ddims(cfg, B, N, &d)) return dod_fail(DOD_ERR_INVALID, "dense decoder train: unsupported configuration");
   DTape t; DScratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
   int rc = entry_check("dense decoder train", dense_params_ok(p, d.L) && dense_params_ok(grads, d.L) && memory && d_det && tape && ws, 0.f, tape_bytes,
                        carve_dtape(d, tape, t) + 256, ws_bytes, carve_dscratch(d, ws, sc) + 256); if (rc) return rc;

@@ -82,12 +82,12 @@ extern "C" size_t dod_detect_workspace_bytes(int B, int Q, int C, int K) {
 extern "C" int dod_detect(const float* det, int B, int Q, int C, int first_class, const float* sizes, float threshold, int K,
                           float iou_threshold, int class_agnostic, int clamp, float* scores, int32_t* labels, int32_t* queries,
                           float* boxes, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!det || !scores || !labels || !queries || !boxes || !counts) return DOD_ERR_INVALID;
-  if (!det_shape_ok(B, Q, C, K) || first_class < 0 || first_class >= C) return DOD_ERR_INVALID;
+  if (!det || !scores || !labels || !queries || !boxes || !counts) return dod_fail(DOD_ERR_INVALID, "dod_detect: null argument");
+  if (!det_shape_ok(B, Q, C, K) || first_class < 0 || first_class >= C) return dod_fail(DOD_ERR_INVALID, "dod_detect: B=%d Q=%d C=%d K=%d outside the limits, or first_class = %d outside [0, C)", B, Q, C, K, first_class);
   const bool nms = iou_threshold >= 0.0f;
-  if (nms && K > DET_NMS_MAX_K) return DOD_ERR_INVALID;
-  if (((uintptr_t)boxes & 15) != 0) return DOD_ERR_INVALID;      // rows are stored as float4
-  if (!workspace || workspace_bytes < dod_detect_workspace_bytes(B, Q, C, K)) return DOD_ERR_INVALID;
+  if (nms && K > DET_NMS_MAX_K) return dod_fail(DOD_ERR_INVALID, "dod_detect: K = %d above the %d rows the NMS takes", K, DET_NMS_MAX_K);
+  if (((uintptr_t)boxes & 15) != 0) return dod_fail(DOD_ERR_INVALID, "dod_detect: boxes not 16-byte aligned");      // rows are stored as float4
+  if (!workspace || workspace_bytes < dod_detect_workspace_bytes(B, Q, C, K)) return dod_fail(DOD_ERR_INVALID, "dod_detect: null or short workspace");
   DetArgs a;
   a.det = det; a.sizes = sizes; a.keys = (unsigned*)workspace;
   a.out = DetOut{scores, labels, nullptr, queries, boxes, nullptr, counts};
@@ -97,5 +97,5 @@ extern "C" int dod_detect(const float* det, int B, int Q, int C, int first_class
   hipStream_t s = (hipStream_t)stream;
   if (nms) hipLaunchKernelGGL(det_kernel<true>, dim3(B), dim3(DET_THREADS), 0, s, a);
   else hipLaunchKernelGGL(det_kernel<false>, dim3(B), dim3(DET_THREADS), 0, s, a);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_detect");
 }

@@ -268,24 +268,26 @@ extern "C" size_t dod_detect_views_workspace_bytes(int V, int Q, int C, int K) {
 }
 extern "C" size_t dod_fuse_views_workspace_bytes(int V, int Q, int C, int K) { return dod_detect_views_workspace_bytes(V, Q, C, K); }
 
-// What dod_detect_views and dod_fuse_views check alike, and the DvArgs of both; false = DOD_ERR_INVALID.  `out` is complete: an entry
-// point checks its own arguments (nms_metric, conf, members) itself.
-static bool dv_prepare(DvArgs& a, const float* det, int B, int V, int Q, int C, const int32_t* view_offsets, const int32_t* view_rects,
+// What dod_detect_views and dod_fuse_views check alike, and the DvArgs of both; a dod_status, its message under the entry point's
+// name `who`.  `out` is complete: an entry point checks its own arguments (nms_metric, conf, members) itself.
+static int dv_prepare(const char* who, DvArgs& a, const float* det, int B, int V, int Q, int C, const int32_t* view_offsets, const int32_t* view_rects,
                        const uint8_t* view_flips, const float* sizes, int first_class, float threshold, int K, float iou_threshold,
                        int nms_metric, int class_agnostic, int clamp, float edge_margin, const DetOut& out, void* workspace,
                        size_t workspace_bytes) {
-  if (!view_offsets || !sizes || !out.scores || !out.labels || !out.views || !out.queries || !out.boxes || !out.counts) return false;
-  if (B < 1 || !dv_shape_ok(V, Q, C, K) || first_class < 0 || first_class >= C) return false;
-  if (V > 0 && (!det || !view_rects || !view_flips)) return false;
-  if (((uintptr_t)out.boxes & 15) != 0) return false;            // rows are stored as float4
-  if (!workspace || workspace_bytes < dod_detect_views_workspace_bytes(V, Q, C, K)) return false;
+  if (!view_offsets || !sizes || !out.scores || !out.labels || !out.views || !out.queries || !out.boxes || !out.counts)
+    return dod_fail(DOD_ERR_INVALID, "%s: null view_offsets, sizes or output", who);
+  if (B < 1 || !dv_shape_ok(V, Q, C, K) || first_class < 0 || first_class >= C)
+    return dod_fail(DOD_ERR_INVALID, "%s: B=%d V=%d Q=%d C=%d K=%d outside the limits, or first_class = %d outside [0, C)", who, B, V, Q, C, K, first_class);
+  if (V > 0 && (!det || !view_rects || !view_flips)) return dod_fail(DOD_ERR_INVALID, "%s: null det, view_rects or view_flips with V > 0", who);
+  if (((uintptr_t)out.boxes & 15) != 0) return dod_fail(DOD_ERR_INVALID, "%s: boxes not 16-byte aligned", who);            // rows are stored as float4
+  if (!workspace || workspace_bytes < dod_detect_views_workspace_bytes(V, Q, C, K)) return dod_fail(DOD_ERR_INVALID, "%s: null or short workspace", who);
   a.det = det; a.voffs = view_offsets; a.rects = view_rects; a.flips = view_flips; a.sizes = sizes;
   a.keys = (unsigned*)workspace; a.cut = (unsigned char*)workspace + dv_keys_bytes(V, Q, C);
   a.out = out;
   a.V = V; a.Q = Q; a.C = C; a.first_class = first_class; a.K = K;
   a.threshold = threshold; a.iou = iou_threshold; a.margin = edge_margin;
   a.metric = nms_metric; a.agnostic = class_agnostic; a.clamp = clamp;
-  return true;
+  return DOD_OK;
 }
 
 extern "C" int dod_detect_views(const float* det, int B, int V, int Q, int C, const int32_t* view_offsets, const int32_t* view_rects,
@@ -294,15 +296,15 @@ extern "C" int dod_detect_views(const float* det, int B, int V, int Q, int C, co
                                 int32_t* labels, int32_t* views, int32_t* queries, float* boxes, int32_t* counts, void* workspace,
                                 size_t workspace_bytes, void* stream) {
   DvArgs a;
-  if (nms_metric != 0 && nms_metric != 1) return DOD_ERR_INVALID;
-  if (!dv_prepare(a, det, B, V, Q, C, view_offsets, view_rects, view_flips, sizes, first_class, threshold, K, iou_threshold, nms_metric,
+  if (nms_metric != 0 && nms_metric != 1) return dod_fail(DOD_ERR_INVALID, "dod_detect_views: nms_metric = %d is neither 0 nor 1", nms_metric);
+  if (const int rc = dv_prepare("dod_detect_views", a, det, B, V, Q, C, view_offsets, view_rects, view_flips, sizes, first_class, threshold, K, iou_threshold, nms_metric,
                   class_agnostic, clamp, edge_margin, DetOut{scores, labels, views, queries, boxes, nullptr, counts}, workspace, workspace_bytes))
-    return DOD_ERR_INVALID;
+    return rc;
   hipStream_t s = (hipStream_t)stream;
   if (!(iou_threshold >= 0.0f)) hipLaunchKernelGGL(dv_kernel<0>, dim3(B), dim3(DET_THREADS), 0, s, a);
   else if (K <= 512) hipLaunchKernelGGL(dv_kernel<512>, dim3(B), dim3(DET_THREADS), 0, s, a);
   else hipLaunchKernelGGL(dv_kernel<DV_NMS_MAX_K>, dim3(B), dim3(DET_THREADS), 0, s, a);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_detect_views");
 }
 
 extern "C" int dod_fuse_views(const float* det, int B, int V, int Q, int C, const int32_t* view_offsets, const int32_t* view_rects,
@@ -311,11 +313,11 @@ extern "C" int dod_fuse_views(const float* det, int B, int V, int Q, int C, cons
                               int32_t* labels, int32_t* views, int32_t* queries, float* boxes, int32_t* members, int32_t* counts,
                               void* workspace, size_t workspace_bytes, void* stream) {
   DvArgs a;
-  if (!members || (conf != 0 && conf != 1)) return DOD_ERR_INVALID;
-  if (!dv_prepare(a, det, B, V, Q, C, view_offsets, view_rects, view_flips, sizes, first_class, threshold, K, iou_threshold, 0,
+  if (!members || (conf != 0 && conf != 1)) return dod_fail(DOD_ERR_INVALID, "dod_fuse_views: null members, or conf = %d is neither 0 nor 1", conf);
+  if (const int rc = dv_prepare("dod_fuse_views", a, det, B, V, Q, C, view_offsets, view_rects, view_flips, sizes, first_class, threshold, K, iou_threshold, 0,
                   class_agnostic, clamp, edge_margin, DetOut{scores, labels, views, queries, boxes, members, counts}, workspace, workspace_bytes))
-    return DOD_ERR_INVALID;
+    return rc;
   hipLaunchKernelGGL(fv_kernel, dim3(B), dim3(DET_THREADS), 0, (hipStream_t)stream, a, conf);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_fuse_views");
 }
 

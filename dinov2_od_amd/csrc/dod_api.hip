@@ -10,13 +10,18 @@
 
 using namespace dod;
 
-static std::string g_err;
+// The calling thread's message slot (include/dinodet.h "Errors"): every handle-less failure of the library is written here.
+static thread_local std::string t_err;
 
 static int vfail(const dod_handle* h, int code, const char* fmt, va_list ap, int launch_rc = 0) {
   char buf[512];
   const int n = vsnprintf(buf, sizeof buf, fmt, ap);
   if (launch_rc && n >= 0 && (size_t)n < sizeof buf) snprintf(buf + n, sizeof buf - n, " rejected (rc %d)", launch_rc);
-  if (h) h->err = buf; else g_err = buf;
+  if (h) h->err = buf; else t_err = buf;
+  return code;
+}
+int dod_fail(int code, const char* fmt, ...) {
+  va_list ap; va_start(ap, fmt); code = vfail(nullptr, code, fmt, ap); va_end(ap);
   return code;
 }
 int dod::fail(const dod_handle* h, int code, const char* fmt, ...) {
@@ -94,7 +99,9 @@ int dod_device_count(void) {
   return hipGetDeviceCount(&n) == hipSuccess ? n : -1;
 }
 
-const char* dod_last_error(const dod_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
+const char* dod_last_error(const dod_handle* h) { return h ? h->err.c_str() : t_err.c_str(); }
+const char* dod_decoder_train_last_error(void) { return t_err.c_str(); }
+const char* dod_optim_last_error(void) { return t_err.c_str(); }
 
 int dod_create(const dod_config* cfg, dod_handle** out) {
   if (!cfg || !out) return fail(nullptr, DOD_ERR_INVALID, "null argument");

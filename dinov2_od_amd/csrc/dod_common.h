@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include "../../include/dinodet.h"      // dod_status
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -13,6 +14,17 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef unsigned short bf16_t;   // storage type of bf16 in memory
 
 #define DOD_WAVE 64
+
+// ---- errors without a handle (include/dinodet.h "Errors"): dod_fail writes the calling thread's message slot (dod_api.hip) and returns `code`.
+// Every extern "C" exit that returns a non-zero dod_status without a handle goes through it, with a message that begins with the entry point's name.
+int dod_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// the end of an entry point that launched on a stream: DOD_OK, or the launch error under the entry point's name
+inline int dod_launched(const char* name) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DOD_OK : dod_fail(DOD_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
+}
+// per-device process state is kept in arrays of 16: the current device's index, or -1 (no device, or one beyond the arrays)
+int current_device_slot();            // gemm_dispatch.hip
 
 namespace dod {
 // the one rounding of every workspace carve: the parts of a workspace start 256 bytes apart
@@ -366,13 +378,15 @@ int run_gemm_h2(const void* A, int lda, const void* W, int ldw, int M, int N, in
 int run_gemm_ksplit_reduce(const float* part, int S, int R, int N, const GemmEpi& e, int m_base, int M, int K, hipStream_t s);
 int run_gemm_fp8(int form, const unsigned char* A, int lda, const unsigned char* W, int ldw, int M, int N, int K, const GemmEpi& e, int gm, hipStream_t s);      // gemm_fp8.hip
 int run_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int N, int K, const GemmEpi& e, int S, hipStream_t s);               // gemm_f32.hip
-// Scratch of the tail split's K-split launch (gemm_pp.hip): gemm_tail_reserve(bytes) allocates it outside any stream capture.  One slab of
-// `bytes` per launching stream (four per device, least-recently-used first: a forward may run as two concurrent micro-batches on two
-// streams, engine.py).  The slices are summed in a fixed order, so results do not depend on scheduling.
+// Scratch of the tail split's K-split launch and of the fp32 K split: two instances of the one stream-slab pool (gemm_dispatch.hip).
+// gemm_tail_reserve(bytes) / gemm_f32_ksplit_reserve() allocate outside any stream capture.  One slab per launching stream (four per device,
+// least-recently-used first: a forward may run as two concurrent micro-batches on two streams, engine.py).  The tail split's slices are
+// summed in a fixed order, so results do not depend on scheduling.
 int gemm_tail_reserve(size_t bytes);
 size_t gemm_tail_reserved();              // bytes per slab on the current device (0: none)
 float* gemm_tail_slab(hipStream_t s);     // the launching stream's slab
-bool gemm_f32_ksplit_reserved();          // gemm_f32.hip: the current device has the fp32 K split's slabs
+bool gemm_f32_ksplit_reserved();          // the current device has the fp32 K split's slabs
+char* gemm_f32_ksplit_slab(hipStream_t s);
 // tgt[b][q][:] = query_embed[q][:]
 int launch_bcast_rows(const float* src, float* dst, int B, int rows, int D, hipStream_t s);
 

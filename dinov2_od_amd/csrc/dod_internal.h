@@ -83,7 +83,7 @@ struct dod_handle {
 namespace dod {
 
 // ------------------------------------------------------------------------------------------- errors
-int fail(const dod_handle* h, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));   // dod_api.hip; h null: the process-wide string
+int fail(const dod_handle* h, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));   // dod_api.hip; h null: dod_fail's slot of the calling thread
 // a launcher's return code (0 ok, 3 = the HIP runtime refused the launch, else a rejected shape / argument) as DOD_ERR_* with "<what> rejected (rc r)"
 int rejected(const dod_handle* h, int r, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 #define HIPCHK(h, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return dod::fail(h, DOD_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)

@@ -369,14 +369,14 @@ static DrwLayer drw_layer(const dod_draw_layer* l) {
 
 extern "C" int dod_draw_detections(const void* images, int images_fp32, int B, int H, int W, const dod_draw_layer* below,
                                    const dod_draw_layer* above, const dod_draw_style* style, uint8_t* out, void* stream) {
-  if (!images || !out || !style || (const void*)out == images) return DOD_ERR_INVALID;
-  if (images_fp32 != 0 && images_fp32 != 1) return DOD_ERR_INVALID;
-  if (B < 1 || H < 1 || W < 1 || B > DRW_MAX_B || H > DRW_MAX_DIM || W > DRW_MAX_DIM) return DOD_ERR_INVALID;
-  if (images_fp32 && ((uintptr_t)images & 3) != 0) return DOD_ERR_INVALID;
-  if (style->thickness < 1 || style->thickness > 8 || style->fill_alpha < 0 || style->fill_alpha > 255) return DOD_ERR_INVALID;
-  if (style->font_scale < 0 || style->font_scale > 4 || (style->font_scale > 0 && !style->font)) return DOD_ERR_INVALID;
-  if (style->names && (style->n_names < 1 || style->name_len < 1 || style->name_len > DRW_MAX_NAME)) return DOD_ERR_INVALID;
-  if (!drw_layer_ok(below, style) || !drw_layer_ok(above, style)) return DOD_ERR_INVALID;
+  if (!images || !out || !style || (const void*)out == images) return dod_fail(DOD_ERR_INVALID, "dod_draw_detections: null images / out / style, or out aliases images");
+  if (images_fp32 != 0 && images_fp32 != 1) return dod_fail(DOD_ERR_INVALID, "dod_draw_detections: images_fp32 = %d is neither 0 nor 1", images_fp32);
+  if (B < 1 || H < 1 || W < 1 || B > DRW_MAX_B || H > DRW_MAX_DIM || W > DRW_MAX_DIM) return dod_fail(DOD_ERR_INVALID, "dod_draw_detections: B=%d H=%d W=%d outside the limits", B, H, W);
+  if (images_fp32 && ((uintptr_t)images & 3) != 0) return dod_fail(DOD_ERR_INVALID, "dod_draw_detections: fp32 images not 4-byte aligned");
+  if (style->thickness < 1 || style->thickness > 8 || style->fill_alpha < 0 || style->fill_alpha > 255) return dod_fail(DOD_ERR_INVALID, "dod_draw_detections: thickness outside 1..8 or fill_alpha outside 0..255");
+  if (style->font_scale < 0 || style->font_scale > 4 || (style->font_scale > 0 && !style->font)) return dod_fail(DOD_ERR_INVALID, "dod_draw_detections: font_scale outside 0..4, or a font_scale without a font");
+  if (style->names && (style->n_names < 1 || style->name_len < 1 || style->name_len > DRW_MAX_NAME)) return dod_fail(DOD_ERR_INVALID, "dod_draw_detections: names with n_names < 1 or name_len outside the limits");
+  if (!drw_layer_ok(below, style) || !drw_layer_ok(above, style)) return dod_fail(DOD_ERR_INVALID, "dod_draw_detections: a layer with K or format outside the limits, null labels, boxes not 16-byte aligned, or use_palette without a palette");
   DrwArgs a = {};
   a.img = images; a.out = out; a.fp32 = images_fp32; a.B = B; a.H = H; a.W = W;
   a.layer[0] = drw_layer(below); a.layer[1] = drw_layer(above);
@@ -386,5 +386,5 @@ extern "C" int dod_draw_detections(const void* images, int images_fp32, int B, i
   a.font = style->font;
   const dim3 grid((W + DRW_TW - 1) / DRW_TW, (H + DRW_TH - 1) / DRW_TH, B);
   hipLaunchKernelGGL(drw_kernel, grid, dim3(DRW_THREADS), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_draw_detections");
 }

@@ -1,28 +1,86 @@
 // Executor of the inference GEMM plans (gemm_plan.h): the one place that gathers what the dispatch policy reads -- the device's CU count, the
 // scratch reserved, the test options, the tuning-build overrides, the policy-relevant facts of the epilogue -- and runs a plan's steps through
 // the run_* function of each form (dod_common.h).  launch_gemm_bf16 / _x3 / _h2 / _fp8 / _f32 check their arguments and end here.
+// The dispatch's per-device process state lives here too: the CU counts and the two scratch pools (SlabPool).
 #include "dod_common.h"
 #include "gemm_epi.h"
 #include "gemm_plan.h"
+#include "stream_slabs.h"
 #include <atomic>
 #include <cstring>
+#include <mutex>
+
+int current_device_slot() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16 ? dev : -1;
+}
 
 int device_cus() {
   static std::atomic<int> cus[16];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
+  const int dev = current_device_slot();
+  if (dev < 0) return 256;
   int c = cus[dev].load();
   if (!c) { (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev); c = c > 0 ? c : 256; cus[dev].store(c); }
   return c;
 }
 
 void gemm_lds_attr_once(bool* done, const KernelLds* k, int n) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16 || done[dev]) return;
+  const int dev = current_device_slot();
+  if (dev < 0 || done[dev]) return;
   for (int i = 0; i < n; ++i) (void)hipFuncSetAttribute(k[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, k[i].bytes);
   done[dev] = true;
 }
+
+// ---- stream-slab pool: per device, blocks of SLAB_SLOTS slabs, one slab per launching stream (stream_slabs.h holds the rule).  reserve()
+// runs outside any stream capture.  A pool only ever GROWS, by adding a block (at most max_gens of them), and never frees one: captured
+// hipGraphs keep slab addresses.  The newest block is the one handed out; growing forgets the owners.
+#define SLAB_SLOTS 4
+struct SlabPool {
+  const int max_gens;          // blocks a device may ever get
+  const bool zero_fill;        // the block starts zeroed (a pool whose kernels leave their counters zero between launches)
+  std::mutex mu;               // autograd / DataLoader threads may launch GEMMs beside the main thread
+  struct Dev { char* block; int gens; size_t bytes; StreamSlabs<SLAB_SLOTS> slots; } dev[16] = {};
+
+  // 0: every slab of the current device holds `bytes`; 3: no device, the generation limit, or the allocation failed
+  int reserve(size_t bytes) {
+    const int d = current_device_slot();
+    if (d < 0) return 3;
+    std::lock_guard<std::mutex> lk(mu);
+    Dev& v = dev[d];
+    if (v.bytes >= bytes) return 0;
+    if (v.gens >= max_gens) return 3;  // never free a block a captured graph may still reference: refuse instead
+    char* blk = nullptr;
+    if (hipMalloc((void**)&blk, bytes * SLAB_SLOTS) != hipSuccess) return 3;
+    if (zero_fill && hipMemset(blk, 0, bytes * SLAB_SLOTS) != hipSuccess) { (void)hipFree(blk); return 3; }
+    v.block = blk; ++v.gens; v.bytes = bytes;
+    v.slots.reset();
+    return 0;
+  }
+  size_t reserved() {                  // bytes per slab on the current device (0: none)
+    const int d = current_device_slot();
+    if (d < 0) return 0;
+    std::lock_guard<std::mutex> lk(mu);
+    return dev[d].bytes;
+  }
+  char* slab(hipStream_t s) {          // the launching stream's slab (null: nothing reserved)
+    const int d = current_device_slot();
+    if (d < 0) return nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    Dev& v = dev[d];
+    return v.block ? v.block + (size_t)v.slots.pick(s) * v.bytes : nullptr;
+  }
+};
+static SlabPool g_tail_pool{4, false};      // tail split's K-split partials (gemm_pp.hip): sized by the caller, growable
+// fp32 K split (gemm_f32.hip): one fixed size -- F32K_TILES counters (zero between launches) + partials of at most F32K_PARTS (tile, slice)
+// pairs; the planner (gemm_plan.h) drops the split beyond them
+static SlabPool g_f32k_pool{1, true};
+static constexpr size_t F32K_SLAB = (size_t)F32K_TILES * 4 + (size_t)F32K_PARTS * 16 * 256 * 4;
+int gemm_tail_reserve(size_t bytes) { return g_tail_pool.reserve(bytes); }
+size_t gemm_tail_reserved() { return g_tail_pool.reserved(); }
+float* gemm_tail_slab(hipStream_t s) { return reinterpret_cast<float*>(g_tail_pool.slab(s)); }
+int gemm_f32_ksplit_reserve() { return g_f32k_pool.reserve(F32K_SLAB); }
+bool gemm_f32_ksplit_reserved() { return g_f32k_pool.reserved() != 0; }
+char* gemm_f32_ksplit_slab(hipStream_t s) { return g_f32k_pool.slab(s); }
 
 // Every tuning-build switch that steers the dispatch (include/dinodet_tuning.h).  The release build reads no environment: DOD_TUNE_ENV is a null
 // constant there and this folds to GemmTune's defaults.  The tile overrides are read per call (tools/ flip them between launches), the rest once.

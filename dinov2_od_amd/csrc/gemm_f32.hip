@@ -19,7 +19,6 @@
 #include "gemm_plan.h"
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 
 #define FBM 64
 #define FBN 64
@@ -210,49 +209,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
   }
 }
 
-// ---- scratch of the K split: F32K_SLOTS slabs per device, one per launching stream (least recently used first, as gemm_pp.hip's tail scratch:
-// a forward may run as concurrent micro-batches on separate streams); a slab = F32K_TILES counters (zero between launches) + partials of at most
-// F32K_PARTS (tile, slice) pairs.  Allocated by gemm_f32_ksplit_reserve() outside any stream capture, never freed (captured graphs keep the addresses).
-#define F32K_SLOTS 4      // (F32K_TILES, F32K_PARTS: gemm_plan.h -- the planner drops the split beyond them)
-static std::mutex g_f32k_mu;
-static char* g_f32k[16] = {};
-static hipStream_t g_f32k_owner[16][F32K_SLOTS] = {};
-static unsigned long long g_f32k_used[16][F32K_SLOTS] = {};
-static unsigned long long g_f32k_clock = 0;
-static constexpr size_t F32K_SLAB = (size_t)F32K_TILES * 4 + (size_t)F32K_PARTS * 16 * 256 * 4;
-int gemm_f32_ksplit_reserve() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 3;
-  std::lock_guard<std::mutex> lk(g_f32k_mu);
-  if (g_f32k[dev]) return 0;
-  char* blk = nullptr;
-  if (hipMalloc((void**)&blk, F32K_SLAB * F32K_SLOTS) != hipSuccess) return 3;
-  if (hipMemset(blk, 0, F32K_SLAB * F32K_SLOTS) != hipSuccess) { (void)hipFree(blk); return 3; }
-  g_f32k[dev] = blk;
-  return 0;
-}
-static char* f32k_slab(int dev, hipStream_t s) {
-  std::lock_guard<std::mutex> lk(g_f32k_mu);
-  if (dev < 0 || dev >= 16 || !g_f32k[dev]) return nullptr;
-  int pick = -1;
-  for (int i = 0; i < F32K_SLOTS; ++i)
-    if (g_f32k_used[dev][i] && g_f32k_owner[dev][i] == s) { pick = i; break; }
-  if (pick < 0) {
-    pick = 0;
-    for (int i = 1; i < F32K_SLOTS; ++i)
-      if (g_f32k_used[dev][i] < g_f32k_used[dev][pick]) pick = i;
-    g_f32k_owner[dev][pick] = s;
-  }
-  g_f32k_used[dev][pick] = ++g_f32k_clock;
-  return g_f32k[dev] + (size_t)pick * F32K_SLAB;
-}
-bool gemm_f32_ksplit_reserved() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
-  std::lock_guard<std::mutex> lk(g_f32k_mu);
-  return g_f32k[dev] != nullptr;
-}
-
 int launch_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int N, int K,
                     const GemmEpi& e, hipStream_t s, bool allow_ksplit) {
   if (M <= 0 || N <= 0 || K <= 0) return 1;
@@ -265,9 +221,7 @@ int run_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int N,
   const int tiles = ((M + FBM - 1) / FBM) * ((N + FBN - 1) / FBN);
   float* part = nullptr; unsigned* counters = nullptr;
   if (S > 1) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    char* slab = f32k_slab(dev, s);
+    char* slab = gemm_f32_ksplit_slab(s);
     if (!slab || tiles > F32K_TILES || (long)tiles * S > F32K_PARTS) return 2;
     counters = reinterpret_cast<unsigned*>(slab); part = reinterpret_cast<float*>(slab + (size_t)F32K_TILES * 4);
   }

@@ -19,7 +19,6 @@
 //   * WAR: the LDS reads of a phase are retired (lgkmcnt(0)) BEFORE the barrier that ends the LOAD segment; a plane is
 //     re-staged only after the barrier following group 1's last read of it.  RAW: a plane is read one barrier (at least)
 //     after the barrier that follows every wave's vmcnt wait for it.
-#include <mutex>
 #include "dod_common.h"
 #include "gemm_epi.h"
 #include <cstdlib>
@@ -565,59 +564,6 @@ __global__ __launch_bounds__(512) void gemm_ksplit_reduce_kernel(const float* __
   const ColParams cp = load_col_params<PPN, LN>(e, n0, N, tid);
   if (drain8_ok(e, N)) drain_tile_bf16x8<KSR_ROWS, PPN, 512, LN>(smem, PITCH, e, M, N, n0, tid, rowmap);
   else drain_tile<KSR_ROWS, PPN, 512, LN>(smem, PITCH, e, cp, M, N, n0, tid, rowmap);
-}
-
-// scratch: TAIL_SLOTS slabs per device, handed to launching streams least-recently-used first (a forward may run as concurrent
-// micro-batches on separate streams -- engine.py: two -- and a process creates many short-lived streams over time: warm-up, capture,
-// side streams).  Streams that launch concurrently must not share a slab: up to TAIL_SLOTS of them never do.
-#define TAIL_SLOTS 4
-#define TAIL_GENS 4                            // the scratch only ever GROWS by adding a block: captured hipGraphs keep slab addresses
-static std::mutex g_tail_mu;                   // autograd / DataLoader threads may launch GEMMs beside the main thread
-static float* g_tail_scratch[16][TAIL_GENS] = {};
-static int g_tail_gen[16] = {};                // blocks allocated so far (the newest one is handed out)
-static size_t g_tail_bytes[16] = {};           // bytes per slab of the newest block
-static hipStream_t g_tail_owner[16][TAIL_SLOTS] = {};
-static unsigned long long g_tail_used[16][TAIL_SLOTS] = {};
-static unsigned long long g_tail_clock = 0;
-int gemm_tail_reserve(size_t bytes) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 3;
-  std::lock_guard<std::mutex> lk(g_tail_mu);
-  if (g_tail_bytes[dev] >= bytes) return 0;
-  if (g_tail_gen[dev] >= TAIL_GENS) return 3;  // never free a block a captured graph may still reference: refuse instead
-  float* blk = nullptr;
-  if (hipMalloc((void**)&blk, bytes * TAIL_SLOTS) != hipSuccess) return 3;
-  g_tail_scratch[dev][g_tail_gen[dev]++] = blk;
-  for (int i = 0; i < TAIL_SLOTS; ++i) { g_tail_used[dev][i] = 0; g_tail_owner[dev][i] = nullptr; }
-  g_tail_bytes[dev] = bytes;
-  return 0;
-}
-static float* tail_slab(int dev, hipStream_t s) {
-  std::lock_guard<std::mutex> lk(g_tail_mu);
-  if (!g_tail_gen[dev]) return nullptr;
-  int pick = -1;
-  for (int i = 0; i < TAIL_SLOTS; ++i)
-    if (g_tail_used[dev][i] && g_tail_owner[dev][i] == s) { pick = i; break; }
-  if (pick < 0) {
-    pick = 0;
-    for (int i = 1; i < TAIL_SLOTS; ++i)
-      if (g_tail_used[dev][i] < g_tail_used[dev][pick]) pick = i;
-    g_tail_owner[dev][pick] = s;
-  }
-  g_tail_used[dev][pick] = ++g_tail_clock;
-  return (float*)((char*)g_tail_scratch[dev][g_tail_gen[dev] - 1] + (size_t)pick * g_tail_bytes[dev]);
-}
-
-size_t gemm_tail_reserved() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
-  std::lock_guard<std::mutex> lk(g_tail_mu);
-  return g_tail_bytes[dev];
-}
-float* gemm_tail_slab(hipStream_t s) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  return tail_slab(dev, s);
 }
 
 // FORM_KSPLIT_REDUCE: sums the S partial slabs of rows m_base .. m_base + R - 1 in slice order and runs the call's epilogue `e` on them

@@ -217,7 +217,7 @@ __global__ __launch_bounds__(JC_THREADS) void jpeg_color_kernel(const uint8_t* _
 // ------------------------------------------------------------------------------------------------------------ entry points
 extern "C" int dod_jpeg_entropy_host(const uint8_t* bytes, int64_t nbytes, const int64_t* images, int first, int count, const int32_t* htabs,
                                      int n_htabs, int16_t* coef, int64_t coef_blocks, int32_t* status) {
-  if (!bytes || !images || !htabs || !coef || !status || nbytes < 0 || first < 0 || count < 0 || n_htabs < 1 || coef_blocks < 0) return DOD_ERR_INVALID;
+  if (!bytes || !images || !htabs || !coef || !status || nbytes < 0 || first < 0 || count < 0 || n_htabs < 1 || coef_blocks < 0) return dod_fail(DOD_ERR_INVALID, "dod_jpeg_entropy_host: null argument, or a negative nbytes / first / count / coef_blocks, or n_htabs < 1");
   for (int b = first; b < first + count; ++b) {
     const int64_t* ji = images + (size_t)b * DOD_JI_STRIDE;
     const int ncomp = (int)ji[DOD_JI_NCOMP];
@@ -241,29 +241,29 @@ extern "C" int dod_jpeg_entropy_host(const uint8_t* bytes, int64_t nbytes, const
 extern "C" int dod_jpeg_entropy_device(const uint8_t* bytes, int64_t nbytes, const int64_t* images, int n_images, const int64_t* intervals,
                                        int n_intervals, const int32_t* htabs, int n_htabs, int16_t* coef, int64_t coef_blocks,
                                        int32_t* status, void* stream) {
-  if (!bytes || !images || !intervals || !htabs || !coef || !status) return DOD_ERR_INVALID;
-  if (nbytes < 0 || n_images < 1 || n_intervals < 1 || n_htabs < 1 || coef_blocks < 1) return DOD_ERR_INVALID;
+  if (!bytes || !images || !intervals || !htabs || !coef || !status) return dod_fail(DOD_ERR_INVALID, "dod_jpeg_entropy_device: null argument");
+  if (nbytes < 0 || n_images < 1 || n_intervals < 1 || n_htabs < 1 || coef_blocks < 1) return dod_fail(DOD_ERR_INVALID, "dod_jpeg_entropy_device: negative nbytes, or n_images / n_intervals / n_htabs / coef_blocks below 1");
   hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((n_intervals + 63) / 64), dim3(64), 0, (hipStream_t)stream, bytes, images, intervals,
                      n_intervals, n_images, htabs, n_htabs, coef, coef_blocks, nbytes, status);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_jpeg_entropy_device");
 }
 
 extern "C" int dod_jpeg_idct(const int16_t* coef, int64_t n_blocks, const int64_t* comps, int n_comps, const uint16_t* qtabs, int n_qtabs,
                              uint8_t* planes, void* stream) {
-  if (!coef || !comps || !qtabs || !planes || n_blocks < 1 || n_comps < 1 || n_qtabs < 1) return DOD_ERR_INVALID;
-  if ((reinterpret_cast<uintptr_t>(coef) & 15) || (reinterpret_cast<uintptr_t>(qtabs) & 15) || (reinterpret_cast<uintptr_t>(planes) & 7)) return DOD_ERR_INVALID;
+  if (!coef || !comps || !qtabs || !planes || n_blocks < 1 || n_comps < 1 || n_qtabs < 1) return dod_fail(DOD_ERR_INVALID, "dod_jpeg_idct: null argument, or n_blocks / n_comps / n_qtabs below 1");
+  if ((reinterpret_cast<uintptr_t>(coef) & 15) || (reinterpret_cast<uintptr_t>(qtabs) & 15) || (reinterpret_cast<uintptr_t>(planes) & 7)) return dod_fail(DOD_ERR_INVALID, "dod_jpeg_idct: coef or qtabs not 16-byte aligned, or planes not 8-byte aligned");
   const int64_t groups = (n_blocks + JI_BLOCKS - 1) / JI_BLOCKS;
-  if (groups > 0x7fffffff) return DOD_ERR_INVALID;
+  if (groups > 0x7fffffff) return dod_fail(DOD_ERR_INVALID, "dod_jpeg_idct: n_blocks = %lld beyond the grid range", (long long)n_blocks);
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)groups), dim3(JI_BLOCKS * 8), 0, (hipStream_t)stream, coef, n_blocks, comps, n_comps,
                      qtabs, n_qtabs, planes);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_jpeg_idct");
 }
 
 extern "C" int dod_jpeg_color(const uint8_t* planes, const int64_t* images, int n_images, int64_t n_items, uint8_t* out, void* stream) {
-  if (!planes || !images || !out || n_images < 1 || n_items < 1) return DOD_ERR_INVALID;
-  if (reinterpret_cast<uintptr_t>(planes) & 3) return DOD_ERR_INVALID;
+  if (!planes || !images || !out || n_images < 1 || n_items < 1) return dod_fail(DOD_ERR_INVALID, "dod_jpeg_color: null argument, or n_images / n_items below 1");
+  if (reinterpret_cast<uintptr_t>(planes) & 3) return dod_fail(DOD_ERR_INVALID, "dod_jpeg_color: planes not 4-byte aligned");
   const int64_t groups = (n_items + JC_THREADS - 1) / JC_THREADS;
-  if (groups > 0x7fffffff) return DOD_ERR_INVALID;
+  if (groups > 0x7fffffff) return dod_fail(DOD_ERR_INVALID, "dod_jpeg_color: n_items = %lld beyond the grid range", (long long)n_items);
   hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)groups), dim3(JC_THREADS), 0, (hipStream_t)stream, planes, images, n_images, n_items, out);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_jpeg_color");
 }

@@ -64,11 +64,11 @@ __global__ __launch_bounds__(256) void match_cost_kernel(const float* __restrict
 extern "C" int dod_match_cost(const float* det, int B, int Q, int C, const int64_t* labels, const float* gt_boxes,
                               const int32_t* gt_offsets, int G, float w_class, float w_bbox, float w_giou, float alpha,
                               float gamma, int rows_from, float* cost, void* stream) {
-  if (!det || B <= 0 || Q <= 0 || C <= 0 || G < 0 || !gt_offsets || rows_from >= B) return DOD_ERR_INVALID;
+  if (!det || B <= 0 || Q <= 0 || C <= 0 || G < 0 || !gt_offsets || rows_from >= B) return dod_fail(DOD_ERR_INVALID, "dod_match_cost: null det / gt_offsets, non-positive B / Q / C, negative G, or rows_from >= B");
   if (G == 0) return DOD_OK;
-  if (!labels || !gt_boxes || !cost) return DOD_ERR_INVALID;
+  if (!labels || !gt_boxes || !cost) return dod_fail(DOD_ERR_INVALID, "dod_match_cost: null labels / gt_boxes / cost with G > 0");
   const long total = (long)G * Q;
   hipLaunchKernelGGL(match_cost_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, det, B, Q, C,
                      (const long long*)labels, gt_boxes, gt_offsets, G, w_class, w_bbox, w_giou, alpha, gamma, rows_from, cost);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_match_cost");
 }

@@ -283,28 +283,19 @@ __global__ __launch_bounds__(kThreads) void optim_scale_kernel(const NormArgs a,
 __global__ void optim_store_kernel(float* dst, float value) { *dst = value; }
 
 // ------------------------------------------------------------------------------------------------ host
-thread_local std::string g_oerr;
 std::atomic<long> g_launches{0};
-
-int ofail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int ofail(int code, const char* fmt, ...) {
-  char buf[256];
-  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-  g_oerr = buf;
-  return code;
-}
 
 inline i64 chunks_of(i64 n, i64 span) { return (n + span - 1) / span; }
 
 // arguments every entry point checks before it touches a device; *total = elements, *nz = tensors with n > 0
 int check_list(const char* who, const dod_optim_tensor* t, int nt, bool adam, i64* total) {
-  if (nt < 0) return ofail(DOD_ERR_INVALID, "%s: n_tensors = %d is negative", who, nt);
-  if (nt > 0 && !t) return ofail(DOD_ERR_INVALID, "%s: null tensor list", who);
+  if (nt < 0) return dod_fail(DOD_ERR_INVALID, "%s: n_tensors = %d is negative", who, nt);
+  if (nt > 0 && !t) return dod_fail(DOD_ERR_INVALID, "%s: null tensor list", who);
   i64 sum = 0;
   for (int i = 0; i < nt; ++i) {
-    if (t[i].n < 0) return ofail(DOD_ERR_INVALID, "%s: tensor %d has n = %lld", who, i, (long long)t[i].n);
-    if (t[i].n > (i64)kChunk * kMaxGrid) return ofail(DOD_ERR_INVALID, "%s: tensor %d has more than 2^42 elements", who, i);
-    if (t[i].n > 0 && (!t[i].g || (adam && (!t[i].p || !t[i].m || !t[i].v)))) return ofail(DOD_ERR_INVALID, "%s: tensor %d has a null pointer", who, i);
+    if (t[i].n < 0) return dod_fail(DOD_ERR_INVALID, "%s: tensor %d has n = %lld", who, i, (long long)t[i].n);
+    if (t[i].n > (i64)kChunk * kMaxGrid) return dod_fail(DOD_ERR_INVALID, "%s: tensor %d has more than 2^42 elements", who, i);
+    if (t[i].n > 0 && (!t[i].g || (adam && (!t[i].p || !t[i].m || !t[i].v)))) return dod_fail(DOD_ERR_INVALID, "%s: tensor %d has a null pointer", who, i);
     sum += t[i].n;
   }
   *total = sum;
@@ -314,7 +305,7 @@ int check_list(const char* who, const dod_optim_tensor* t, int nt, bool adam, i6
 int launched(const char* who) {
   ++g_launches;
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? DOD_OK : ofail(DOD_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+  return e == hipSuccess ? DOD_OK : dod_fail(DOD_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
 }
 
 // kernel 1 over the whole list: partial[0 .. *np)
@@ -354,17 +345,17 @@ int run_step(const char* who, const dod_optim_tensor* t, float* const* ema, cons
   i64 total = 0;
   if (int rc = check_list(who, t, n_tensors, true, &total)) return rc;
   const bool clip = o.max_norm > 0.f, skip = o.skip_nonfinite != 0, ready = o.norm_ready != 0, norm = clip || (skip && !ready);
-  if (ready && (!skip || clip)) return ofail(DOD_ERR_INVALID, "%s: norm_ready goes with skip_nonfinite and max_norm <= 0 only", who);
-  if ((norm || skip) && !o.total_norm_dev) return ofail(DOD_ERR_INVALID, "%s: null total_norm_dev with max_norm > 0 or skip_nonfinite", who);
+  if (ready && (!skip || clip)) return dod_fail(DOD_ERR_INVALID, "%s: norm_ready goes with skip_nonfinite and max_norm <= 0 only", who);
+  if ((norm || skip) && !o.total_norm_dev) return dod_fail(DOD_ERR_INVALID, "%s: null total_norm_dev with max_norm > 0 or skip_nonfinite", who);
   if (!(o.beta1 >= 0.0 && o.beta1 < 1.0 && o.beta2 >= 0.0 && o.beta2 < 1.0) || !(o.eps >= 0.f) || !(o.weight_decay >= 0.0) || !(o.max_norm == o.max_norm))
-    return ofail(DOD_ERR_INVALID, "%s: betas outside [0, 1), negative eps / weight_decay or a NaN max_norm", who);
-  if (ema && !(o.ema_w >= 0.0 && o.ema_w <= 1.0)) return ofail(DOD_ERR_INVALID, "%s: ema_w = %g outside [0, 1]", who, o.ema_w);
+    return dod_fail(DOD_ERR_INVALID, "%s: betas outside [0, 1), negative eps / weight_decay or a NaN max_norm", who);
+  if (ema && !(o.ema_w >= 0.0 && o.ema_w <= 1.0)) return dod_fail(DOD_ERR_INVALID, "%s: ema_w = %g outside [0, 1]", who, o.ema_w);
   if (decay)
     for (int i = 0; i < n_tensors; ++i)
-      if (!(decay[i] == decay[i])) return ofail(DOD_ERR_INVALID, "%s: tensor %d has a NaN decay factor", who, i);
+      if (!(decay[i] == decay[i])) return dod_fail(DOD_ERR_INVALID, "%s: tensor %d has a NaN decay factor", who, i);
   if (total == 0) return norm ? store_norm0(who, o.total_norm_dev, s) : DOD_OK;
   if (norm && (!ws || ws_bytes < ws_need(n_tensors, total)))
-    return ofail(DOD_ERR_INVALID, "%s: workspace of %zu bytes, %zu needed", who, ws ? ws_bytes : (size_t)0, ws_need(n_tensors, total));
+    return dod_fail(DOD_ERR_INVALID, "%s: workspace of %zu bytes, %zu needed", who, ws ? ws_bytes : (size_t)0, ws_need(n_tensors, total));
   double* partial = norm ? reinterpret_cast<double*>(dod::align_ws(ws)) : nullptr;
   int np = -1;                                             // -1: no norm launch, the adam kernel skips the reduction
   if (norm) if (int rc = run_sumsq(who, t, n_tensors, total, partial, &np, s)) return rc;
@@ -414,8 +405,6 @@ long optim_constant(int which) { return which == 0 ? kChunk : which == 1 ? kAdam
 
 extern "C" {
 
-const char* dod_optim_last_error(void) { return g_oerr.c_str(); }
-
 size_t dod_optim_workspace_bytes(int n_tensors, int64_t total_elems) {
   if (n_tensors < 0 || total_elems < 0) return 0;
   return ws_need(n_tensors, total_elems);
@@ -426,11 +415,11 @@ int dod_optim_clip_grad_norm(const dod_optim_tensor* t, int n_tensors, float max
   static const char* who = "dod_optim_clip_grad_norm";
   i64 total = 0;
   if (int rc = check_list(who, t, n_tensors, false, &total)) return rc;
-  if (!total_norm_dev) return ofail(DOD_ERR_INVALID, "%s: null total_norm_dev", who);
-  if (!(max_norm == max_norm)) return ofail(DOD_ERR_INVALID, "%s: max_norm is NaN", who);
+  if (!total_norm_dev) return dod_fail(DOD_ERR_INVALID, "%s: null total_norm_dev", who);
+  if (!(max_norm == max_norm)) return dod_fail(DOD_ERR_INVALID, "%s: max_norm is NaN", who);
   hipStream_t s = (hipStream_t)stream;
   if (total == 0) return store_norm0(who, total_norm_dev, s);
-  if (!ws || ws_bytes < ws_need(n_tensors, total)) return ofail(DOD_ERR_INVALID, "%s: workspace of %zu bytes, %zu needed", who, ws ? ws_bytes : (size_t)0, ws_need(n_tensors, total));
+  if (!ws || ws_bytes < ws_need(n_tensors, total)) return dod_fail(DOD_ERR_INVALID, "%s: workspace of %zu bytes, %zu needed", who, ws ? ws_bytes : (size_t)0, ws_need(n_tensors, total));
   double* partial = reinterpret_cast<double*>(dod::align_ws(ws));
   int np = 0;
   if (int rc = run_sumsq(who, t, n_tensors, total, partial, &np, s)) return rc;
@@ -463,23 +452,23 @@ int dod_optim_adam_step(const dod_optim_tensor* t, int n_tensors, double beta1, 
 int dod_optim_step(const dod_optim_tensor* t, float* const* ema, const double* decay, int n_tensors, const dod_optim_options* o, void* ws,
                    size_t ws_bytes, void* stream) {
   static const char* who = "dod_optim_step";
-  if (!o) return ofail(DOD_ERR_INVALID, "%s: null options", who);
+  if (!o) return dod_fail(DOD_ERR_INVALID, "%s: null options", who);
   if (ema && n_tensors > 0)
     for (int i = 0; i < n_tensors; ++i)
       if (ema[i] && t && t[i].n > 0 && (ema[i] == t[i].p || ema[i] == t[i].m || ema[i] == t[i].v))
-        return ofail(DOD_ERR_INVALID, "%s: the average of tensor %d aliases its parameter or state", who, i);
+        return dod_fail(DOD_ERR_INVALID, "%s: the average of tensor %d aliases its parameter or state", who, i);
   return run_step(who, t, ema, decay, n_tensors, *o, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int dod_optim_ema_update(const dod_optim_ema_tensor* t, int n_tensors, double w, void* stream) {
   static const char* who = "dod_optim_ema_update";
-  if (n_tensors < 0) return ofail(DOD_ERR_INVALID, "%s: n_tensors = %d is negative", who, n_tensors);
-  if (n_tensors > 0 && !t) return ofail(DOD_ERR_INVALID, "%s: null tensor list", who);
-  if (!(w >= 0.0 && w <= 1.0)) return ofail(DOD_ERR_INVALID, "%s: w = %g outside [0, 1]", who, w);
+  if (n_tensors < 0) return dod_fail(DOD_ERR_INVALID, "%s: n_tensors = %d is negative", who, n_tensors);
+  if (n_tensors > 0 && !t) return dod_fail(DOD_ERR_INVALID, "%s: null tensor list", who);
+  if (!(w >= 0.0 && w <= 1.0)) return dod_fail(DOD_ERR_INVALID, "%s: w = %g outside [0, 1]", who, w);
   for (int i = 0; i < n_tensors; ++i) {
-    if (t[i].n < 0) return ofail(DOD_ERR_INVALID, "%s: tensor %d has n = %lld", who, i, (long long)t[i].n);
-    if (t[i].n > (i64)kChunk * kMaxGrid) return ofail(DOD_ERR_INVALID, "%s: tensor %d has more than 2^42 elements", who, i);
-    if (t[i].n > 0 && (!t[i].e || !t[i].p)) return ofail(DOD_ERR_INVALID, "%s: tensor %d has a null pointer", who, i);
+    if (t[i].n < 0) return dod_fail(DOD_ERR_INVALID, "%s: tensor %d has n = %lld", who, i, (long long)t[i].n);
+    if (t[i].n > (i64)kChunk * kMaxGrid) return dod_fail(DOD_ERR_INVALID, "%s: tensor %d has more than 2^42 elements", who, i);
+    if (t[i].n > 0 && (!t[i].e || !t[i].p)) return dod_fail(DOD_ERR_INVALID, "%s: tensor %d has a null pointer", who, i);
   }
   hipStream_t s = (hipStream_t)stream;
   int i = 0;

@@ -92,9 +92,9 @@ extern "C" size_t dod_postprocess_workspace_bytes(int B, int Q, int C) {
 extern "C" int dod_postprocess(const float* det, int B, int Q, int C, const int64_t* image_ids, float threshold,
                                dod_detection* out, int64_t max_out, int64_t* count, void* workspace,
                                size_t workspace_bytes, void* stream) {
-  if (!det || !count || B <= 0 || Q <= 0 || C <= 1 || max_out < 0 || (max_out > 0 && !out)) return DOD_ERR_INVALID;
-  if ((long long)B * (C - 1) > (1 << 24)) return DOD_ERR_INVALID;
-  if (!workspace || workspace_bytes < dod_postprocess_workspace_bytes(B, Q, C)) return DOD_ERR_INVALID;
+  if (!det || !count || B <= 0 || Q <= 0 || C <= 1 || max_out < 0 || (max_out > 0 && !out)) return dod_fail(DOD_ERR_INVALID, "dod_postprocess: null det / count, B=%d Q=%d C=%d max_out=%lld outside the limits, or max_out > 0 without out", B, Q, C, (long long)max_out);
+  if ((long long)B * (C - 1) > (1 << 24)) return dod_fail(DOD_ERR_INVALID, "dod_postprocess: B * (C - 1) above 2^24");
+  if (!workspace || workspace_bytes < dod_postprocess_workspace_bytes(B, Q, C)) return dod_fail(DOD_ERR_INVALID, "dod_postprocess: null or short workspace");
   hipStream_t s = (hipStream_t)stream;
   const int runs = B * (C - 1);
   unsigned* counts = (unsigned*)workspace;
@@ -104,5 +104,5 @@ extern "C" int dod_postprocess(const float* det, int B, int Q, int C, const int6
   hipLaunchKernelGGL(pp_scan_kernel, dim3(1), dim3(1024), 0, s, counts, runs, offsets, (long long*)count);
   hipLaunchKernelGGL(pp_emit_kernel, dim3(blocks), dim3(256), 0, s, det, B, Q, C, threshold,
                      (const long long*)image_ids, offsets, out, (long long)max_out);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_postprocess");
 }

@@ -264,10 +264,10 @@ __global__ __launch_bounds__(G::COLS) void pp_horizontal_kernel(const unsigned c
   pp_horizontal_crop<G::COLS>(src + src_offs[q.src], q, jittered, tmp + tmp_offs[i], kk[threadIdx.x]);
 }
 
-// the buffers every entry takes: sources, temporary, one of the two outputs
+// the buffers every entry takes: sources, temporary, one of the two outputs; who: the entry point's name, for its messages
 struct pp_io_t {
   const uint8_t* src; const int64_t* src_offs; const int32_t* hs; const int32_t* ws; uint8_t* tmp; const int64_t* tmp_offs;
-  float* out; uint8_t* out_u8; hipStream_t s;
+  float* out; uint8_t* out_u8; hipStream_t s; const char* who;
 };
 
 // what every entry checks before it launches anything: its pointers, n items within the grid limit, and the window taps of the
@@ -289,7 +289,7 @@ static int pp_chain(const pp_io_t& io, const G& g, int n, int max_ch, int max_cw
     if (jitter) {
       const int sum_blocks = (max_ch + PP_SUM_ROWS - 1) / PP_SUM_ROWS;
       if (lsum) {
-        if (hipMemsetAsync(lsum, 0, (size_t)n * sizeof(uint64_t), io.s) != hipSuccess) return DOD_ERR_HIP;
+        if (hipMemsetAsync(lsum, 0, (size_t)n * sizeof(uint64_t), io.s) != hipSuccess) return dod_fail(DOD_ERR_HIP, "%s: hipMemsetAsync failed", io.who);
         hipLaunchKernelGGL(pp_luma_sum_kernel<G>, dim3(sum_blocks, n), dim3(256), 0, io.s, io.src, so, g, jitter, (unsigned long long*)lsum);
       }
       hipLaunchKernelGGL(pp_jitter_kernel<G>, dim3((max_cw + 255) / 256, sum_blocks, n), dim3(256), 0, io.s, io.src, so, g, jitter, ls, io.tmp, to);
@@ -353,11 +353,11 @@ template <int HS>
 static int pp_vertical(const pp_io_t& io, const int32_t* hs, int B, int out_h, int out_w) {
   hipLaunchKernelGGL(pp_vertical_kernel<HS>, dim3(out_h, B), dim3(256), 0, io.s, io.tmp, (const long long*)io.tmp_offs, hs, out_h, out_w, io.out,
                      io.out_u8);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched(io.who);
 }
 
 static int preprocess_impl(const pp_io_t& io, int B, int max_h, int max_w, int out_h, int out_w) {
-  if (!pp_args_ok(io, B, max_h, max_w, out_h, out_w)) return DOD_ERR_INVALID;
+  if (!pp_args_ok(io, B, max_h, max_w, out_h, out_w)) return dod_fail(DOD_ERR_INVALID, "%s: null argument, B or a size outside the limits, or more than 32 taps", io.who);
   const pp_whole_t g = {io.hs, io.ws, out_w};
   const int rc = pp_chain(io, g, B, max_h, max_w, out_w, nullptr, nullptr);
   return rc ? rc : pp_vertical<1>(io, io.hs, B, out_h, out_w);
@@ -366,17 +366,18 @@ static int preprocess_impl(const pp_io_t& io, int B, int max_h, int max_w, int o
 extern "C" int dod_preprocess(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
                               int max_h, int max_w, int out_h, int out_w, uint8_t* tmp, const int64_t* tmp_offs, float* out,
                               void* stream) {
-  return preprocess_impl({src, src_offs, heights, widths, tmp, tmp_offs, out, nullptr, (hipStream_t)stream}, B, max_h, max_w, out_h, out_w);
+  return preprocess_impl({src, src_offs, heights, widths, tmp, tmp_offs, out, nullptr, (hipStream_t)stream, "dod_preprocess"}, B, max_h, max_w, out_h, out_w);
 }
 extern "C" int dod_preprocess_u8(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
                                  int max_h, int max_w, int out_h, int out_w, uint8_t* tmp, const int64_t* tmp_offs, uint8_t* out_hwc,
                                  void* stream) {
-  return preprocess_impl({src, src_offs, heights, widths, tmp, tmp_offs, nullptr, out_hwc, (hipStream_t)stream}, B, max_h, max_w, out_h, out_w);
+  return preprocess_impl({src, src_offs, heights, widths, tmp, tmp_offs, nullptr, out_hwc, (hipStream_t)stream, "dod_preprocess_u8"}, B, max_h, max_w, out_h, out_w);
 }
 
 static int preprocess_aug_impl(const pp_io_t& io, int B, const int32_t* crops, const uint8_t* flips, const float* jitter, uint64_t* lsum,
                                int max_crop_h, int max_crop_w, int out_h, int out_w) {
-  if (!crops || !flips || !pp_args_ok(io, B, max_crop_h, max_crop_w, out_h, out_w)) return DOD_ERR_INVALID;
+  if (!crops || !flips || !pp_args_ok(io, B, max_crop_h, max_crop_w, out_h, out_w))
+    return dod_fail(DOD_ERR_INVALID, "%s: null argument, B or a size outside the limits, or more than 32 taps", io.who);
   const pp_crops_t g = {io.hs, io.ws, crops, flips, out_w};
   const int rc = pp_chain(io, g, B, max_crop_h, max_crop_w, out_w, jitter, lsum);
   return rc ? rc : pp_vertical<4>(io, crops + 3, B, out_h, out_w);
@@ -385,14 +386,14 @@ static int preprocess_aug_impl(const pp_io_t& io, int B, const int32_t* crops, c
 extern "C" int dod_preprocess_aug(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
                                   const int32_t* crops, const uint8_t* flips, const float* jitter, uint64_t* lsum, int max_crop_h,
                                   int max_crop_w, int out_h, int out_w, uint8_t* tmp, const int64_t* tmp_offs, float* out, void* stream) {
-  return preprocess_aug_impl({src, src_offs, heights, widths, tmp, tmp_offs, out, nullptr, (hipStream_t)stream}, B, crops, flips, jitter, lsum,
+  return preprocess_aug_impl({src, src_offs, heights, widths, tmp, tmp_offs, out, nullptr, (hipStream_t)stream, "dod_preprocess_aug"}, B, crops, flips, jitter, lsum,
                              max_crop_h, max_crop_w, out_h, out_w);
 }
 extern "C" int dod_preprocess_aug_u8(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
                                      const int32_t* crops, const uint8_t* flips, const float* jitter, uint64_t* lsum, int max_crop_h,
                                      int max_crop_w, int out_h, int out_w, uint8_t* tmp, const int64_t* tmp_offs, uint8_t* out_hwc,
                                      void* stream) {
-  return preprocess_aug_impl({src, src_offs, heights, widths, tmp, tmp_offs, nullptr, out_hwc, (hipStream_t)stream}, B, crops, flips, jitter, lsum,
+  return preprocess_aug_impl({src, src_offs, heights, widths, tmp, tmp_offs, nullptr, out_hwc, (hipStream_t)stream, "dod_preprocess_aug_u8"}, B, crops, flips, jitter, lsum,
                              max_crop_h, max_crop_w, out_h, out_w);
 }
 
@@ -473,26 +474,26 @@ static int preprocess_compose_impl(const pp_io_t& io, int S, const int32_t* piec
   // checks each piece)
   if (!pieces || !piece_offsets || !fills || S <= 0 || N <= 0 || N > 65535 || max_dw <= 0 || max_dw > out_w ||
       !pp_args_ok(io, P, max_crop_h, max_crop_w, out_h, out_w))
-    return DOD_ERR_INVALID;
+    return dod_fail(DOD_ERR_INVALID, "%s: null argument, S / N / P / max_dw or a size outside the limits, or more than 32 taps", io.who);
   const pp_pieces_t g = {io.hs, io.ws, pieces, {S, P, out_h, out_w, max_crop_h, max_crop_w, max_dw}};
   const int rc = pp_chain(io, g, P, max_crop_h, max_crop_w, max_dw, jitter, lsum);
   if (rc) return rc;
   hipLaunchKernelGGL(pp_compose_kernel, dim3((out_h + PP_CROWS - 1) / PP_CROWS, N), dim3(64 * PP_CROWS), 0, io.s, io.tmp, (const long long*)io.tmp_offs,
                      piece_offsets, g, fills, fill_per_canvas, io.out, io.out_u8);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched(io.who);
 }
 
 extern "C" int dod_preprocess_compose(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int S,
                                       const int32_t* pieces, const int32_t* piece_offsets, int N, int P, const float* jitter, uint64_t* lsum,
                                       const uint8_t* fills, int fill_per_canvas, int max_crop_h, int max_crop_w, int max_dw, int out_h,
                                       int out_w, uint8_t* tmp, const int64_t* tmp_offs, float* out, void* stream) {
-  return preprocess_compose_impl({src, src_offs, heights, widths, tmp, tmp_offs, out, nullptr, (hipStream_t)stream}, S, pieces, piece_offsets, N, P,
+  return preprocess_compose_impl({src, src_offs, heights, widths, tmp, tmp_offs, out, nullptr, (hipStream_t)stream, "dod_preprocess_compose"}, S, pieces, piece_offsets, N, P,
                                  jitter, lsum, fills, fill_per_canvas, max_crop_h, max_crop_w, max_dw, out_h, out_w);
 }
 extern "C" int dod_preprocess_compose_u8(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int S,
                                          const int32_t* pieces, const int32_t* piece_offsets, int N, int P, const float* jitter, uint64_t* lsum,
                                          const uint8_t* fills, int fill_per_canvas, int max_crop_h, int max_crop_w, int max_dw, int out_h,
                                          int out_w, uint8_t* tmp, const int64_t* tmp_offs, uint8_t* out_hwc, void* stream) {
-  return preprocess_compose_impl({src, src_offs, heights, widths, tmp, tmp_offs, nullptr, out_hwc, (hipStream_t)stream}, S, pieces, piece_offsets, N,
+  return preprocess_compose_impl({src, src_offs, heights, widths, tmp, tmp_offs, nullptr, out_hwc, (hipStream_t)stream, "dod_preprocess_compose_u8"}, S, pieces, piece_offsets, N,
                                  P, jitter, lsum, fills, fill_per_canvas, max_crop_h, max_crop_w, max_dw, out_h, out_w);
 }

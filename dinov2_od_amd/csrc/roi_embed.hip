@@ -144,14 +144,14 @@ __global__ __launch_bounds__(kRoiThreads) void roi_embed_kernel(RoiArgs a) {
 
 extern "C" int dod_roi_embed(const float* features, int B, int N, int D, int first_token, int gh, int gw, const float* boxes, const int32_t* counts,
                              const float* sizes, int K, int grid, float* emb, void* stream) {
-  if (!features || !boxes || !emb || ((uintptr_t)features & 15) != 0 || ((uintptr_t)emb & 15) != 0) return DOD_ERR_INVALID;
-  if (B < 1 || K < 1 || K > kRoiMaxK || (long long)B * K > 0x7fffffffLL) return DOD_ERR_INVALID;
-  if (D < 4 || D > kRoiMaxD || D % 4 != 0 || grid < 1 || grid > kRoiMaxGrid) return DOD_ERR_INVALID;
-  if (gh < 1 || gw < 1 || first_token < 0 || N < 1 || (long long)first_token + (long long)gh * gw > (long long)N) return DOD_ERR_INVALID;
+  if (!features || !boxes || !emb || ((uintptr_t)features & 15) != 0 || ((uintptr_t)emb & 15) != 0) return dod_fail(DOD_ERR_INVALID, "dod_roi_embed: null features / boxes / emb, or features / emb not 16-byte aligned");
+  if (B < 1 || K < 1 || K > kRoiMaxK || (long long)B * K > 0x7fffffffLL) return dod_fail(DOD_ERR_INVALID, "dod_roi_embed: B=%d K=%d outside the limits", B, K);
+  if (D < 4 || D > kRoiMaxD || D % 4 != 0 || grid < 1 || grid > kRoiMaxGrid) return dod_fail(DOD_ERR_INVALID, "dod_roi_embed: D=%d or grid=%d outside the limits, or D no multiple of 4", D, grid);
+  if (gh < 1 || gw < 1 || first_token < 0 || N < 1 || (long long)first_token + (long long)gh * gw > (long long)N) return dod_fail(DOD_ERR_INVALID, "dod_roi_embed: gh=%d gw=%d first_token=%d do not fit the N=%d tokens", gh, gw, first_token, N);
   RoiArgs a;
   a.feat = features; a.N = N; a.D = D; a.first = first_token; a.gh = gh; a.gw = gw;
   a.boxes = boxes; a.counts = (const int*)counts; a.sizes = sizes;
   a.K = K; a.grid = grid; a.emb = emb;
   hipLaunchKernelGGL(roi_embed_kernel, dim3((unsigned)(B * K)), dim3(kRoiThreads), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_roi_embed");
 }

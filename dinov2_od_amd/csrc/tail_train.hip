@@ -86,12 +86,12 @@ size_t dod_backbone_tail_workspace_bytes(const dod_config* cfg, int B, int N, in
 
 int dod_backbone_tail_train_forward(const dod_config* cfg, const dod_bb_tail_params* p, const float* x_in, int B, int N, float* mem_out,
                                     void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {
-  if (!p || !p->blocks) return tfail(DOD_ERR_INVALID, "backbone tail: null parameters");
+  if (!p || !p->blocks) return dod_fail(DOD_ERR_INVALID, "backbone tail: null parameters");
   TDims d;
-  if (!make_tdims(cfg, B, N, p->nblocks, &d)) return tfail(DOD_ERR_INVALID, "backbone tail: unsupported configuration (head_dim <= 128, N <= %d, 1 <= lora_r <= 64, at most 8 blocks)", MHA_MAXQ);
+  if (!make_tdims(cfg, B, N, p->nblocks, &d)) return dod_fail(DOD_ERR_INVALID, "backbone tail: unsupported configuration (head_dim <= 128, N <= %d, 1 <= lora_r <= 64, at most 8 blocks)", MHA_MAXQ);
   TTape t; TScratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
   int rc = entry_check("backbone tail", x_in && mem_out && tape && ws, 0.f, tape_bytes, carve_ttape(d, tape, t) + 256, ws_bytes, carve_tscratch(d, ws, sc) + 256); if (rc) return rc;
-  if (cfg->target_dim && (!p->proj_w || !p->proj_b)) return tfail(DOD_ERR_MISSING, "backbone tail: projection weights missing");
+  if (cfg->target_dim && (!p->proj_w || !p->proj_b)) return dod_fail(DOD_ERR_MISSING, "backbone tail: projection weights missing");
   hipStream_t s = (hipStream_t)stream;
   const Mm mm = mm_of(cfg);      // DOD_PREC_BF16X3: every linear of the tail, forward and backward, as a bf16 split product (attention, LoRA rank-r products and LayerNorm stay)
   const int M = d.M, D = d.D, F = d.F, F1 = d.F1;
@@ -136,9 +136,9 @@ int dod_backbone_tail_train_forward(const dod_config* cfg, const dod_bb_tail_par
 
 int dod_backbone_tail_train_backward(const dod_config* cfg, const dod_bb_tail_params* p, int B, int N, const float* d_mem, const void* tape,
                                      size_t tape_bytes, const dod_bb_tail_params* grads, void* ws, size_t ws_bytes, void* stream) {
-  if (!p || !p->blocks || !grads || !grads->blocks || grads->nblocks != p->nblocks) return tfail(DOD_ERR_INVALID, "backbone tail: null / mismatched parameters");
+  if (!p || !p->blocks || !grads || !grads->blocks || grads->nblocks != p->nblocks) return dod_fail(DOD_ERR_INVALID, "backbone tail: null / mismatched parameters");
   TDims d;
-  if (!make_tdims(cfg, B, N, p->nblocks, &d)) return tfail(DOD_ERR_INVALID, "backbone tail: unsupported configuration");
+  if (!make_tdims(cfg, B, N, p->nblocks, &d)) return dod_fail(DOD_ERR_INVALID, "backbone tail: unsupported configuration");
   TTape t; TScratch sc;      // carved first: the carve itself says how many bytes each buffer must hold
   int rc = entry_check("backbone tail", d_mem && tape && ws, 0.f, tape_bytes, carve_ttape(d, tape, t) + 256, ws_bytes, carve_tscratch(d, ws, sc) + 256); if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;

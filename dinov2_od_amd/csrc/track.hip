@@ -439,24 +439,26 @@ extern "C" size_t dod_track_workspace_bytes(int S, int T, int K) {
 }
 
 extern "C" int dod_track_reset(void* state, int S, int T, const int32_t* stream_mask, void* stream) {
-  if (!state || ((uintptr_t)state & 7) != 0 || !trk_shape_ok(S, T)) return DOD_ERR_INVALID;
+  if (!state || ((uintptr_t)state & 7) != 0 || !trk_shape_ok(S, T)) return dod_fail(DOD_ERR_INVALID, "dod_track_reset: null or misaligned state, or S / T outside the limits");
   TrkTable tab;
   trk_carve((unsigned char*)state, S, T, &tab);
   hipLaunchKernelGGL(track_reset_kernel, dim3((unsigned)S), dim3(DOD_WAVE), 0, (hipStream_t)stream, tab, T, (const int*)stream_mask);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_track_reset");
 }
 
-// the argument check dod_track_update and dod_track_update_app share, and the arguments both kernels take
-static int trk_update_args(void* state, int S, int T, const float* scores, const int32_t* labels, const float* boxes, const int32_t* counts, int K,
+// the argument check dod_track_update and dod_track_update_app share (who: the entry point, for the message), and the arguments both kernels take
+static int trk_update_args(const char* who, void* state, int S, int T, const float* scores, const int32_t* labels, const float* boxes, const int32_t* counts, int K,
                            const dod_track_params* params, int32_t* ids, float* track_boxes, void* workspace, size_t workspace_bytes, TrkArgs& a) {
-  if (!state || ((uintptr_t)state & 7) != 0 || !scores || !labels || !boxes || !counts || !params || !ids || !track_boxes) return DOD_ERR_INVALID;
-  if (!trk_shape_ok(S, T) || !trk_rows_ok(K)) return DOD_ERR_INVALID;
+  if (!state || ((uintptr_t)state & 7) != 0 || !scores || !labels || !boxes || !counts || !params || !ids || !track_boxes)
+    return dod_fail(DOD_ERR_INVALID, "%s: null argument or misaligned state", who);
+  if (!trk_shape_ok(S, T) || !trk_rows_ok(K)) return dod_fail(DOD_ERR_INVALID, "%s: S=%d T=%d K=%d outside the limits", who, S, T, K);
   const dod_track_params& p = *params;
   const float th[6] = {p.track_thresh, p.low_thresh, p.new_thresh, p.match_thresh, p.second_thresh, p.tentative_thresh};
   for (float v : th)
-    if (v != v) return DOD_ERR_INVALID;
-  if (p.max_age < 0 || !(p.low_thresh <= p.track_thresh)) return DOD_ERR_INVALID;
-  if (!workspace || ((uintptr_t)workspace & 7) != 0 || workspace_bytes < dod_track_workspace_bytes(S, T, K)) return DOD_ERR_INVALID;
+    if (v != v) return dod_fail(DOD_ERR_INVALID, "%s: a NaN threshold", who);
+  if (p.max_age < 0 || !(p.low_thresh <= p.track_thresh)) return dod_fail(DOD_ERR_INVALID, "%s: negative max_age, or low_thresh above track_thresh", who);
+  if (!workspace || ((uintptr_t)workspace & 7) != 0 || workspace_bytes < dod_track_workspace_bytes(S, T, K))
+    return dod_fail(DOD_ERR_INVALID, "%s: null, misaligned or short workspace", who);
   trk_carve((unsigned char*)state, S, T, &a.tab);
   a.T = T; a.K = K;
   a.scores = scores; a.labels = (const int*)labels; a.boxes = boxes; a.counts = (const int*)counts;
@@ -472,9 +474,9 @@ extern "C" int dod_track_update(void* state, int S, int T, const float* scores, 
                                 int K, const dod_track_params* params, int32_t* ids, float* track_boxes, void* workspace, size_t workspace_bytes,
                                 void* stream) {
   TrkArgs a;
-  if (const int rc = trk_update_args(state, S, T, scores, labels, boxes, counts, K, params, ids, track_boxes, workspace, workspace_bytes, a)) return rc;
+  if (const int rc = trk_update_args("dod_track_update", state, S, T, scores, labels, boxes, counts, K, params, ids, track_boxes, workspace, workspace_bytes, a)) return rc;
   hipLaunchKernelGGL(track_update_kernel<false>, dim3((unsigned)S), dim3(DOD_WAVE), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_track_update");
 }
 
 static bool trk_app_params_ok(const dod_track_app_params* q) {
@@ -486,37 +488,39 @@ extern "C" int dod_track_update_app(void* state, int S, int T, const float* scor
                                     int K, const dod_track_params* params, const dod_track_app_params* app_params, const float* dots, int32_t* ids,
                                     float* track_boxes, int32_t* assoc, void* workspace, size_t workspace_bytes, void* stream) {
   TrkAppArgs a;
-  if (!trk_app_params_ok(app_params) || !dots || !assoc) return DOD_ERR_INVALID;
-  if (const int rc = trk_update_args(state, S, T, scores, labels, boxes, counts, K, params, ids, track_boxes, workspace, workspace_bytes, a)) return rc;
+  if (!trk_app_params_ok(app_params) || !dots || !assoc) return dod_fail(DOD_ERR_INVALID, "dod_track_update_app: null dots / assoc, or app_params null or out of range");
+  if (const int rc = trk_update_args("dod_track_update_app", state, S, T, scores, labels, boxes, counts, K, params, ids, track_boxes, workspace, workspace_bytes, a)) return rc;
   a.dots = dots; a.assoc = (int*)assoc;
   a.app_thresh = app_params->appearance_thresh; a.prox_thresh = app_params->proximity_thresh;
   hipLaunchKernelGGL(track_update_kernel<true>, dim3((unsigned)S), dim3(DOD_WAVE), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_track_update_app");
 }
 
 extern "C" int dod_track_embed_dots(const float* slot_emb, const float* emb, int S, int T, int K, int D, float* dots, void* stream) {
-  if (!slot_emb || !emb || !dots || !trk_shape_ok(S, T) || !trk_rows_ok(K) || !trk_embed_ok(D)) return DOD_ERR_INVALID;
+  if (!slot_emb || !emb || !dots || !trk_shape_ok(S, T) || !trk_rows_ok(K) || !trk_embed_ok(D))
+    return dod_fail(DOD_ERR_INVALID, "dod_track_embed_dots: null argument, or S / T / K / D outside the limits");
   GemmF32X g = {};
   g.A = slot_emb; g.lda = D; g.a_sb = (long long)T * D;
   g.W = emb; g.ldw = D; g.w_sb = (long long)K * D;
   g.C = dots; g.ldc = K; g.c_sb = (long long)T * K;
   g.M = T; g.N = K; g.K = D; g.batch = S; g.hb = 1; g.alpha = 1.0f; g.ksplit = 1;
   const int rc = launch_gemm_f32x(g, (hipStream_t)stream);
-  return rc == 0 ? DOD_OK : (rc == 3 ? DOD_ERR_HIP : DOD_ERR_INVALID);
+  return rc == 0 ? DOD_OK : dod_fail(rc == 3 ? DOD_ERR_HIP : DOD_ERR_INVALID, "dod_track_embed_dots: launch_gemm_f32x rejected (rc %d)", rc);
 }
 
 extern "C" int dod_track_embed_commit(float* slot_emb, const float* emb, const int32_t* assoc, int S, int T, int K, int D, float momentum, void* stream) {
-  if (!slot_emb || !emb || !assoc || !trk_shape_ok(S, T) || !trk_rows_ok(K) || !trk_embed_ok(D)) return DOD_ERR_INVALID;
-  if (!(momentum >= 0.0f && momentum <= 1.0f)) return DOD_ERR_INVALID;
+  if (!slot_emb || !emb || !assoc || !trk_shape_ok(S, T) || !trk_rows_ok(K) || !trk_embed_ok(D))
+    return dod_fail(DOD_ERR_INVALID, "dod_track_embed_commit: null argument, or S / T / K / D outside the limits");
+  if (!(momentum >= 0.0f && momentum <= 1.0f)) return dod_fail(DOD_ERR_INVALID, "dod_track_embed_commit: momentum %g outside [0, 1]", momentum);
   hipLaunchKernelGGL(track_embed_commit_kernel, dim3((unsigned)K, (unsigned)S), dim3(DOD_WAVE), 0, (hipStream_t)stream, slot_emb, emb, (const int*)assoc, T, K, D,
                      momentum);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched("dod_track_embed_commit");
 }
 
 extern "C" int dod_track_export(const void* state, int S, int T, double* mean, double* cov, int32_t* slot_state, int32_t* id, int32_t* label,
                                 int32_t* last_frame, float* score, int32_t* frame, int32_t* next_id, int32_t* overflow, void* stream) {
-  if (!state || ((uintptr_t)state & 7) != 0 || !trk_shape_ok(S, T)) return DOD_ERR_INVALID;
-  if (!mean || !cov || !slot_state || !id || !label || !last_frame || !score || !frame || !next_id || !overflow) return DOD_ERR_INVALID;
+  if (!state || ((uintptr_t)state & 7) != 0 || !trk_shape_ok(S, T)) return dod_fail(DOD_ERR_INVALID, "dod_track_export: null or misaligned state, or S / T outside the limits");
+  if (!mean || !cov || !slot_state || !id || !label || !last_frame || !score || !frame || !next_id || !overflow) return dod_fail(DOD_ERR_INVALID, "dod_track_export: null output");
   TrkTable tab;
   trk_carve((unsigned char*)const_cast<void*>(state), S, T, &tab);
   const size_t n = (size_t)S * T;
@@ -526,6 +530,6 @@ extern "C" int dod_track_export(const void* state, int S, int T, double* mean, d
       {label, tab.label, n * 4}, {last_frame, tab.last, n * 4}, {score, tab.score, n * 4}, {frame, tab.frame, (size_t)S * 4},
       {next_id, tab.next_id, (size_t)S * 4}, {overflow, tab.overflow, (size_t)S * 4}};
   for (const auto& c : parts)
-    if (hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return DOD_ERR_HIP;
+    if (hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return dod_fail(DOD_ERR_HIP, "dod_track_export: hipMemcpyAsync failed");
   return DOD_OK;
 }

@@ -12,21 +12,19 @@ namespace dtrain {
 inline size_t up4(size_t x) { return (x + 3) & ~(size_t)3; }
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// ------------------------------------------------------------------------------------------------ errors (train_ops.hip)
-// One thread_local message behind dod_decoder_train_last_error(): forward and backward of a step may run on different threads (autograd engine)
-int tfail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-#define TK(x) do { int r_ = (x); if (r_) return dtrain::tfail(r_ == 3 ? DOD_ERR_HIP : DOD_ERR_INVALID, "decoder train: %s failed (%d)", #x, r_); } while (0)
-#define TH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return dtrain::tfail(DOD_ERR_HIP, "decoder train: %s: %s", #x, hipGetErrorString(e_)); } while (0)
-#define OPFAIL(...) return dtrain::tfail(DOD_ERR_INVALID, __VA_ARGS__)
+// ------------------------------------------------------------------------------------------------ errors (dod_common.h dod_fail)
+#define TK(x) do { int r_ = (x); if (r_) return dod_fail(r_ == 3 ? DOD_ERR_HIP : DOD_ERR_INVALID, "decoder train: %s failed (%d)", #x, r_); } while (0)
+#define TH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return dod_fail(DOD_ERR_HIP, "decoder train: %s: %s", #x, hipGetErrorString(e_)); } while (0)
+#define OPFAIL(...) return dod_fail(DOD_ERR_INVALID, __VA_ARGS__)
 
 // ------------------------------------------------------------------------------------------------ entry checks, tape / scratch carve
 // What every step's entry point checks once its configuration is taken: `buffers` = none of its pointers is null; the backward passes
 // dropout_p = 0 (the forward has checked the rate both calls are given); *_need = what the step's carve from the caller's pointer
 // reports + 256 (a null pointer carves as the sizing pass does, and fails the first check).  Returns a dod_status.
 inline int entry_check(const char* step, bool buffers, float dropout_p, size_t tape_bytes, size_t tape_need, size_t ws_bytes, size_t ws_need) {
-  if (!buffers) return tfail(DOD_ERR_INVALID, "%s: null buffer / mismatched parameters", step);
-  if (dropout_p < 0.f || dropout_p >= 1.f) return tfail(DOD_ERR_INVALID, "%s: dropout %g outside [0, 1)", step, dropout_p);
-  if (tape_bytes < tape_need || ws_bytes < ws_need) return tfail(DOD_ERR_STATE, "%s: tape / workspace too small", step);
+  if (!buffers) return dod_fail(DOD_ERR_INVALID, "%s: null buffer / mismatched parameters", step);
+  if (dropout_p < 0.f || dropout_p >= 1.f) return dod_fail(DOD_ERR_INVALID, "%s: dropout %g outside [0, 1)", step, dropout_p);
+  if (tape_bytes < tape_need || ws_bytes < ws_need) return dod_fail(DOD_ERR_STATE, "%s: tape / workspace too small", step);
   return DOD_OK;
 }
 // The tape and scratch layouts are carved by dod::Carver (256-byte slots; a null base is the sizing pass and yields null pointers) from

@@ -44,8 +44,8 @@ static float* det_scratch(size_t floats) {
   static std::mutex mu;
   static float* buf[16] = {};
   static size_t cap[16] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+  const int dev = current_device_slot();
+  if (dev < 0) return nullptr;
   std::lock_guard<std::mutex> lk(mu);
   if (cap[dev] < floats) {
     if (buf[dev]) { (void)hipDeviceSynchronize(); (void)hipFree(buf[dev]); buf[dev] = nullptr; cap[dev] = 0; }
@@ -562,22 +562,13 @@ __global__ __launch_bounds__(256) void deform_bwd_values_det_kernel(const float*
   if (lane + 64 < dh) dv[lane + 64] += acc1;
 }
 
-// ------------------------------------------------------------------------------------------------ errors
-thread_local std::string g_terr;   // forward and backward of a step may run on different threads (autograd engine)
-int tfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-  g_terr = buf;
-  return code;
-}
-
 // dproj zero on entry, dvalues accumulated; the scatter kernel, or in deterministic mode the three ordered ones.  Returns a dod_status.
 int launch_deform_bwd(const float* proj, int ldp, const float* values, const float* dout, int B, int Q, int N, int Hd, int P, int dh, int h, int w,
                       float* dproj, float* dvalues, hipStream_t s) {
   const int BQ = B * Q;
   if (det_mode()) {
     float* dref_part = det_scratch((size_t)BQ * Hd * 2);
-    if (!dref_part) return tfail(DOD_ERR_HIP, "deterministic mode: scratch allocation failed");
+    if (!dref_part) return dod_fail(DOD_ERR_HIP, "deterministic mode: scratch allocation failed");
     hipLaunchKernelGGL(deform_bwd_kernel<true>, dim3((unsigned)(((long)BQ * Hd + 3) / 4)), dim3(256), 0, s, proj, ldp, values, dout, B, Q, N, Hd, P, dh, h, w,
                        dproj, dvalues, dref_part);
     hipLaunchKernelGGL(deform_dref_det_kernel, dim3((BQ + 255) / 256), dim3(256), 0, s, dref_part, BQ, Hd, ldp, dproj);
@@ -746,8 +737,6 @@ inline bool attn_vjp_shape_ok(int B, int Lq, int Lk, int heads, int dh, int form
 
 extern "C" {
 
-const char* dod_decoder_train_last_error(void) { return g_terr.c_str(); }
-
 int dod_op_layernorm_bwd(const float* x, const float* gamma, const float* dy, float eps, int rows, int D, float* dx, float* dgamma, float* dbeta,
                          void* stream) {
   if (!x || !gamma || !dy || !dx || !dgamma || !dbeta) OPFAIL("dod_op_layernorm_bwd: null buffer");
@@ -771,7 +760,7 @@ int dod_op_attention_f32_vjp(const float* q, int ldq, const float* k, const floa
   if (ldq < Dm || ldkv < Dm || ldo < Dm || lddq < Dm || lddkv < Dm || (ldq | ldkv | ldo | lddq | lddkv) % 4)
     OPFAIL("dod_op_attention_f32_vjp: every pitch must be a multiple of 4 and at least heads * head_dim = %d", Dm);
   if (dropout_p < 0.f || dropout_p >= 1.f || (form == 1 && dropout_p != 0.f)) OPFAIL("dod_op_attention_f32_vjp: dropout %g (form 0: [0, 1); form 1: 0)", dropout_p);
-  if (workspace_bytes < attn_vjp_ws(B, Lq, Lk, heads, form) + 256) return tfail(DOD_ERR_STATE, "dod_op_attention_f32_vjp: workspace too small");
+  if (workspace_bytes < attn_vjp_ws(B, Lq, Lk, heads, form) + 256) return dod_fail(DOD_ERR_STATE, "dod_op_attention_f32_vjp: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   dod::Carver c = carver(workspace);
   if (form == 0) {
@@ -814,7 +803,7 @@ int dod_op_lora_grads(const float* X, int in_f, const float* dY, int ldy, int ou
   if (!X || !dY || !A || !Bm || !dA || !dB || !workspace) OPFAIL("dod_op_lora_grads: null buffer");
   if (r < 1 || r > 64) OPFAIL("dod_op_lora_grads: rank %d outside 1..64", r);
   if (M <= 0 || in_f <= 0 || out_f <= 0 || ldy < out_f) OPFAIL("dod_op_lora_grads: M=%d in=%d out=%d ldy=%d", M, in_f, out_f, ldy);
-  if (workspace_bytes < dod_op_lora_grads_workspace_bytes(M, r)) return tfail(DOD_ERR_STATE, "dod_op_lora_grads: workspace too small");
+  if (workspace_bytes < dod_op_lora_grads_workspace_bytes(M, r)) return dod_fail(DOD_ERR_STATE, "dod_op_lora_grads: workspace too small");
   dod::Carver c = carver(workspace);
   float* T = takef(c, (size_t)M * up4(r));
   float* U = takef(c, (size_t)M * up4(r));

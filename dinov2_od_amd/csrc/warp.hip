@@ -88,13 +88,13 @@ __global__ __launch_bounds__(WP_TX * WP_TY) void wp_warp_kernel(const unsigned c
   }
 }
 
-static int preprocess_warp_impl(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
+static int preprocess_warp_impl(const char* who, const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
                                 const double* coeffs, const uint8_t* fills, int fill_per_image, int out_h, int out_w, float* out,
                                 uint8_t* out_u8, void* stream) {
-  if (!src || !src_offs || !heights || !widths || !coeffs || !fills || (!out && !out_u8)) return DOD_ERR_INVALID;
-  if (B <= 0 || B > 65535 || out_h <= 0 || out_w <= 0) return DOD_ERR_INVALID;
+  if (!src || !src_offs || !heights || !widths || !coeffs || !fills || (!out && !out_u8)) return dod_fail(DOD_ERR_INVALID, "%s: null argument", who);
+  if (B <= 0 || B > 65535 || out_h <= 0 || out_w <= 0) return dod_fail(DOD_ERR_INVALID, "%s: B=%d out_h=%d out_w=%d outside the limits", who, B, out_h, out_w);
   const dim3 grid((out_w + WP_TX - 1) / WP_TX, (out_h + WP_TY - 1) / WP_TY, B);
-  if (grid.y > 65535) return DOD_ERR_INVALID;      // more than 524 280 output rows: past one launch
+  if (grid.y > 65535) return dod_fail(DOD_ERR_INVALID, "%s: out_h = %d past one launch", who, out_h);      // more than 524 280 output rows: past one launch
   hipStream_t s = (hipStream_t)stream;
   if (out_u8)
     hipLaunchKernelGGL(wp_warp_kernel<true>, grid, dim3(WP_TX * WP_TY), 0, s, (const unsigned char*)src, (const long long*)src_offs, heights,
@@ -102,16 +102,16 @@ static int preprocess_warp_impl(const uint8_t* src, const int64_t* src_offs, con
   else
     hipLaunchKernelGGL(wp_warp_kernel<false>, grid, dim3(WP_TX * WP_TY), 0, s, (const unsigned char*)src, (const long long*)src_offs, heights,
                        widths, coeffs, (const unsigned char*)fills, fill_per_image, out_h, out_w, out, (unsigned char*)nullptr);
-  return hipGetLastError() == hipSuccess ? DOD_OK : DOD_ERR_HIP;
+  return dod_launched(who);
 }
 
 extern "C" int dod_preprocess_warp(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
                                    const double* coeffs, const uint8_t* fills, int fill_per_image, int out_h, int out_w, float* out,
                                    void* stream) {
-  return preprocess_warp_impl(src, src_offs, heights, widths, B, coeffs, fills, fill_per_image, out_h, out_w, out, nullptr, stream);
+  return preprocess_warp_impl("dod_preprocess_warp", src, src_offs, heights, widths, B, coeffs, fills, fill_per_image, out_h, out_w, out, nullptr, stream);
 }
 extern "C" int dod_preprocess_warp_u8(const uint8_t* src, const int64_t* src_offs, const int32_t* heights, const int32_t* widths, int B,
                                       const double* coeffs, const uint8_t* fills, int fill_per_image, int out_h, int out_w,
                                       uint8_t* out_hwc, void* stream) {
-  return preprocess_warp_impl(src, src_offs, heights, widths, B, coeffs, fills, fill_per_image, out_h, out_w, nullptr, out_hwc, stream);
+  return preprocess_warp_impl("dod_preprocess_warp_u8", src, src_offs, heights, widths, B, coeffs, fills, fill_per_image, out_h, out_w, nullptr, out_hwc, stream);
 }

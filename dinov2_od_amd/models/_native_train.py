@@ -70,9 +70,7 @@ def _struct(tensors, cfg=None):
 
 
 def _check(rc):
-    if rc != 0:
-        msg = nat.lib().dod_decoder_train_last_error()
-        raise (ValueError if rc == 1 else RuntimeError)(msg.decode() if msg else f"dinodet error {rc}")
+    nat.check(rc, exc={1: ValueError}, default=RuntimeError)      # the training step's own mapping: a missing weight is a RuntimeError here
 
 
 # What tells the two decoder steps apart: the four entry points dod_<stem>_train_{tape_bytes, workspace_bytes, forward, backward}, the

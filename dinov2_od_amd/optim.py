@@ -41,12 +41,7 @@ _DESC = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", 
 assert _DESC.itemsize == C.sizeof(_native.DodOptimTensor)
 _EMA_DESC = np.dtype([("e", "<u8"), ("p", "<u8"), ("n", "<i8")])       # struct dod_optim_ema_tensor
 assert _EMA_DESC.itemsize == C.sizeof(_native.DodOptimEmaTensor)
-
-
-def _check(rc):
-    if rc != 0:
-        msg = _native.lib().dod_optim_last_error()
-        raise _native._EXC.get(rc, _native.DodError)(msg.decode() if msg else f"dinodet error {rc}")
+_check = _native.check
 
 
 def _dense_f32_cuda(t):

@@ -11,8 +11,16 @@
  *  - plain pointers and sizes only; every tensor pointer is a DEVICE pointer (HIP), row-major, fp32
  *    unless stated; `stream` is a hipStream_t passed as void* (NULL = default stream).
  *  - every call returns 0 on success, a non-zero dod_status otherwise; no C++ exception crosses
- *    the ABI.  dod_last_error() returns a message for the last failing call on that handle
- *    (handle may be NULL for errors of dod_create / stateless ops).
+ *    the ABI.
+ *  - errors: a failing call that is given a handle leaves its message on that handle, read with
+ *    dod_last_error(handle).  Every other failing call (dod_create, a NULL handle, every stateless
+ *    entry point: ops, training steps, optimizer, pre / post-processing, tracking, evaluation)
+ *    has written the CALLING THREAD's message slot before it returns non-zero; a successful call
+ *    leaves the slot alone.  The message begins with the entry point's name (the training steps:
+ *    with the step's; dod_create and the dod_op_* operators name the offending argument only).
+ *    dod_last_error(NULL), dod_decoder_train_last_error() and
+ *    dod_optim_last_error() all return the calling thread's slot: the pointer is valid until that
+ *    thread's next failing call.
  *  - all work is enqueued on the caller's stream; forward calls never synchronise and never
  *    allocate once dod_prepare() has been called for that (H, W).
  *  - a handle is re-entrant across handles but not thread-safe on one handle (the reference is
@@ -1049,7 +1057,7 @@ int dod_dense_decoder_train_backward(const dod_config* cfg, const dod_dense_dec_
  * lora_A / lora_B (dino_detector/utils.py:46-70) and of the projection.  Frozen tensors (w, b, LayerNorm, LayerScale) are read
  * only; in `grads` only A, Bm, proj_w, proj_b are written (float accumulators, same layout).  GELU MLP (ViT-S/B/L) or SwiGLU
  * (ViT-g, cfg->swiglu: the fc1 / fc2 slots then hold mlp.weights_in [2F, D] / mlp.weights_out [D, F]); hidden <= 2048;
- * errors through dod_decoder_train_last_error(). */
+ */
 typedef struct dod_lora_linear { const float *w, *b, *A, *Bm; } dod_lora_linear;        /* [out,in], [out], [r,in], [out,r] */
 typedef struct dod_bb_block_params {
   const float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *ls1, *ls2;                              /* frozen */
@@ -1076,7 +1084,7 @@ int dod_backbone_tail_train_backward(const dod_config* cfg, const dod_bb_tail_pa
  * run.  Stateless; every pointer is a caller-owned fp32 DEVICE buffer; enqueued on `stream`, no sync.  The "deterministic" test
  * option / DINODET_DETERMINISTIC selects the ordered reductions exactly as in the steps (that mode keeps a library-owned partial-sum
  * buffer).  DOD_ERR_INVALID before any launch for a NULL pointer or a shape outside the stated limits, DOD_ERR_STATE for a
- * workspace that is too small; messages through dod_decoder_train_last_error().
+ * workspace that is too small.
  *
  * LayerNorm backward: x, dy, dx [rows, D] dense, D <= 2048.  dx is written; dgamma / dbeta [D] ACCUMULATE. */
 int dod_op_layernorm_bwd(const float* x, const float* gamma, const float* dy, float eps, int rows, int D, float* dx, float* dgamma,
@@ -1140,8 +1148,7 @@ int dod_op_colsum_add(const float* src, int ld, int rows, int cols, float* dst, 
  *   dod_optim_adam_step       max_norm > 0: clip and update fused, the clipped gradient is NOT written back, total_norm is stored.
  *                             max_norm <= 0: no clip, no norm launch, total_norm_dev and ws are not touched (may be NULL)
  *   workspace                 dod_optim_workspace_bytes(n_tensors, total elements) bytes, monotone in both (0 for a negative one)
- * n_tensors == 0 (or no elements at all) succeeds and stores total_norm = 0.  DOD_ERR_INVALID, before any HIP call and with a
- * message behind dod_optim_last_error() (per thread): n_tensors < 0, a NULL list, a negative n, a NULL pointer of a tensor with
+ * n_tensors == 0 (or no elements at all) succeeds and stores total_norm = 0.  DOD_ERR_INVALID, before any HIP call: n_tensors < 0, a NULL list, a negative n, a NULL pointer of a tensor with
  * n > 0, NULL total_norm_dev, a NULL or short workspace, betas outside [0, 1), negative eps / weight_decay.
  * dod_test_counter("optim_launches") counts the launches of both entries; "optim_chunk_elems" / "optim_table_tensors" /
  * "optim_norm_table_tensors" report the elements per workgroup and the tensors per update / norm launch. */

@@ -434,3 +434,200 @@ def test_engine_named_cache_follows_replaced_parameters():
 def test_abi_version_matches_header(lib):
     hdr = open(os.path.join(ROOT, "include", "dinodet.h")).read()
     assert int(re.search(r"#define DOD_ABI_VERSION (\d+)", hdr).group(1)) == lib.dod_abi_version() == nat.ABI_VERSION
+
+
+# ---- the calling thread's error slot (include/dinodet.h, Conventions: errors)
+# every status-returning entry point of track / criterion / jpeg / draw / detect / detect_views / preproc / roi_embed / warp / postproc /
+# assign / matchcost .hip, with the status its all-NULL, all-zero call returns: a null pointer fails each one's first check, before any device call
+ENTRY_POINTS = [
+    ("dod_track_reset", 1), ("dod_track_update", 1), ("dod_track_update_app", 1), ("dod_track_embed_dots", 1), ("dod_track_embed_commit", 1),
+    ("dod_track_export", 1),
+    ("dod_set_criterion_forward", 1), ("dod_set_criterion_backward", 1), ("dod_set_criterion_layers_forward", 1),
+    ("dod_set_criterion_layers_backward", 1),
+    ("dod_jpeg_entropy_host", 1), ("dod_jpeg_entropy_device", 1), ("dod_jpeg_idct", 1), ("dod_jpeg_color", 1),
+    ("dod_draw_detections", 1), ("dod_detect", 1), ("dod_detect_views", 1), ("dod_fuse_views", 1),
+    ("dod_preprocess", 1), ("dod_preprocess_u8", 1), ("dod_preprocess_aug", 1), ("dod_preprocess_aug_u8", 1), ("dod_preprocess_compose", 1),
+    ("dod_preprocess_compose_u8", 1), ("dod_preprocess_warp", 1), ("dod_preprocess_warp_u8", 1),
+    ("dod_roi_embed", 1), ("dod_postprocess", 1), ("dod_match_assign", 1), ("dod_match_cost", 1),
+]
+
+
+def _null_args(name):
+    """NULL for every pointer argument and zero for every number of entry point `name` (by the binding's argument types)"""
+    return [0.0 if t in (C.c_float, C.c_double) else 0 if t in (C.c_int, C.c_int32, C.c_int64, C.c_size_t, C.c_uint64) else None
+            for t in nat.SYMBOLS[name][1]]
+
+
+def _buf():
+    return C.cast((C.c_double * 64)(), C.c_void_p)      # 8-byte aligned host memory: argument checks never read through it
+
+
+# one more rejecting call per shared checker and per status other than DOD_ERR_INVALID: (entry point, arguments by position over the null
+# call, status, a word of the message)
+def _shape_cases():
+    p = _buf()
+    return [
+        ("dod_track_update", {0: p, 3: p, 4: p, 5: p, 6: p, 8: C.byref(nat.DodTrackParams()), 9: p, 10: p}, 1, b"outside the limits"),      # S = T = K = 0
+        ("dod_track_update_app", {9: C.byref(nat.DodTrackAppParams()), 10: p, 13: p}, 1, b"null argument or misaligned state"),       # its own check passes
+        ("dod_set_criterion_forward", {0: p, 1: 4, 4: 1, 5: 1, 6: 4, 7: p, 9: 1}, 1, b"null losses"),                # the shared check passes
+        ("dod_set_criterion_layers_forward", {0: p, 1: 4, 4: 1, 5: 1, 6: 1, 7: 4, 8: p, 10: 1, 16: p, 18: p}, 3, b"workspace too small"),
+        ("dod_match_assign", {1: p, 2: 1, 3: 1, 7: p, 8: p}, 3, b"workspace"),
+        ("dod_detect_views", {13: 2}, 1, b"nms_metric"),
+        ("dod_preprocess_warp_u8", {0: p, 1: p, 2: p, 3: p, 4: 70000, 5: p, 6: p, 8: 8, 9: 8, 10: p}, 1, b"B=70000"),
+    ]
+
+
+@pytest.mark.parametrize("name,status", ENTRY_POINTS)
+def test_every_rejecting_entry_point_names_itself(lib, name, status):
+    assert lib.dod_test_set_option(b"no_such_option", 1) == 1                      # something else's message is in the slot
+    assert getattr(lib, name)(*_null_args(name)) == status
+    msg = lib.dod_last_error(None)
+    assert msg.startswith(name.encode() + b":"), msg
+
+
+@pytest.mark.parametrize("case", range(7))
+def test_shared_checkers_name_the_entry_point_that_called_them(lib, case):
+    name, over, status, word = _shape_cases()[case]
+    args = _null_args(name)
+    for i, v in over.items():
+        args[i] = v
+    assert getattr(lib, name)(*args) == status
+    msg = lib.dod_last_error(None)
+    assert msg.startswith(name.encode() + b":") and word in msg, msg
+
+
+def test_entry_point_table_covers_the_twelve_files():
+    """every extern "C" int function of the twelve files is in ENTRY_POINTS, and none of them returns a bare DOD_ERR_* constant or ends on a
+    bare launch-error check: every such exit goes through dod_fail / dod_launched"""
+    found = set()
+    for f in ("track", "criterion", "jpeg", "draw", "detect", "detect_views", "preproc", "roi_embed", "warp", "postproc", "assign", "matchcost"):
+        src = open(os.path.join(ROOT, "dinov2_od_amd", "csrc", f + ".hip")).read()
+        found |= set(re.findall(r'^extern "C" int (dod_\w+)\(', src, re.M))
+        assert not re.search(r"return DOD_ERR_\w+;|\? DOD_OK : DOD_ERR_HIP", src), f
+    assert found == {n for n, _ in ENTRY_POINTS}
+    csrc = os.path.join(ROOT, "dinov2_od_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, f)).read() for f in os.listdir(csrc))
+    for gone in ("g_err", "g_terr", "g_oerr", "g_tail_owner", "g_f32k_owner"):
+        assert not re.search(rf"\b{gone}\b", text), gone
+
+
+def test_a_rejected_call_replaces_a_stale_message(lib):
+    assert lib.dod_test_set_option(b"no_such_option", 1) == 1 and b"unknown test option" in lib.dod_last_error(None)
+    assert lib.dod_track_update(*_null_args("dod_track_update")) == 1
+    assert lib.dod_last_error(None).startswith(b"dod_track_update:")
+    assert lib.dod_test_set_option(b"tailsplit", -1) == 0                          # a successful call leaves the slot alone
+    assert lib.dod_last_error(None).startswith(b"dod_track_update:")
+
+
+def _readers(lib):
+    return lib.dod_last_error(None), lib.dod_decoder_train_last_error(), lib.dod_optim_last_error()
+
+
+def test_the_three_readers_return_one_slot(lib):
+    assert lib.dod_optim_ema_update(None, -1, 0.5, None) == 1
+    a, b, c = _readers(lib)
+    assert a == b == c and a.startswith(b"dod_optim_ema_update:")
+    assert lib.dod_op_colsum_add(None, 4, 4, 4, None, None) == 1
+    a, b, c = _readers(lib)
+    assert a == b == c and a.startswith(b"dod_op_colsum_add:")
+    assert lib.dod_detect(*_null_args("dod_detect")) == 1
+    a, b, c = _readers(lib)
+    assert a == b == c and a.startswith(b"dod_detect:")
+
+
+def test_each_thread_reads_its_own_message(lib):
+    """two threads fail in two different entry points (ctypes releases the GIL around the calls); a barrier holds both until both calls
+    have returned, then each reads its own message through all three readers"""
+    import threading
+    barrier = threading.Barrier(2)
+    calls = [lambda: lib.dod_test_set_option(b"no_such_option", 1), lambda: lib.dod_track_update(*_null_args("dod_track_update"))]
+    want = [b"unknown test option 'no_such_option'", b"dod_track_update:"]
+    got = [None, None]
+
+    def work(i):
+        for _ in range(50):
+            rc = calls[i]()
+            barrier.wait(timeout=30)
+            got[i] = (rc, _readers(lib))
+            barrier.wait(timeout=30)
+            if rc != 1 or not all(m.startswith(want[i]) for m in got[i][1]):
+                break
+    threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(60)
+    for i in range(2):
+        assert got[i] is not None and got[i][0] == 1 and all(m.startswith(want[i]) for m in got[i][1]), (i, got[i])
+
+
+def test_check_maps_each_status_as_its_call_site_did(lib):
+    """_native.check: ValueError / KeyError / RuntimeError / RuntimeError for the four statuses, DodError beyond; the training steps'
+    mapping (models/_native_train.py) keeps RuntimeError for everything but DOD_ERR_INVALID.  The text is the calling thread's message."""
+    from dinov2_od_amd.models import _native_train as nt
+    rc = lib.dod_match_cost(*_null_args("dod_match_cost"))
+    for status, exc, texc in ((1, ValueError, ValueError), (2, KeyError, RuntimeError), (3, RuntimeError, RuntimeError), (4, RuntimeError, RuntimeError),
+                              (9, nat.DodError, RuntimeError)):
+        with pytest.raises(exc, match="dod_match_cost") as e:
+            nat.check(status)
+        assert type(e.value) is exc
+        with pytest.raises(texc, match="dod_match_cost") as e:
+            nt._check(status)
+        assert type(e.value) is texc
+    assert rc == 1
+    nat.check(0)
+    nt._check(0)
+    from dinov2_od_amd import optim
+    assert optim._check is nat.check
+
+
+def test_stream_slab_rule_in_a_sanitized_standalone_program(tmp_path):
+    """tests/stream_slabs_main.cpp includes only csrc/stream_slabs.h (the slot rule of both GEMM scratch pools); built with the host
+    compiler and -fsanitize=address,undefined (a report of either aborts the program) it checks that one stream keeps its slot, four
+    streams get four slots, a fifth evicts the least recently used and reset() forgets the owners."""
+    import shutil
+    import subprocess
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "clang++", "c++") if c and shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler found")
+    sanitize = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    probe = tmp_path / "probe.cpp"
+    probe.write_text("int main() { return 0; }\n")
+    static = None
+    for flags in (["-static-libasan", "-static-libubsan"], ["-static-libsan"], []):
+        p = subprocess.run([cxx] + sanitize + flags + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
+        if p.returncode == 0:
+            static = flags
+            break
+    if static is None:
+        pytest.skip(f"{cxx} cannot link a program with -fsanitize=address,undefined here: {(p.stderr.strip().splitlines() or ['?'])[-1]}")
+    exe = str(tmp_path / "stream_slabs_main")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer"] + sanitize + static +
+                       [os.path.join(ROOT, "tests", "stream_slabs_main.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout == "ok\n", r.stdout[-2000:] + r.stderr[-4000:]
+
+
+@pytest.mark.gpu
+def test_python_call_sites_raise_what_they_raised_with_the_entry_point_named():
+    """tracking, losses, matching and optim each make one call their own Python checks let through and the library rejects: ValueError,
+    as before, and the text now names the entry point"""
+    from dinov2_od_amd import losses, matching, optim, tracking
+    dev = torch.device("cuda")
+    trk = tracking.Tracker(num_streams=1, max_tracks=8, device=dev)
+    state = trk._ensure(dev)
+    trk._state = torch.empty(state.numel() + 8, dtype=torch.uint8, device=dev)[1:1 + state.numel()]      # misaligned: the table holds doubles
+    with pytest.raises(ValueError, match="^dod_track_reset:"):
+        trk.reset()
+    x = torch.zeros(4, 3, device=dev)
+    with pytest.raises(ValueError, match="^dod_set_criterion_forward:"):
+        losses._FocalFn.apply(x, torch.zeros(4, dtype=torch.int64, device=dev), 0.25, -1.0, "mean")          # a negative gamma
+    det = torch.zeros(2, 5, 3 + 4, device=dev)
+    labels, gt, offs = torch.zeros(2, dtype=torch.int64, device=dev), torch.full((2, 4), 0.5, device=dev), torch.tensor([0, 1, 2], dtype=torch.int32, device=dev)
+    with pytest.raises(ValueError, match="^dod_match_cost:"):
+        matching.match_cost(det, 3, labels, gt, offs, rows_from=2)                                       # rows_from >= B
+    w = torch.nn.Parameter(torch.ones(8, device=dev))
+    w.grad = torch.ones(8, device=dev)
+    with pytest.raises(ValueError, match="^dod_optim_clip_grad_norm:"):
+        optim.clip_grad_norm_([w], float("nan"))
