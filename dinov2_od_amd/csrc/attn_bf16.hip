@@ -17,6 +17,7 @@
 #include "dod_common.h"
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 #define AT_WAVES 4
 // AT_NQ (32-row query blocks per wave) is a template parameter of the kernel: 2 for large launches, 1 for small ones
@@ -35,7 +36,11 @@ typedef bf16x4 __attribute__((address_space(3))) * lds_bf16x4_ptr;
 // Softmax in the exp2 domain with the scale folded into one FMA: p = exp2(s*c - m*c), m = running max of the raw scores (c > 0).
 // NQ = 2 gives the scheduler two independent MFMA -> VALU -> MFMA chains to interleave (PMC on NQ = 1: 42 % of wave
 // cycles stalled on instruction dependencies, MFMA pipe 34 % busy) and halves the K/V fragment reads per MFMA.
-template <int TAIL, int NQ>
+// REF: the reference form, for the tiles behind the first of the fixed-reference pass (attn_bf16_body).  m_run is then the row's FROZEN reference,
+// the scaled maximum of key tile 0: p = exp2(s*c - m_run) and l += sum p, with no row maximum (its 46 v_max3 / v_max, the lane swap -- the
+// head of the chain S -> max -> exp -> pack -> P V --), no alpha and no rescale of O and l: about 128 plain instructions and 2 exponentials
+// less per tile at NQ = 2.  A masked key is still -inf -> p = +0.  p may exceed 1 here; what happens when it grows too far is the caller's.
+template <int TAIL, int NQ, bool REF>
 __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, const bf16x8 (&qf)[NQ][4], f32x16 (&o)[NQ][2],
                                           float (&m_run)[NQ], float (&l_run)[NQ], float c, int kbase, int N,
                                           int lr, int lh, int g16, int tq, int tp) {
@@ -65,22 +70,25 @@ __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, const 
           if (key >= N) s[q][kb][r] = -INFINITY;
         }
     }
-    float mx = s[q][0][0];
+    float alpha = 1.f;
+    if (!REF) {
+      float mx = s[q][0][0];
 #pragma unroll
-    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[q][0][r]);
-    if (KB == 2) {
+      for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[q][0][r]);
+      if (KB == 2) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[q][KB - 1][r]);
+        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[q][KB - 1][r]);
+      }
+      {   // other half's max by v_permlane32_swap (VALU; __shfl_xor goes through the LDS crossbar and an lgkmcnt wait)
+        const unsigned mb = __float_as_uint(mx);
+        const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
+        mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+      }
+      const float m_new = fmaxf(m_run[q], mx * c);            // scaled (exp2-domain) running max
+      alpha = __builtin_amdgcn_exp2f(m_run[q] - m_new);
+      m_run[q] = m_new;
     }
-    {   // other half's max by v_permlane32_swap (VALU; __shfl_xor goes through the LDS crossbar and an lgkmcnt wait)
-      const unsigned mb = __float_as_uint(mx);
-      const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-      mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-    }
-    const float m_new = fmaxf(m_run[q], mx * c);            // scaled (exp2-domain) running max
-    const float alpha = __builtin_amdgcn_exp2f(m_run[q] - m_new);
-    m_run[q] = m_new;
-    const float nm = -m_new;
+    const float nm = -m_run[q];
     float lsum;
     {      // Plain fp32 VALU only (one value per lane), and the file is built with -fno-slp-vectorize (_build.py) so that hipcc does not re-pack it:
            // `tools/probes/mfma_valu_overlap.hip` (profiles/r04_mfma_valu_overlap_probe.txt) shows that v_pk_*_f32 does NOT overlap an executing MFMA
@@ -100,12 +108,18 @@ __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, const 
         }
       lsum = (l0 + l1) + (l2 + l3);
     }
-    l_run[q] = fmaf(l_run[q], alpha, lsum);   // per-half partial; the halves are combined once at the end
-    // (a thresholded "lazy" rescale behind a wave-uniform branch -- the reference maximum moves only when a row's maximum exceeds it by 2^8 -- was
-    //  measured twice: 4 % slower on the packed form of round 3, 5 % slower on this one (attention 6.05 -> 6.38 ms, tools/experiments/r4_exp30.sh;
-    //  8 spilled registers): the branch splits the scheduling region, and the 64 multiplies it saves run beside the MFMAs anyway)
+    // Two ideas to keep apart.  (a) A thresholded "lazy" rescale -- the per-tile maximum stays, all of its max instructions and the swap, and a
+    //  wave-uniform branch INSIDE the tile moves the reference only when a row's maximum exceeds it by 2^8 -- was measured twice and lost: 4 % slower
+    //  on the packed form of round 3, 5 % slower on this one (attention 6.05 -> 6.38 ms, tools/experiments/r4_exp30.sh; 8 spilled registers): the
+    //  branch splits the scheduling region.  (b) REF removes the maximum itself from the tile and adds no branch to it; the one decision -- did a
+    //  row outgrow its reference -- is taken once, behind the last tile (attn_bf16_body).
+    if (REF) {
+      l_run[q] += lsum;                       // per-half partial; the halves are combined once at the end
+    } else {
+      l_run[q] = fmaf(l_run[q], alpha, lsum);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { o[q][0][r] *= alpha; o[q][1][r] *= alpha; }
+      for (int r = 0; r < 16; ++r) { o[q][0][r] *= alpha; o[q][1][r] *= alpha; }
+    }
     // P^T fragments: accumulator registers 8u..8u+7 of key block kb are the B operand of k-step 2kb+u
 #pragma unroll
     for (int s4 = 0; s4 < 2 * KB; ++s4) {
@@ -191,14 +205,24 @@ __device__ unsigned long long* g_attn_stamps = nullptr;
 
 // K/V ring, [slot][K|V][64 rows][128 B] = 48 KiB: ONE file-scope array, so that both bodies of the fused kernel address the same
 // compile-time-constant LDS locations (a pointer parameter cost the 64-rows-per-wave body three registers and a spill)
-__shared__ __attribute__((aligned(16))) char g_attn_smem[3 * 2 * AT_KV * 128];
+// Behind the ring: one vote word per wave (attn_bf16_body).  They live in THIS array on purpose: with a second __shared__ variable in the
+// kernel hipcc tags every LDS access with the variable it belongs to, then sees the LDS-DMA writes and the K fragment reads hit the same one,
+// and waits vmcnt(0) -- the two tiles in flight -- before the first ds_read of EVERY tile (measured: the kernel no faster than its parent).
+#define AT_RING_BYTES (3 * 2 * AT_KV * 128)
+__shared__ __attribute__((aligned(16))) char g_attn_smem[AT_RING_BYTES + 4 * AT_WAVES];
+__device__ unsigned int g_attn_reruns;                                  // workgroups that reran (dod_test_counter("attn_rerun"))
+// The fixed-reference pass holds for a row while its normaliser l_tot = sum_k exp2(s_k c - m0), m0 the scaled maximum of key tile 0, stays below
+// 2^60.  Every p is at most l_tot, so below the threshold the exp2 argument stays <= 60: the fp32 rounding of s c - m0 then moves p by at most
+// 60 * 2^-24 * ln 2 = 2.5e-6 relative (inside attention_cases.ACC_REL), bf16 keeps P's relative precision at any exponent, and an accumulator
+// |sum p v| <= l_tot max|v| cannot overflow fp32 for any |v| < 2^67.  Whatever lies beyond that shows as an accumulator that is not finite.
+constexpr float AT_REF_LMAX = 0x1p60f;
 // the kernel body for workgroup index `blk_` of a launch over query rows [q_lo, q_hi)
 // MX (fp8 mode, round 4): the context leaves as block-scaled e4m3 -- ctx is then a BYTE buffer [B*N, D], bs its e8m0 bytes [B*N][2][D / 64] --
 // the out-proj GEMM's operand, written here instead of by a quantisation pass over bf16 rows (a head's 64 columns are two blocks of 32)
 // DIET = false (test option "attn_diet" = 0): the full-width tail tile and the per-lane global pointers of the staging, as before
 template <int AT_NQ, bool MX, bool DIET>
 __device__ __forceinline__ void attn_bf16_body(const int blk_, const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
-                                               int N, int heads, int npairs, float scale_log2e, int q_lo, int q_hi, unsigned char* __restrict__ bs = nullptr) {
+                                               int N, int heads, int npairs, float scale_log2e, int q_lo, int q_hi, unsigned char* __restrict__ bs, int fixed_ref) {
   char* const smem = g_attn_smem;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
@@ -288,12 +312,6 @@ __device__ __forceinline__ void attn_bf16_body(const int blk_, const bf16_t* __r
 
   f32x16 o[AT_NQ][2];
   float m_run[AT_NQ], l_run[AT_NQ];
-#pragma unroll
-  for (int q = 0; q < AT_NQ; ++q) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { o[q][0][r] = 0.f; o[q][1][r] = 0.f; }
-    m_run[q] = -INFINITY; l_run[q] = 0.f;
-  }
   const bool active = __builtin_amdgcn_readfirstlane(q0) < q_hi;     // waves past the last row only stage and sync
 
   // tr-read lane geometry (ds_read_b64_tr_b16: 16-lane groups, lane 4q+p supplies row q, cols 4p..4p+3)
@@ -301,18 +319,14 @@ __device__ __forceinline__ void attn_bf16_body(const int blk_, const bf16_t* __r
 
   const int nkt = (N + AT_KV - 1) / AT_KV;
   const int nfull = N / AT_KV;                 // tiles without a masked key
-  AT_STAGE(0, 0)
-  if (nkt > 1) AT_STAGE(1, 1)
   int slot = 0;
   unsigned long long* stamps = ATTN_STAMPS;
   unsigned long long t_begin = 0, t_wait = 0;
-  if (stamps) t_begin = __builtin_amdgcn_s_memtime();
-  // full tiles in the loop, the masked last tile (if any) behind it: the loop body holds ONE form of the tile -- with the tail forms as
-  // branches of the body the register allocation of all of them met in one region (64-row body: 256 registers and spills; here 235)
-  for (int kt = 0; kt < nfull; ++kt) {
+  // tile kt has landed (tile kt+1 may fly) and every wave is behind tile kt-1, whose slot takes tile kt+2
+  auto tile_ready = [&](int kt) __attribute__((always_inline)) {
     unsigned long long tw0 = 0;
     if (stamps) tw0 = __builtin_amdgcn_s_memtime();
-    if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");     // tile kt landed, tile kt+1 may fly
+    if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -321,72 +335,147 @@ __device__ __forceinline__ void attn_bf16_body(const int blk_, const bf16_t* __r
       const int ns = slot >= 1 ? slot - 1 : 2;      // (slot + 2) % 3: the slot tile kt-1 just vacated
       AT_STAGE(ns, kt + 2)
     }
-    const char* sK = smem + slot * (2 * AT_KV * 128);
-    if (active) attn_tile<0, AT_NQ>(sK, sK + AT_KV * 128, qf, o, m_run, l_run, scale_log2e, kt * AT_KV, N, lr, lh, g16, tq, tp);
-    slot = slot == 2 ? 0 : slot + 1;
-  }
-  if (nfull < nkt) {      // the last tile, 1..63 keys: nothing left to stage
-    unsigned long long tw0 = 0;
-    if (stamps) tw0 = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (stamps) t_wait += __builtin_amdgcn_s_memtime() - tw0;
-    const char* sK = smem + slot * (2 * AT_KV * 128);
-    if (active) {
-      if (DIET && N - nfull * AT_KV <= 32) attn_tile<2, AT_NQ>(sK, sK + AT_KV * 128, qf, o, m_run, l_run, scale_log2e, nfull * AT_KV, N, lr, lh, g16, tq, tp);
-      else attn_tile<1, AT_NQ>(sK, sK + AT_KV * 128, qf, o, m_run, l_run, scale_log2e, nfull * AT_KV, N, lr, lh, g16, tq, tp);
+  };
+  // One pass over the keys: (m, l, O) of this wave's rows from nothing.
+  // FIX = false: every tile tracks the running row maximum and rescales O and l by alpha.
+  // FIX = true: tile 0 does, and stands in front of the loop; every tile behind it -- the loop of full tiles and the masked last one -- is the
+  // reference form (attn_tile REF), which subtracts tile 0's maximum.  Softmax does not care which reference is subtracted; the rows whose
+  // maximum lies in tile 0 get the very bits of FIX = false (alpha is exactly 1 there).
+  // Either way the loop body holds ONE form of the tile -- with the tail forms as branches of the body the register allocation of all of them
+  // met in one region (64-row body: 256 registers and spills; here 235).
+  auto pass = [&](auto fix_) __attribute__((always_inline)) {
+    constexpr bool FIX = decltype(fix_)::value;
+#pragma unroll
+    for (int q = 0; q < AT_NQ; ++q) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { o[q][0][r] = 0.f; o[q][1][r] = 0.f; }
+      m_run[q] = -INFINITY; l_run[q] = 0.f;
     }
-  }
-
-  if (stamps && tid == 0) {
-    unsigned long long* o_ = stamps + (size_t)blockIdx.x * 6;
-    o_[0] = __builtin_amdgcn_s_memtime() - t_begin; o_[1] = t_wait; o_[2] = nkt; o_[3] = active ? 1 : 0;
-    o_[4] = rt_entry; o_[5] = __builtin_amdgcn_s_memrealtime();
-  }
-#pragma unroll
-  for (int qi = 0; qi < AT_NQ; ++qi) {
-    const float l_tot = l_run[qi] + __shfl_xor(l_run[qi], 32, 64);
-    const float inv = 1.0f / l_tot;
-    const int q = q0 + qi * 32 + lr;
-    if (MX) {
-      // block db of this head = columns db*32 .. +31 of query q: 16 of them in this lane, 16 in lane ^ 32 (every lane takes part in the shuffle)
-      const bool okq = active && q < q_hi;
-      unsigned char* op8 = reinterpret_cast<unsigned char*>(ctx) + ((size_t)b * N + q) * D + h * 64;
-#pragma unroll
-      for (int db = 0; db < 2; ++db) {
-        float amax = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) amax = fmaxf(amax, fabsf(o[qi][db][r] * inv));
-        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        const unsigned eb = mx_ebyte(amax);
-        const float sc = inv * mx_inv_scale(eb);
-        if (okq) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<unsigned*>(op8 + db * 32 + 8 * g + 4 * lh) = pack4_fp8(o[qi][db][4 * g] * sc, o[qi][db][4 * g + 1] * sc, o[qi][db][4 * g + 2] * sc, o[qi][db][4 * g + 3] * sc);
-          if (lh == 0) bs[((size_t)b * N + q) * (D >> 5) + mx_scale_off(D, h * 2 + db)] = (unsigned char)eb;
-        }
+    AT_STAGE(0, 0)
+    if (nkt > 1) AT_STAGE(1, 1)
+    slot = 0;
+    int kt = 0;
+    if (FIX) {      // only with nkt > 1: tile 0 is a full tile
+      tile_ready(0);
+      if (active) attn_tile<0, AT_NQ, false>(smem, smem + AT_KV * 128, qf, o, m_run, l_run, scale_log2e, 0, N, lr, lh, g16, tq, tp);
+      slot = 1;
+      kt = 1;
+    }
+    for (; kt < nfull; ++kt) {
+      tile_ready(kt);
+      const char* sK = smem + slot * (2 * AT_KV * 128);
+      if (active) attn_tile<0, AT_NQ, FIX>(sK, sK + AT_KV * 128, qf, o, m_run, l_run, scale_log2e, kt * AT_KV, N, lr, lh, g16, tq, tp);
+      slot = slot == 2 ? 0 : slot + 1;
+    }
+    if (nfull < nkt) {      // the last tile, 1..63 keys: nothing left to stage
+      tile_ready(nfull);
+      const char* sK = smem + slot * (2 * AT_KV * 128);
+      if (active) {
+        if (DIET && N - nfull * AT_KV <= 32) attn_tile<2, AT_NQ, FIX>(sK, sK + AT_KV * 128, qf, o, m_run, l_run, scale_log2e, nfull * AT_KV, N, lr, lh, g16, tq, tp);
+        else attn_tile<1, AT_NQ, FIX>(sK, sK + AT_KV * 128, qf, o, m_run, l_run, scale_log2e, nfull * AT_KV, N, lr, lh, g16, tq, tp);
       }
-    } else if (active && q < q_hi) {
-      bf16_t* op = ctx + ((size_t)b * N + q) * D + h * 64;
-#pragma unroll
-      for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          uint2 pk;
-          pk.x = pack2bf(o[qi][db][4 * g] * inv, o[qi][db][4 * g + 1] * inv);
-          pk.y = pack2bf(o[qi][db][4 * g + 2] * inv, o[qi][db][4 * g + 3] * inv);
-          *reinterpret_cast<uint2*>(op + db * 32 + 8 * g + 4 * lh) = pk;
-        }
     }
+  };
+  // the rows `sel` of this lane leave as O / l_tot
+  auto store_rows = [&](const float (&l_tot)[AT_NQ], const bool (&sel)[AT_NQ]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int qi = 0; qi < AT_NQ; ++qi) {
+      const float inv = 1.0f / l_tot[qi];
+      const int q = q0 + qi * 32 + lr;
+      const bool okq = active && q < q_hi && sel[qi];
+      if (MX) {
+        // block db of this head = columns db*32 .. +31 of query q: 16 of them in this lane, 16 in lane ^ 32 (every lane takes part in the shuffle;
+        // only the stores are predicated)
+        unsigned char* op8 = reinterpret_cast<unsigned char*>(ctx) + ((size_t)b * N + q) * D + h * 64;
+#pragma unroll
+        for (int db = 0; db < 2; ++db) {
+          float amax = 0.f;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) amax = fmaxf(amax, fabsf(o[qi][db][r] * inv));
+          amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+          const unsigned eb = mx_ebyte(amax);
+          const float sc = inv * mx_inv_scale(eb);
+          if (okq) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+              *reinterpret_cast<unsigned*>(op8 + db * 32 + 8 * g + 4 * lh) = pack4_fp8(o[qi][db][4 * g] * sc, o[qi][db][4 * g + 1] * sc, o[qi][db][4 * g + 2] * sc, o[qi][db][4 * g + 3] * sc);
+            if (lh == 0) bs[((size_t)b * N + q) * (D >> 5) + mx_scale_off(D, h * 2 + db)] = (unsigned char)eb;
+          }
+        }
+      } else if (okq) {
+        bf16_t* op = ctx + ((size_t)b * N + q) * D + h * 64;
+#pragma unroll
+        for (int db = 0; db < 2; ++db)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            uint2 pk;
+            pk.x = pack2bf(o[qi][db][4 * g] * inv, o[qi][db][4 * g + 1] * inv);
+            pk.y = pack2bf(o[qi][db][4 * g + 2] * inv, o[qi][db][4 * g + 3] * inv);
+            *reinterpret_cast<uint2*>(op + db * 32 + 8 * g + 4 * lh) = pk;
+          }
+      }
+    }
+  };
+  auto write_stamps = [&]() __attribute__((always_inline)) {
+    if (stamps && tid == 0) {
+      unsigned long long* o_ = stamps + (size_t)blockIdx.x * 6;
+      o_[0] = __builtin_amdgcn_s_memtime() - t_begin; o_[1] = t_wait; o_[2] = nkt; o_[3] = active ? 1 : 0;
+      o_[4] = rt_entry; o_[5] = __builtin_amdgcn_s_memrealtime();
+    }
+    stamps = nullptr;      // the first pass only
+  };
+
+  float l_tot[AT_NQ];
+  bool redo[AT_NQ];      // rows the running-maximum pass (re)computes and stores
+  if (stamps) t_begin = __builtin_amdgcn_s_memtime();
+  // fixed_ref = 0 (test option "attn_fixed_ref"): every row goes through the running-maximum pass and nothing runs in front of it -- the
+  // arithmetic before the reference form existed, from this same instantiation.  A sequence of one key tile has no tile behind the first.
+  if (fixed_ref && nkt > 1) {
+    pass(std::true_type{});
+    write_stamps();
+    // Did a row outgrow its reference?  Taken ONCE, here, not per tile.  A row is bad when its normaliser (both halves) is not below
+    // AT_REF_LMAX or one of its 64 accumulators is not finite: chk = sum of o * 0 is (+-)0 when every o is finite and NaN otherwise, and goes
+    // through the same combine as l (l + 0 = l: a good row's l_tot keeps today's bits).
+    int any_bad = 0;
+#pragma unroll
+    for (int qi = 0; qi < AT_NQ; ++qi) {
+      float c0 = 0.f, c1 = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { c0 = fmaf(o[qi][0][r], 0.f, c0); c1 = fmaf(o[qi][1][r], 0.f, c1); }
+      const float lc = l_run[qi] + (c0 + c1);
+      l_tot[qi] = lc + __shfl_xor(lc, 32, 64);
+      redo[qi] = !(l_tot[qi] < AT_REF_LMAX);      // a row's two half-lanes agree: l_tot is the same sum in both
+      any_bad |= redo[qi] ? 1 : 0;
+    }
+    // the workgroup's vote: one LDS word per wave, one barrier.  The barrier also puts every wave behind its last tile: the ring is free.
+    const int wave_bad = __builtin_amdgcn_readfirstlane(__any(any_bad) ? 1 : 0);
+    int* const vote = reinterpret_cast<int*>(smem + AT_RING_BYTES);
+    if (lane == 0) vote[wid] = wave_bad;
+    bool good[AT_NQ];
+#pragma unroll
+    for (int qi = 0; qi < AT_NQ; ++qi) good[qi] = !redo[qi];
+    store_rows(l_tot, good);
+    __syncthreads();
+    const int wg_bad = __builtin_amdgcn_readfirstlane(vote[0] | vote[1] | vote[2] | vote[3]);
+    if (!wg_bad) return;      // every workgroup of ordinary activations ends here: the path costs the vote
+    if (tid == 0) atomicAdd(&g_attn_reruns, 1u);
+  } else {
+#pragma unroll
+    for (int qi = 0; qi < AT_NQ; ++qi) redo[qi] = true;
   }
+  // The workgroup restages from tile 0 and runs the running-maximum pass for all of its rows, but stores ONLY the bad ones (per lane): a row's
+  // bits depend on its own q and its image's K/V alone -- not on its workgroup mates, not on the body (32 or 64 rows per wave), not on the batch.
+  pass(std::false_type{});
+  write_stamps();
+#pragma unroll
+  for (int qi = 0; qi < AT_NQ; ++qi) l_tot[qi] = l_run[qi] + __shfl_xor(l_run[qi], 32, 64);
+  store_rows(l_tot, redo);
 }
 
 template <int AT_NQ, bool MX, bool DIET>
 __global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
-                                                        int N, int heads, int npairs, float scale_log2e, int q_lo, int q_hi, unsigned char* __restrict__ bs) {
-  attn_bf16_body<AT_NQ, MX, DIET>(blockIdx.x, qkv, ctx, N, heads, npairs, scale_log2e, q_lo, q_hi, bs);
+                                                        int N, int heads, int npairs, float scale_log2e, int q_lo, int q_hi, unsigned char* __restrict__ bs, int fixed_ref) {
+  attn_bf16_body<AT_NQ, MX, DIET>(blockIdx.x, qkv, ctx, N, heads, npairs, scale_log2e, q_lo, q_hi, bs, fixed_ref);
 }
 // ONE launch for a sequence whose last 256-row block is short (N = 1370: 5 blocks + 90 rows): workgroups [0, main_blocks) run the
 // 64-rows-per-wave body over rows [0, q_main), the workgroups behind them the 32-rows-per-wave body over the remainder -- dispatched
@@ -394,9 +483,9 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const bf16_t* __restr
 // took 62.6 us per layer for 6.6 % of the rows, profiles/r03_bench_bf16_kernel_stats.csv).  main_blocks % 8 == 0 keeps both XCD maps.
 template <bool MX, bool DIET>
 __global__ __launch_bounds__(256, 2) void attn_bf16_fused_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
-                                                              int N, int heads, int npairs, float scale_log2e, int main_blocks, int q_main, unsigned char* __restrict__ bs) {
-  if ((int)blockIdx.x < main_blocks) attn_bf16_body<2, MX, DIET>(blockIdx.x, qkv, ctx, N, heads, npairs, scale_log2e, 0, q_main, bs);
-  else attn_bf16_body<1, MX, DIET>((int)blockIdx.x - main_blocks, qkv, ctx, N, heads, npairs, scale_log2e, q_main, N, bs);
+                                                              int N, int heads, int npairs, float scale_log2e, int main_blocks, int q_main, unsigned char* __restrict__ bs, int fixed_ref) {
+  if ((int)blockIdx.x < main_blocks) attn_bf16_body<2, MX, DIET>(blockIdx.x, qkv, ctx, N, heads, npairs, scale_log2e, 0, q_main, bs, fixed_ref);
+  else attn_bf16_body<1, MX, DIET>((int)blockIdx.x - main_blocks, qkv, ctx, N, heads, npairs, scale_log2e, q_main, N, bs, fixed_ref);
 }
 
 // (Round 4 built a 512-thread PING-PONG form of this kernel -- both waves of every SIMD in one workgroup, phased against each other with the
@@ -413,7 +502,7 @@ extern "C" int dod_debug_attn_stamps(void* dev_buf) {
 #endif
 
 // the kernel of a launch: NQ = 1 / 2 query blocks per wave, 0 = the fused kernel; every form has the same parameters
-typedef void (*attn_kern_t)(const bf16_t*, bf16_t*, int, int, int, float, int, int, unsigned char*);
+typedef void (*attn_kern_t)(const bf16_t*, bf16_t*, int, int, int, float, int, int, unsigned char*, int);
 template <int NQ>
 static attn_kern_t attn_pick(bool mx, bool diet) {
   if constexpr (NQ == 0) return mx ? (diet ? attn_bf16_fused_kernel<true, true> : attn_bf16_fused_kernel<true, false>)
@@ -423,6 +512,10 @@ static attn_kern_t attn_pick(bool mx, bool diet) {
 }
 static std::atomic<long> g_attn_half_tiles{0};
 long attn_half_tile_count() { return g_attn_half_tiles.load(); }
+long attn_rerun_count() {      // a synchronising copy: a test facility, not on the forward path
+  unsigned int v = 0;
+  return hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_attn_reruns), sizeof(v)) == hipSuccess ? (long)v : -1;
+}
 
 int launch_attn_bf16(const bf16_t* qkv, bf16_t* ctx, int B, int N, int heads, float scale, hipStream_t s, unsigned char* ctx_bs) {
   if (B <= 0 || N <= 0 || heads <= 0) return 1;
@@ -431,6 +524,7 @@ int launch_attn_bf16(const bf16_t* qkv, bf16_t* ctx, int B, int N, int heads, fl
   const int npairs = B * heads, pairs8 = (npairs + 7) / 8 * 8;
   const float c = scale * 1.44269504088896340736f;
   const bool diet = dod_option(DOD_OPT_ATTN_DIET) != 0;                  // 0: the full-width tail tile and pointer staging (bit-identical)
+  const int fixed_ref = dod_option(DOD_OPT_ATTN_FIXED_REF) != 0;         // 0: the running row maximum for every row
   if (diet && (N - 1) % AT_KV < 32) ++g_attn_half_tiles;                 // the last key tile holds 1..32 keys
   // 64 query rows per wave once the grid still fills the chip several times over (measured: +5 % at B*heads = 768,
   // -12 % at 96), else 32
@@ -451,18 +545,18 @@ int launch_attn_bf16(const bf16_t* qkv, bf16_t* ctx, int B, int N, int heads, fl
       static const int pad = [] { const char* v = getenv("DINODET_ATTN_LDS_PAD"); return v ? atoi(v) : 0; }();
       if (pad > 0 && !mx) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bf16_fused_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, pad);
-        hipLaunchKernelGGL((attn_bf16_fused_kernel<false, true>), dim3(pairs8 * nqb + pairs8), dim3(256), pad, s, qkv, ctx, N, heads, npairs, c, pairs8 * nqb, q_main, ctx_bs);
+        hipLaunchKernelGGL((attn_bf16_fused_kernel<false, true>), dim3(pairs8 * nqb + pairs8), dim3(256), pad, s, qkv, ctx, N, heads, npairs, c, pairs8 * nqb, q_main, ctx_bs, fixed_ref);
         return hipGetLastError() == hipSuccess ? 0 : 3;
       }
 #endif
-      hipLaunchKernelGGL(attn_pick<0>(mx, diet), dim3(pairs8 * nqb + pairs8), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, pairs8 * nqb, q_main, ctx_bs);
+      hipLaunchKernelGGL(attn_pick<0>(mx, diet), dim3(pairs8 * nqb + pairs8), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, pairs8 * nqb, q_main, ctx_bs, fixed_ref);
     } else {
-      hipLaunchKernelGGL(attn_pick<2>(mx, diet), dim3(pairs8 * nqb), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, 0, q_main, ctx_bs);
-      if (split) hipLaunchKernelGGL(attn_pick<1>(mx, diet), dim3(pairs8), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, q_main, N, ctx_bs);
+      hipLaunchKernelGGL(attn_pick<2>(mx, diet), dim3(pairs8 * nqb), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, 0, q_main, ctx_bs, fixed_ref);
+      if (split) hipLaunchKernelGGL(attn_pick<1>(mx, diet), dim3(pairs8), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, q_main, N, ctx_bs, fixed_ref);
     }
   } else {
     const int nqb = (N + AT_WAVES * 32 - 1) / (AT_WAVES * 32);
-    hipLaunchKernelGGL(attn_pick<1>(mx, diet), dim3(pairs8 * nqb), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, 0, N, ctx_bs);
+    hipLaunchKernelGGL(attn_pick<1>(mx, diet), dim3(pairs8 * nqb), dim3(256), 0, s, qkv, ctx, N, heads, npairs, c, 0, N, ctx_bs, fixed_ref);
   }
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }

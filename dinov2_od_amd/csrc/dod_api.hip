@@ -43,10 +43,10 @@ static bool check_common(dod_handle* h, int B, int H, int W, int* rc) {
 }
 
 // ---- test hooks (dod_common.h DOD_OPT_*)
-static std::atomic<int> g_options[DOD_OPT_COUNT] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+static std::atomic<int> g_options[DOD_OPT_COUNT] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
 int dod_option(int which) { return which >= 0 && which < DOD_OPT_COUNT ? g_options[which].load() : -1; }
 static const char* const k_option_names[DOD_OPT_COUNT] = {"tailsplit", "dec_fused_split", "mha_chunk_images", "no_fused_patch", "ln_fold", "deterministic", "f32_ksplit",
-                                                       "attn_bwd_flash", "epi_regmath", "f32x3_tile", "attn_diet"};
+                                                       "attn_bwd_flash", "epi_regmath", "f32x3_tile", "attn_diet", "attn_fixed_ref"};
 
 static std::atomic<long> g_form_launches[FORM_COUNT];
 static const char* const k_form_names[FORM_COUNT] = {"bf16_128_r2", "bf16_128_r3", "bf16_m16", "k64", "ppm", "x3_16w", "x3_pp", "h2", "fp8_rows", "fp8mx_256x128",
@@ -67,6 +67,7 @@ long dod_test_counter(const char* name) {
   if (name && !strcmp(name, "f32_ksplits")) return gemm_f32_ksplit_count();
   if (name && !strcmp(name, "epi_regmath")) return gemm_epi_regmath_count();
   if (name && !strcmp(name, "attn_diet")) return attn_half_tile_count();
+  if (name && !strcmp(name, "attn_rerun")) return attn_rerun_count();
   if (name && !strcmp(name, "f32x3_launches")) return gemm_f32x3_count(0);
   if (name && !strcmp(name, "f32x3_wide_launches")) return gemm_f32x3_count(1);
   if (name && !strcmp(name, "optim_launches")) return optim_launch_count();

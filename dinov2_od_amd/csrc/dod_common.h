@@ -47,6 +47,7 @@ enum { DOD_OPT_TAILSPLIT = 0,         // GEMM wave-quantisation tail split: 0 of
        DOD_OPT_EPI_REGMATH,           // 16-wave bf16 GEMM, plain bf16 rows (gemm_x3.hip): 0 = the LDS-staged epilogue, 1 = epilogue math on the accumulators (shipped)
        DOD_OPT_F32X3_TILE,            // fp32-in bf16 split GEMM (gemm_f32x3.hip): 64 / 128 = that tile for every product (0 = the shipped rule)
        DOD_OPT_ATTN_DIET,             // bf16 flash attention (attn_bf16.hip): 0 = the full-width tail key tile and per-lane pointer staging, 1 = half tail tile + descriptor staging (shipped)
+       DOD_OPT_ATTN_FIXED_REF,        // bf16 flash attention (attn_bf16.hip): 0 = running row maximum and rescale for every row, 1 = one softmax reference per row from key tile 0, rows that overflow rerun (shipped)
        DOD_OPT_COUNT };
 int dod_option(int which);            // dod_api.hip; -1 when unset
 long gemm_tail_split_count();         // gemm_dispatch.hip: GEMM calls that took the tail-split path so far
@@ -54,6 +55,7 @@ long optim_launch_count();            // optim.hip: launches of the optimizer en
 long optim_constant(int which);       // optim.hip: 0 elements per workgroup, 1 / 2 / 3 tensors per update / norm / ema launch
 long gemm_rem_cut_count();            // gemm_dispatch.hip: GEMM calls whose short last round ran as a launch of its own
 long attn_half_tile_count();          // attn_bf16.hip: attention launches whose last key tile ran at half width
+long attn_rerun_count();              // attn_bf16.hip: workgroups that reran rows with the running maximum (reads a device word back: synchronises; tests only)
 long gemm_epi_regmath_count();        // gemm_dispatch.hip: launches of the 16-wave bf16 GEMM that took the register epilogue
 // kernel launches per inference GEMM form so far (dod_api.hip; dod_test_counter("form_<name>"), names in include/dinodet.h): counted by gemm_dispatch
 enum { FORM_BF16_128_R2 = 0, FORM_BF16_128_R3, FORM_BF16_M16, FORM_K64, FORM_PPM, FORM_X3_16W, FORM_X3_PP, FORM_H2, FORM_FP8_ROWS, FORM_FP8MX_256X128,
